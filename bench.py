@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GP refit + NORA acquisition cycle (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cycle|farm]
+    python bench.py --gpus N --steps K --warmup W [--workload cycle|farm] [--dump-outputs DIR]
 
 ``--workload cycle`` (default; BASELINE configs[2] at N=1, configs[3] at N>1).  One *step* is one
 active-learning cycle of GPry's hot path at EXACTLY N_train = 4096 (16-d synthetic posterior,
@@ -61,6 +61,7 @@ F64_MFMA_PEAK_TFLOPS = 78.6   # MI355X public spec (FP64 matrix == FP64 vector);
 #                               matrix-core table has no f64 row, see DESIGN.md
 HBM_PEAK_GBPS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 CPU_CHUNK = 32768             # the CPU sweep is chunked at 32 768 candidates
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most 64 MB in all
 
 
 def synthetic(N, d, M, seed_train=0, seed_cand=1):
@@ -82,6 +83,24 @@ def synthetic(N, d, M, seed_train=0, seed_cand=1):
         b = min(M, a + (1 << 18))
         Xc[a:b] = np.clip(rng_c.standard_normal((b - a, d)) @ (math.sqrt(1.5) * Lc).T, -5, 5)
     return bounds, X, truth(X), Xc, truth
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: what the timed path returned in its last step, one float64 ``<name>.npy`` per array, so that
+    two builds can be compared output for output on the same seeded inputs.  Beyond ``DUMP_LIMIT_BYTES`` in all, every
+    array keeps the same fixed, seeded sample of its rows (arrays of equal length keep the same rows)."""
+    arrays = {k: np.atleast_1d(np.array(v, dtype=np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        for k, a in arrays.items():
+            n = int(len(a) * DUMP_LIMIT_BYTES / total)
+            arrays[k] = a[np.sort(np.random.default_rng(0).choice(len(a), n, replace=False))]
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:   # outputs, not sources, wherever the directory lands
+            f.write("*\n")
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _cpu_model():
@@ -616,6 +635,8 @@ def run_farm(args, rank, world, local_rank):
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"theta": gpr.kernel_.theta, "lml": gpr.log_marginal_likelihood_value_})
     evals_rank = (gpr.n_eval_loglike - e0) / K
     if comm is not None:
         elapsed = float(comm.allreduce_max(np.array([elapsed]))[0])
@@ -713,6 +734,8 @@ def run_config1(args):
     T = {k_: dev.timing(k_) for k_ in names}
     dev.set_option("timing", 0)
     res = dev.sweep_fetch(want=("y", "sigma"))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mean": res["y"], "std": res["sigma"]})
     same = {"bit_identical": bool(np.array_equal(res["y"], mean0) and np.array_equal(res["sigma"], std0)),
             "max_abs_mean": float(np.max(np.abs(res["y"] - mean0))), "max_abs_std": float(np.max(np.abs(res["sigma"] - std0)))}
     # through the host boundary
@@ -973,9 +996,13 @@ def main(argv=None):
     ap.add_argument("--allow-gloo", action="store_true")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--extras", choices=["auto", "off"], default="auto")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     group_mode = args.workload == "farm" and args.mode == "group"
@@ -1053,19 +1080,19 @@ def main(argv=None):
     first_fit = {"ms": (time.perf_counter() - t0) * 1e3, "lml_grad_evals": gpr.n_eval_loglike - e0,
                  "N_train": gpr.n, "note": "unfitted model: one run from a random start (gpry/gpr.py:917-918), "
                                            "includes context creation and allocation"}
-    X_new, _, _ = acq.multi_add(gpr, n_points=npts, rng=rng)
+    X_new, y_lies, acq_vals = acq.multi_add(gpr, n_points=npts, rng=rng)
 
     host_t = {"refit": 0.0, "acq": 0.0}
     n_seen = []
     work = {"sweep_flops": 0.0, "kb_bytes": 0.0, "potrf_flops_each": []}
 
     def step(acq=acq):
-        nonlocal X_new
+        nonlocal X_new, y_lies, acq_vals
         t_a = time.perf_counter()
         rewind(gpr, n_base)
         gpr.append_to_data(X_new, truth(X_new), fit_gpr="simple")
         t_b = time.perf_counter()
-        X_new, _, _ = acq.multi_add(gpr, n_points=npts, rng=rng)
+        X_new, y_lies, acq_vals = acq.multi_add(gpr, n_points=npts, rng=rng)
         host_t["refit"] += t_b - t_a
         host_t["acq"] += time.perf_counter() - t_b
         n = gpr.n
@@ -1094,6 +1121,10 @@ def main(argv=None):
         cache_models += acq.stats.get("cache_models", 0)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step: the refit's hyper-parameters and LML, then the proposals of multi_add
+        dump_outputs(args.dump_outputs, {"theta": gpr.kernel_.theta, "lml": gpr.log_marginal_likelihood_value_,
+                                         "proposals": X_new, "y_lies": y_lies, "acq": acq_vals})
     if comm is not None:
         elapsed = float(comm.allreduce_max(np.array([elapsed]))[0])
     lml_evals = (gpr.n_eval_loglike - lml0) / K

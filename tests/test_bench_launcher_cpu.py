@@ -80,6 +80,41 @@ def test_a_rank_that_fails_after_the_rendezvous_leaves_rank_0s_snapshot():
     assert res["error"]["failed_ranks"] == [1] and res["error"]["exit_codes"][1] == 8
 
 
+def test_one_rank_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """``--dump-outputs DIR``: float64 arrays of the last of exactly ``--steps`` timed steps, the same from run to run."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, DOUBLE, "--gpus", "1"] + SMALL +
+                             ["--steps", "3", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, env=env, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        res = json.loads([ln for ln in out.stdout.splitlines() if ln.lstrip().startswith("{")][-1])
+        assert res["steps"] == 3 and res["config"]["N_train_per_step"] == [96] * 3 and res["ms_per_step"] > 0
+        dumps.append({f.stem: np.load(f) for f in (tmp_path / run).glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["acq", "lml", "proposals", "theta", "y_lies"]
+    assert a["proposals"].shape == (3, 3) and a["theta"].shape == (4,)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.all(np.isfinite(a[k]))
+        np.testing.assert_array_equal(a[k], b[k])
+
+
+def test_dump_outputs_keeps_the_same_seeded_rows_under_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"mean": np.arange(1000.0), "std": -np.arange(1000.0)})
+    a, b = ({k: np.load(tmp_path / run / f"{k}.npy") for k in ("mean", "std")} for run in ("a", "b"))
+    assert 0 < a["mean"].nbytes + a["std"].nbytes <= 8000
+    np.testing.assert_array_equal(a["std"], -a["mean"])          # equal-length arrays keep the same rows
+    np.testing.assert_array_equal(a["mean"], b["mean"])
+
+
 def test_the_watchdog_ends_a_hanging_run():
     out = _launch(2, ["--allow-gloo"], {"GPRY_BENCH_DOUBLE_HANG_RANK": "1"}, timeout=12)
     assert out.returncode != 0 and "time limit" in out.stderr

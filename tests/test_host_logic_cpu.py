@@ -385,3 +385,26 @@ def test_header_is_plain_c99_and_the_c_client_compiles():
     src = os.path.join(ROOT, "tests", "c_abi", "c_abi_smoke.c")
     subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only",
                     "-I", os.path.join(ROOT, "include"), src], check=True)
+
+
+def test_patch_gpry_rebinds_every_name_the_runner_looks_up(monkeypatch):
+    """``patch_gpry()`` on a stand-in ``gpry`` package (the real one is not part of this repository): afterwards the
+    names ``gpry.run.Runner`` resolves at run time are the device-backed classes."""
+    import sys
+    import types
+    from gpry_amd.gp_acquisition import NORA, BatchOptimizer, GenericGPAcquisition
+    from gpry_amd.gpr import GaussianProcessRegressor
+    from gpry_amd.integration import patch_gpry
+    from gpry_amd.preprocessing import Normalize_bounds, Normalize_y
+    pkg = types.ModuleType("gpry")
+    monkeypatch.setitem(sys.modules, "gpry", pkg)
+    for sub in ("gpr", "gp_acquisition", "run"):
+        mod = types.ModuleType("gpry." + sub)
+        monkeypatch.setitem(sys.modules, "gpry." + sub, mod)
+        setattr(pkg, sub, mod)
+    assert patch_gpry() is pkg
+    assert pkg.gpr.GaussianProcessRegressor is GaussianProcessRegressor
+    assert pkg.run.GaussianProcessRegressor is GaussianProcessRegressor
+    assert pkg.gp_acquisition.NORA is NORA and pkg.gp_acquisition.BatchOptimizer is BatchOptimizer
+    assert pkg.run.GenericGPAcquisition is GenericGPAcquisition
+    assert pkg.run.Normalize_bounds is Normalize_bounds and pkg.run.Normalize_y is Normalize_y
