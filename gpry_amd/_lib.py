@@ -68,6 +68,7 @@ SIGNATURES = {
     "gpry_sweep_logexp": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_double, C.c_double,
                                     C.c_double, _vp, _vp, _vp, _P(C.c_int64)]),
     "gpry_sweep_fetch": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "gpry_sweep_prune_info": (C.c_int, [_vp, _vp, _vp]),
     "gpry_sweep_topk": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _P(C.c_int64),
                                   _P(C.c_double)]),
     "gpry_kb_reset": (C.c_int, [_vp]),
@@ -458,6 +459,18 @@ class Device:
         out = {k: (np.empty(M) if k in want else None) for k in ("y", "sigma", "acq")}
         self._check(self._lib.gpry_sweep_fetch(self._h, M, _ptr(out["y"]), _ptr(out["sigma"]),
                                                _ptr(out["acq"])), "gpry_sweep_fetch")
+        return out
+
+    PRUNE_INFO = ("pruned", "M", "K_prime", "rounds", "contracted", "completed", "K", "survivors")
+
+    def sweep_prune_info(self):
+        """Statistics of the last pruned sweep (option ``sweep_prune``, ``gpry_sweep_prune_info``)."""
+        info = np.zeros(len(self.PRUNE_INFO), dtype=np.int64)
+        dinfo = np.zeros(5)
+        self._check(self._lib.gpry_sweep_prune_info(self._h, _ptr(info), _ptr(dinfo)), "gpry_sweep_prune_info")
+        out = {k: int(v) for k, v in zip(self.PRUNE_INFO, info)}
+        out["tau"] = float(dinfo[0])
+        out["stage_ms"] = dict(zip(("sweep_mean", "sweep_prune_select", "sweep_compact", "sweep_prune_gemm"), dinfo[1:].tolist()))
         return out
 
     def sweep_topk(self, Kp, exclude=None):

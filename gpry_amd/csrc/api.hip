@@ -2,6 +2,7 @@
 // fused NORA sweep, shortlist selection and Kriging-believer support.
 #include "common.h"
 #include <algorithm>
+#include <functional>
 
 static int require_model(gpry_ctx* ctx, bool need_factor) {
     if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
@@ -650,6 +651,69 @@ __global__ void sweep_finish_kernel(const double* __restrict__ mean_part, const 
     acq_all[m] = logexp_value(y, sd, fp.zeta, fp.baseline, fp.sigma_n);
 }
 
+// A pruned sweep (option "sweep_prune"): the sigma of a candidate that is not (yet) contracted.  No evaluated std takes this
+// value (sqrt(var) * y_std >= 0, or NaN), so a shortlist record with it is known to carry a bound, not an exact acquisition.
+#define PRUNED_SIGMA (-1.0)
+
+// Stage A of a pruned sweep: y exactly as sweep_finish_kernel computes it, and the acquisition the candidate would have with
+// ss = 0 (the prior sigma) -- an upper bound of its exact value, bit for bit: the finish sums non-negative per-tile terms
+// (ss >= 0), so var = C - ss <= C, and every later step (sqrt, * y_std, the rounded square, - sigma_n^2, max, log) is
+// monotone under round-to-nearest; y and the linear term are the same operations on the same values.  acq_all starts as the
+// bound, sig_all as PRUNED_SIGMA; the contracted candidates overwrite both (sweep_scatter_finish_kernel).
+__global__ void sweep_mean_kernel(const double* __restrict__ mean_part, int nt_mean, int64_t ldp, int64_t m0, int64_t mc,
+                                  const uint8_t* __restrict__ mask, double* __restrict__ y_all, double* __restrict__ sig_all,
+                                  double* __restrict__ acq_all, double* __restrict__ ub, FinishParams fp) {
+    int64_t ml = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ml >= mc) return;
+    int64_t m = m0 + ml;
+    double mu_ = 0.0;
+#pragma unroll 8
+    for (int t = 0; t < nt_mean; t++) mu_ += mean_part[(int64_t)t * ldp + ml];
+    double y = mu_ * fp.y_std + fp.y_mean;
+    y = fmin(y, fp.clip_hi);
+    unsigned mk = mask ? mask[m] : 0u;
+    if (mk) y = -INFINITY;
+    y_all[m] = y;
+    double var = fp.C - 0.0;
+    if (var < 0.0) var = 0.0;
+    double sd = sqrt(var) * fp.y_std;
+    if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
+    const double a = logexp_value(y, sd, fp.zeta, fp.baseline, fp.sigma_n);
+    ub[m] = a;
+    acq_all[m] = a;
+    sig_all[m] = PRUNED_SIGMA;
+}
+
+// The finish of a compact batch (pool indices gidx[0..n)): sigma and acq as sweep_finish_kernel computes them from the same
+// per-tile partials, summed in the same order, with the y stage A stored
+__global__ void sweep_scatter_finish_kernel(const double* __restrict__ ss_part, int nt, int64_t ldp, const int64_t* __restrict__ gidx,
+                                            int64_t n, const uint8_t* __restrict__ mask, const double* __restrict__ y_all,
+                                            double* __restrict__ sig_all, double* __restrict__ acq_all, FinishParams fp) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t m = gidx[i];
+    double ss = 0.0;
+#pragma unroll 8
+    for (int t = 0; t < nt; t++) ss += ss_part[(int64_t)t * ldp + i];
+    double var = fp.C - ss;
+    if (var < 0.0) var = 0.0;
+    double sd = sqrt(var) * fp.y_std;
+    unsigned mk = mask ? mask[m] : 0u;
+    if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
+    sig_all[m] = sd;
+    acq_all[m] = logexp_value(y_all[m], sd, fp.zeta, fp.baseline, fp.sigma_n);
+}
+
+// rows gidx[0..n) of the pool, then zero rows up to n_pad (the panel builders read whole 256-row blocks)
+__global__ void gather_rows_kernel(const double* __restrict__ Xc, int d, const int64_t* __restrict__ gidx, int64_t n,
+                                   int64_t n_pad, double* __restrict__ Xg) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_pad * d) return;
+    const int64_t i = e / d;
+    const int k = (int)(e - i * d);
+    Xg[e] = i < n ? Xc[gidx[i] * d + k] : 0.0;
+}
+
 // Split-K contraction of a small batch: the slices P[y] (Np x ldp each, `stride` doubles apart) hold
 // partial products of u = V k*; per 128-row tile ti and candidate m
 //     ss_part[ti][m] = sum_{i in tile} ( sum_y P[y][i][m] )^2
@@ -703,23 +767,37 @@ static int ensure_sweep_buffers(gpry_ctx* ctx, int64_t M) {
     return 0;
 }
 
+// candidates per chunk: the K* panel of a chunk (Np x chunk doubles) is 1 GiB at Np = 4096 and stays that size for smaller
+// models -- at Np = 1024 the 1e5 candidates of BASELINE configs[1] are ONE launch of 6256 tiles instead of three and a
+// ragged fourth (contraction 0.60 -> 0.71 of peak); a candidate's result does not depend on the chunking
+static int64_t sweep_chunk(const gpry_ctx* ctx, int64_t M) {
+    int64_t chunk = ctx->opt_sweep_chunk;
+    if (chunk <= 0) chunk = ctx->Np < 4096 ? round_up(32768 * 4096 / ctx->Np, 1024) : 32768;
+    if (chunk > round_up(M, 128)) chunk = round_up(M, 128);
+    return chunk;
+}
+
 // runs the chunked sweep over candidates resident in ctx->dXc
+// mean_only: stage A of a pruned sweep -- the same panel-form decision and the same panel kernels, but the panel is not
+// stored and nothing is contracted: y, the bound ub (ctx->dub) and the initial acq / sigma (sweep_mean_kernel)
 static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bool want_acq,
-                     double zeta, double baseline, double sigma_n, bool allow_split = false) {
+                     double zeta, double baseline, double sigma_n, bool allow_split = false, bool mean_only = false) {
     const int64_t Np = ctx->Np;
     const int nt = (int)(Np / 128);
-    // candidates per chunk: the K* panel of a chunk (Np x chunk doubles) is 1 GiB at Np = 4096 and stays that size for smaller
-    // models -- at Np = 1024 the 1e5 candidates of BASELINE configs[1] are ONE launch of 6256 tiles instead of three and a
-    // ragged fourth (contraction 0.60 -> 0.71 of peak); a candidate's result does not depend on the chunking
-    int64_t chunk = ctx->opt_sweep_chunk;
-    if (chunk <= 0) chunk = Np < 4096 ? round_up(32768 * 4096 / Np, 1024) : 32768;
-    if (chunk > round_up(M, 128)) chunk = round_up(M, 128);
+    const int64_t chunk = sweep_chunk(ctx, M);
     // "sweep_overlap" = 1 (round 6): the cross-kernel panel of chunk c + 1 is built on the side stream while the main stream
     // contracts chunk c -- two panels and two sets of partial sums, one event per hand-over.  Same kernels on the same data:
     // same bits.  Only for sweeps of several chunks with the one-pass contraction.
-    const bool overlap = ctx->opt_sweep_overlap && ctx->stream2 != nullptr && !allow_split && want_std && M > chunk;
+    const bool overlap = ctx->opt_sweep_overlap && ctx->stream2 != nullptr && !allow_split && want_std && !mean_only && M > chunk;
     const int nbuf = overlap ? 2 : 1;
-    if (nbuf * Np * chunk > ctx->kst_cap) {
+    if (mean_only && M > ctx->ub_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->dub) GPRY_TRY(dev_free(ctx, ctx->dub));
+        ctx->dub = nullptr; ctx->ub_cap = 0;
+        GPRY_TRY(dev_alloc(ctx, &ctx->dub, round_up(M, 1024)));
+        ctx->ub_cap = round_up(M, 1024);
+    }
+    if (!mean_only && nbuf * Np * chunk > ctx->kst_cap) {
         if (ctx->dKst) GPRY_TRY(dev_free(ctx, ctx->dKst));
         ctx->dKst = nullptr; ctx->kst_cap = 0;
         GPRY_TRY(dev_alloc(ctx, &ctx->dKst, nbuf * Np * chunk));
@@ -801,6 +879,7 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
         }
     }
     if (fast_panel || hybrid_panel) GPRY_TRY(launch_cross_prepare(ctx));
+    if (mean_only) ctx->prune.form = ctx->panel_form;
     // A fresh pool (gpry_sweep_logexp with a host array, option "sweep_upload"): the rows of chunk c go up on stream2 while
     // the main stream still works on chunk c - 1 -- 4.2 MB against 7.7 ms of kernels at N = 4096 -- and the main stream
     // waits for nothing but its own chunk (one event per chunk, never re-recorded within a call).  From pageable memory
@@ -836,7 +915,8 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
     };
     auto build_panel = [&](size_t ci, double* Kst, double* mean_part) -> int {
         const int64_t m0 = (int64_t)ci * chunk, mc = (M - m0 < chunk) ? M - m0 : chunk, mcp = round_up(mc, 128);
-        StageScope s(ctx, "cross_build");
+        StageScope s(ctx, mean_only ? "sweep_mean" : "cross_build");
+        if (mean_only) Kst = nullptr;       // (the kernels store the mean partials only)
         if (small_build) return launch_cross_build_small(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1);
         if (fast_panel || hybrid_panel) return launch_cross_build_mfma(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1, hybrid_panel ? 1 : 0);
         return launch_cross_build(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1);
@@ -878,6 +958,14 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
                 }
             }
             GPRY_TRY(build_panel(ci, Kst, mean_part));
+        }
+        if (mean_only) {
+            StageScope s(ctx, "sweep_mean");
+            hipLaunchKernelGGL(sweep_mean_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream,
+                               mean_part, nt_mean, mcp, m0, mc, have_mask ? ctx->dmask : nullptr,
+                               ctx->dy_all, ctx->dsig_all, ctx->dacq_all, ctx->dub, fp);
+            HIP_TRY(ctx, hipGetLastError());
+            continue;
         }
         // A batch of a few hundred to a few thousand points has fewer tiles than the GPU has workgroup
         // slots, and its longest tile walks all Np/16 slabs alone (1 ms at Np = 4096): split every
@@ -1332,11 +1420,17 @@ int gpry_predict_grad_batch(gpry_ctx* ctx, const double* X, int64_t m, int want_
     return 0;
 }
 
+}  // extern "C"
+static int prune_complete(gpry_ctx* ctx);
+static int prune_snapshot(gpry_ctx* ctx);
+extern "C" {
+
 int gpry_sweep_fetch(gpry_ctx* ctx, int64_t M, double* y_all, double* sigma_all, double* acq_all) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_fetch: ctx is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (M <= 0 || M != ctx->sw_M) return gpry_fail(ctx, -1, "sweep_fetch: the resident sweep has %lld candidates, not %lld",
                                                   (long long)ctx->sw_M, (long long)M);
+    if (ctx->sw_pruned) GPRY_TRY(prune_complete(ctx));      // the arrays of the full sweep, bit for bit
     if (y_all) HIP_TRY(ctx, hipMemcpyAsync(y_all, ctx->dy_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (sigma_all) HIP_TRY(ctx, hipMemcpyAsync(sigma_all, ctx->dsig_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (acq_all) HIP_TRY(ctx, hipMemcpyAsync(acq_all, ctx->dacq_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
@@ -1382,6 +1476,10 @@ int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
     GPRY_TRY(require_model(ctx, true));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (M <= 0) return gpry_fail(ctx, -1, "sweep: M must be > 0");
+    // option "sweep_prune" and no arrays wanted (NORA's lazy path): stage A of the pruned sweep -- y and a bound of every
+    // candidate's acquisition, nothing contracted yet; gpry_sweep_topk contracts what can reach the shortlist
+    const bool prune = ctx->opt_sweep_prune && !y_all && !sigma_all && !acq_all;
+    ctx->sw_pruned = 0;
     // a pool that comes from the host goes up chunk by chunk underneath the sweep itself (run_sweep); "sweep_upload" = 0:
     // in one piece in front of it (the comparator)
     const bool piped = X != nullptr && ctx->opt_sweep_upload && ctx->stream2 != nullptr;
@@ -1406,10 +1504,14 @@ int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
         }
     } upload_scope{ctx};
     if (piped) { ctx->up_X = X; ctx->up_gates = ctx->gates_on ? 1 : 0; }
-    GPRY_TRY(run_sweep(ctx, M, have_mask, true, true, zeta, baseline, sigma_n));
+    GPRY_TRY(run_sweep(ctx, M, have_mask, true, true, zeta, baseline, sigma_n, false, prune));
     if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, 64));
     HIP_TRY(ctx, hipMemsetAsync(ctx->dsel, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(count_nan_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->dacq_all, M, ctx->dsel);
+    // (pruned: the bound is NaN exactly where y is.  The exact acquisition of a candidate with a finite y is not NaN either: a
+    // NaN per-tile sum needs a NaN in V or in the candidate's panel column, and either one reaches y -- alpha_ = V^T V y
+    // picks up every entry of V in alpha_[0], and a NaN panel entry enters the mean partial through fma(alpha_j, k, .), NaN
+    // for any alpha_j.  The rest of the finish keeps var in [0, C]: the acquisition is finite or -inf.)
+    hipLaunchKernelGGL(count_nan_kernel, dim3(1024), dim3(256), 0, ctx->stream, prune ? ctx->dub : ctx->dacq_all, M, ctx->dsel);
     unsigned long long nn = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&nn, ctx->dsel, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (y_all) HIP_TRY(ctx, hipMemcpyAsync(y_all, ctx->dy_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
@@ -1418,6 +1520,17 @@ int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     upload_scope.done = true;
     if (n_nan) *n_nan = (int64_t)nn;
+    if (prune) {
+        const int form = ctx->prune.form;
+        ctx->prune = gpry_ctx::PruneState();
+        ctx->prune.form = form;
+        ctx->prune.have_mask = have_mask ? 1 : 0;
+        ctx->prune.zeta = zeta; ctx->prune.baseline = baseline; ctx->prune.sigma_n = sigma_n;
+        ctx->prune.C = exp(ctx->theta[0]); ctx->prune.y_mean = ctx->tf.y_mean; ctx->prune.y_std = ctx->tf.y_std;
+        ctx->prune.clip_hi = ctx->tf.clip_hi;
+        GPRY_TRY(prune_snapshot(ctx));
+        ctx->sw_pruned = 1;
+    }
     return 0;
 }
 
@@ -1530,12 +1643,62 @@ static double key_to_acq(unsigned long long k) {
     double a; memcpy(&a, &b, 8); return a;
 }
 
-extern "C" int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n_exclude,
-                               gpry_cand* top, int64_t* n_out, double* bound) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_topk: ctx is NULL");
-    if (!top || !n_out || !bound) return gpry_fail(ctx, -1, "topk: top, n_out and bound must not be NULL");
-    if (n_exclude > 0 && !exclude) return gpry_fail(ctx, -1, "topk: n_exclude > 0 but exclude is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+// Exact device top-K of src[0..M) under the composite key (value desc, idx desc; NaN first), exclusions removed: K records
+// (acq, y, sigma of the resident sweep, idx) in ctx->dcand, in no particular order; cnt = [records, key of the best one below]
+static int device_select(gpry_ctx* ctx, const double* src, int64_t M, int64_t K, const int64_t* exclude, int64_t n_exclude,
+                         unsigned long long cnt[2]) {
+    hipStream_t st = ctx->stream;
+    if (M > ctx->keys_cap) {
+        if (ctx->dkeys) GPRY_TRY(dev_free(ctx, ctx->dkeys));
+        GPRY_TRY(dev_alloc(ctx, &ctx->dkeys, round_up(M, 1024)));
+        ctx->keys_cap = round_up(M, 1024);
+    }
+    if (!ctx->dhist) { GPRY_TRY(dev_alloc(ctx, &ctx->dhist, 256)); }
+    if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, 64));
+    if (K > ctx->cand_cap) {
+        if (ctx->dcand) GPRY_TRY(dev_free(ctx, ctx->dcand));
+        GPRY_TRY(dev_alloc(ctx, &ctx->dcand, round_up(K, 1024)));
+        ctx->cand_cap = round_up(K, 1024);
+    }
+    unsigned nb = (unsigned)((M + 255) / 256);
+    hipLaunchKernelGGL(make_keys_kernel, dim3(nb), dim3(256), 0, st, src, M, ctx->dkeys);
+    TmpBuf<int64_t> bex;
+    int64_t* dex = nullptr;
+    if (n_exclude > 0) {
+        GPRY_TRY(bex.alloc(ctx, n_exclude));
+        dex = bex.p;
+        HIP_TRY(ctx, hipMemcpyAsync(dex, exclude, sizeof(int64_t) * n_exclude, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(exclude_keys_kernel, dim3((unsigned)((n_exclude + 255) / 256)), dim3(256), 0, st,
+                           ctx->dkeys, dex, n_exclude, M);
+    }
+    if (K <= 0) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        return 0;
+    }
+    SelState s0; memset(&s0, 0, sizeof(s0)); s0.k_rem = (unsigned long long)K;
+    SelState* dst = reinterpret_cast<SelState*>(ctx->dsel);          // 32 bytes
+    unsigned long long* dcnt = ctx->dsel + 4;                         // 2 counters after the state
+    HIP_TRY(ctx, hipMemcpyAsync(dst, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(dcnt, 0, 16, st));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dhist, 0, 256 * sizeof(unsigned int), st));
+    unsigned nbs = nb < 2048 ? nb : 2048;
+    for (int pass = 0; pass < 12; pass++) {
+        hipLaunchKernelGGL(select_hist_kernel, dim3(nbs), dim3(256), 0, st, ctx->dkeys, M, dst, pass, ctx->dhist);
+        hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(64), 0, st, ctx->dhist, dst, pass);
+    }
+    hipLaunchKernelGGL(select_emit_kernel, dim3(nbs), dim3(256), 0, st, ctx->dkeys, M, dst, ctx->dacq_all,
+                       ctx->dy_all, ctx->dsig_all, ctx->dcand, K, dcnt);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(cnt, dcnt, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((int64_t)cnt[0] != K)
+        return gpry_fail(ctx, -4, "topk: selected %llu candidates, expected %lld", cnt[0], (long long)K);
+    return 0;
+}
+
+// the shortlist of the resident acq_all as it stands
+static int sweep_topk_plain(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n_exclude,
+                            gpry_cand* top, int64_t* n_out, double* bound) {
     const int64_t M = ctx->sw_M;
     if (M <= 0 || !ctx->dacq_all) return gpry_fail(ctx, -1, "topk: no sweep results resident");
     if (M > 0xFFFFFFFFll) return gpry_fail(ctx, -1, "topk: M too large");
@@ -1584,56 +1747,13 @@ extern "C" int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude
         if ((int64_t)v.size() > K) *bound = v[(size_t)K].acq;
         return 0;
     }
-    if (M > ctx->keys_cap) {
-        if (ctx->dkeys) GPRY_TRY(dev_free(ctx, ctx->dkeys));
-        GPRY_TRY(dev_alloc(ctx, &ctx->dkeys, round_up(M, 1024)));
-        ctx->keys_cap = round_up(M, 1024);
-    }
-    if (!ctx->dhist) { GPRY_TRY(dev_alloc(ctx, &ctx->dhist, 256)); }
-    if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, 64));
     int64_t n_valid = M - (n_exclude > 0 ? n_exclude : 0);
     if (n_valid < 0) n_valid = 0;
     int64_t K = Kp < n_valid ? Kp : n_valid;
-    if (K > ctx->cand_cap) {
-        if (ctx->dcand) GPRY_TRY(dev_free(ctx, ctx->dcand));
-        GPRY_TRY(dev_alloc(ctx, &ctx->dcand, round_up(K, 1024)));
-        ctx->cand_cap = round_up(K, 1024);
-    }
-    unsigned nb = (unsigned)((M + 255) / 256);
-    hipLaunchKernelGGL(make_keys_kernel, dim3(nb), dim3(256), 0, st, ctx->dacq_all, M, ctx->dkeys);
-    TmpBuf<int64_t> bex;
-    int64_t* dex = nullptr;
-    if (n_exclude > 0) {
-        GPRY_TRY(bex.alloc(ctx, n_exclude));
-        dex = bex.p;
-        HIP_TRY(ctx, hipMemcpyAsync(dex, exclude, sizeof(int64_t) * n_exclude, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(exclude_keys_kernel, dim3((unsigned)((n_exclude + 255) / 256)), dim3(256), 0, st,
-                           ctx->dkeys, dex, n_exclude, M);
-    }
     *n_out = 0; *bound = -INFINITY;
-    if (K <= 0) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        return 0;
-    }
-    SelState s0; memset(&s0, 0, sizeof(s0)); s0.k_rem = (unsigned long long)K;
-    SelState* dst = reinterpret_cast<SelState*>(ctx->dsel);          // 32 bytes
-    unsigned long long* dcnt = ctx->dsel + 4;                         // 2 counters after the state
-    HIP_TRY(ctx, hipMemcpyAsync(dst, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(dcnt, 0, 16, st));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dhist, 0, 256 * sizeof(unsigned int), st));
-    unsigned nbs = nb < 2048 ? nb : 2048;
-    for (int pass = 0; pass < 12; pass++) {
-        hipLaunchKernelGGL(select_hist_kernel, dim3(nbs), dim3(256), 0, st, ctx->dkeys, M, dst, pass, ctx->dhist);
-        hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(64), 0, st, ctx->dhist, dst, pass);
-    }
-    hipLaunchKernelGGL(select_emit_kernel, dim3(nbs), dim3(256), 0, st, ctx->dkeys, M, dst, ctx->dacq_all,
-                       ctx->dy_all, ctx->dsig_all, ctx->dcand, K, dcnt);
-    HIP_TRY(ctx, hipGetLastError());
     unsigned long long cnt[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(cnt, dcnt, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if ((int64_t)cnt[0] != K)
-        return gpry_fail(ctx, -4, "topk: selected %llu candidates, expected %lld", cnt[0], (long long)K);
+    GPRY_TRY(device_select(ctx, ctx->dacq_all, M, K, exclude, n_exclude, cnt));
+    if (K <= 0) return 0;
     HIP_TRY(ctx, hipMemcpy(top, ctx->dcand, sizeof(gpry_cand) * K, hipMemcpyDeviceToHost));
     // total order (acq desc, idx desc); NaN first as np.argsort(acq)[::-1] would put it
     std::sort(top, top + K, [](const gpry_cand& a, const gpry_cand& b) {
@@ -1646,6 +1766,313 @@ extern "C" int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude
     });
     *n_out = K;
     *bound = cnt[1] ? key_to_acq(cnt[1]) : -INFINITY;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// Pruned sweep (option "sweep_prune").  Stage A (gpry_sweep_logexp, run_sweep mean_only) left y, the bound ub of every
+// candidate's acquisition (sweep_mean_kernel) and acq_all = ub, sig_all = PRUNED_SIGMA.  gpry_sweep_topk then contracts the
+// top K' candidates by ub exactly (prune_eval: acq_all, sig_all overwritten with the full sweep's values) and selects on the
+// MIXED array, exact values where evaluated and bounds elsewhere.  Since a bound is >= the candidate's exact acquisition,
+// its composite key (acq, idx) only moves up: if the K best records of the mixed array are all exact, every candidate of the
+// full sweep's top K is among them (a pruned one would sit above the K-th record there too), they come out in the full
+// sweep's order, and the value behind them -- max(next exact value, largest bound of a pruned candidate) -- is >= the full
+// sweep's bound.  Otherwise the candidates whose bound is not below the K-th exact value found so far are contracted
+// (prune_survivors), then K' grows x 8; once it would cover a quarter of the pool the full sweep runs (prune_complete).
+//
+// Bits: a candidate's panel column and mean partials depend on its coordinates alone (kernel_build.hip), and the one-pass
+// contraction's per-tile partials of a column depend only on that column, the row tile and the k direction of the row tile,
+// which is a function of the row tile and Np alone (sweep_gemm.hip) -- not of which other candidates share the launch or
+// where the column falls in it.  The compact batches therefore give every candidate the bits of the full sweep.  (Split-K
+// is never used here: it sums in another order.)
+
+__global__ void gather_acq_kernel(const double* __restrict__ acq, const int64_t* __restrict__ gidx, int64_t n, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = acq[gidx[i]];
+}
+__global__ void count_not_below_kernel(const double* __restrict__ a, int64_t n, double tau, unsigned long long* out) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    unsigned long long c = 0;
+    for (; i < n; i += stride) c += !(a[i] < tau) ? 1ull : 0ull;      // (NaN counts: it would sort first)
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+
+// the pool indices of the selected records not contracted yet (order immaterial: a candidate's bits do not depend on it)
+__global__ void cand_idx_kernel(const gpry_cand* __restrict__ c, int64_t n, int64_t* __restrict__ idx, unsigned long long* cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && c[i].sigma == PRUNED_SIGMA) idx[atomicAdd(cnt, 1ull)] = c[i].idx;
+}
+// ... and of every candidate of the pool not contracted yet (the completion)
+__global__ void pruned_idx_kernel(const double* __restrict__ sig, int64_t M, int64_t* __restrict__ idx, unsigned long long* cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < M && sig[i] == PRUNED_SIGMA) idx[atomicAdd(cnt, 1ull)] = i;
+}
+
+static int snap_buf(gpry_ctx* ctx, double** p, int64_t* cap, int64_t need) {
+    if (need <= *cap) return 0;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*p) GPRY_TRY(dev_free(ctx, *p));
+    *p = nullptr; *cap = 0;
+    GPRY_TRY(dev_alloc(ctx, p, need));
+    *cap = need;
+    return 0;
+}
+
+// Stage A's model, kept for the contraction rounds and the completion: V, alpha_, the training rows (raw and scaled for
+// theta), theta, kernel, affine maps, centre.  NORA refits and refactorises between a lazy sweep and the next call, whose
+// re-weighting fetches the arrays of the OLD model; these copies (one Np x Np copy, ~0.1 ms at Np = 4096) are what lets a
+// pruned sweep be completed later with the model it was made with, as the full sweep's arrays would have been.
+static int prune_snapshot(gpry_ctx* ctx) {
+    GPRY_TRY(ensure_pred_xs(ctx));          // dXs scaled for the prediction factor's theta
+    gpry_ctx::ModelSnap& m = ctx->snap;
+    const int64_t Np = ctx->Np, N = ctx->N;
+    GPRY_TRY(snap_buf(ctx, &m.dV, &m.v_cap, Np * Np));
+    GPRY_TRY(snap_buf(ctx, &m.dalpha_, &m.a_cap, Np));
+    GPRY_TRY(snap_buf(ctx, &m.dXs, &m.xs_cap, Np * ctx->dpad));
+    GPRY_TRY(snap_buf(ctx, &m.dX, &m.x_cap, (N > 0 ? N : 1) * ctx->d));
+    HIP_TRY(ctx, hipMemcpyAsync(m.dV, ctx->dV, sizeof(double) * Np * Np, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(m.dalpha_, ctx->dalpha_, sizeof(double) * Np, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(m.dXs, ctx->dXs, sizeof(double) * Np * ctx->dpad, hipMemcpyDeviceToDevice, ctx->stream));
+    if (N > 0) HIP_TRY(ctx, hipMemcpyAsync(m.dX, ctx->dX, sizeof(double) * N * ctx->d, hipMemcpyDeviceToDevice, ctx->stream));
+    m.N = N; m.Np = Np; m.d = ctx->d; m.dpad = ctx->dpad; m.kernel_id = ctx->kernel_id;
+    memcpy(m.theta, ctx->theta, sizeof(m.theta));
+    m.tf = ctx->tf;
+    memcpy(m.xcenter, ctx->xcenter, sizeof(m.xcenter));
+    m.xs_foreign = false;
+    return 0;
+}
+
+// swaps the snapshot in for the duration of a contraction round / the completion (the launchers read the context)
+struct SnapSwap {
+    gpry_ctx* c;
+    explicit SnapSwap(gpry_ctx* ctx) : c(ctx) { swap(); }
+    ~SnapSwap() { swap(); }
+    void swap() {
+        gpry_ctx::ModelSnap& m = c->snap;
+        std::swap(c->dV, m.dV); std::swap(c->dalpha_, m.dalpha_); std::swap(c->dXs, m.dXs); std::swap(c->dX, m.dX);
+        std::swap(c->N, m.N); std::swap(c->Np, m.Np); std::swap(c->d, m.d); std::swap(c->dpad, m.dpad);
+        std::swap(c->kernel_id, m.kernel_id); std::swap(c->theta, m.theta); std::swap(c->tf, m.tf);
+        std::swap(c->xcenter, m.xcenter); std::swap(c->xs_foreign, m.xs_foreign);
+    }
+};
+
+static FinishParams prune_finish_params(const gpry_ctx* ctx) {
+    FinishParams fp;
+    fp.C = ctx->prune.C; fp.y_mean = ctx->prune.y_mean; fp.y_std = ctx->prune.y_std; fp.clip_hi = ctx->prune.clip_hi;
+    fp.zeta = ctx->prune.zeta; fp.baseline = ctx->prune.baseline; fp.sigma_n = ctx->prune.sigma_n;
+    fp.want_std = 1; fp.want_acq = 1;
+    return fp;
+}
+
+static int ensure_gidx(gpry_ctx* ctx, int64_t n) {
+    if (n <= ctx->gidx_cap) return 0;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->dgidx) GPRY_TRY(dev_free(ctx, ctx->dgidx));
+    ctx->dgidx = nullptr; ctx->gidx_cap = 0;
+    GPRY_TRY(dev_alloc(ctx, &ctx->dgidx, round_up(n, 1024)));
+    ctx->gidx_cap = round_up(n, 1024);
+    return 0;
+}
+
+// exact sigma / acq of the n candidates whose pool indices are in ctx->dgidx
+static int prune_eval(gpry_ctx* ctx, int64_t n) {
+    SnapSwap model(ctx);                    // stage A's model, whatever happened to the context's since
+    const int64_t Np = ctx->Np, M = ctx->sw_M;
+    const int nt = (int)(Np / 128);
+    const int64_t chunk = sweep_chunk(ctx, M);
+    const int64_t np_max = round_up(n < chunk ? n : chunk, 128);
+    if (Np * np_max > ctx->kst_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->dKst) GPRY_TRY(dev_free(ctx, ctx->dKst));
+        ctx->dKst = nullptr; ctx->kst_cap = 0;
+        GPRY_TRY(dev_alloc(ctx, &ctx->dKst, Np * np_max));
+        ctx->kst_cap = Np * np_max;
+    }
+    GPRY_TRY(ensure_part(ctx, (int64_t)nt * np_max));
+    const int64_t rows = round_up(np_max, 256);
+    if (rows > ctx->xg_cap) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->dXg) GPRY_TRY(dev_free(ctx, ctx->dXg));
+        ctx->dXg = nullptr; ctx->xg_cap = 0;
+        GPRY_TRY(dev_alloc(ctx, &ctx->dXg, rows * ctx->d));
+        ctx->xg_cap = rows;
+    }
+    const int form = ctx->prune.form;       // the panel form of stage A (a gpry_predict in between may have built another)
+    if (form == 1 || form == 4) GPRY_TRY(launch_cross_prepare(ctx));
+    const FinishParams fp = prune_finish_params(ctx);
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int64_t nc = (n - i0 < chunk) ? n - i0 : chunk, ncp = round_up(nc, 128), npad = round_up(ncp, 256);
+        const int64_t* gidx = ctx->dgidx + i0;
+        {
+            StageScope s(ctx, "sweep_compact");
+            hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((npad * ctx->d + 255) / 256)), dim3(256), 0, ctx->stream,
+                               ctx->dXc, ctx->d, gidx, nc, npad, ctx->dXg);
+            HIP_TRY(ctx, hipGetLastError());
+            // (the builders read rows below min(sw_M, round_up(ncp, 256)) = npad at most: dXg holds npad rows)
+            if (form == 1 || form == 4) GPRY_TRY(launch_cross_build_mfma(ctx, ctx->dXg, 0, ncp, ncp, ctx->dKst, nullptr, 1, form == 4 ? 1 : 0));
+            else GPRY_TRY(launch_cross_build(ctx, ctx->dXg, 0, ncp, ncp, ctx->dKst, nullptr, 1));
+        }
+        StageScope s(ctx, "sweep_prune_gemm");
+        GemmArgs g = {};
+        g.A = ctx->dV; g.lda = Np; g.B = ctx->dKst; g.ldb = ncp; g.C = ctx->dpart; g.ldc = ncp;
+        g.M = (int)Np; g.N = (int)ncp; g.K = (int)Np;
+        g.kmode = KM_A_LOWER; g.lower_only = 0; g.tile_map = TM_SWEEP | (3 << 4);     // as run_sweep: the same k walk per row tile
+        if (ctx->opt_gemm_dma) GPRY_TRY(sweep_gemm_dma_sp_launch(ctx, g));
+        else GPRY_TRY(gemm_f64_launch(ctx, g, false, false, EPI_SUMSQ));
+        hipLaunchKernelGGL(sweep_scatter_finish_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream,
+                           ctx->dpart, nt, ncp, gidx, nc, ctx->prune.have_mask ? ctx->dmask : nullptr, ctx->dy_all,
+                           ctx->dsig_all, ctx->dacq_all, fp);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// the rest of the pool, contracted as the full sweep would have contracted it (stage A's model, same kernels, same bits):
+// afterwards the resident arrays are the full sweep's
+static int prune_complete(gpry_ctx* ctx) {
+    const int64_t M = ctx->sw_M;
+    GPRY_TRY(ensure_gidx(ctx, M));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dsel + 7, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(pruned_idx_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dsig_all, M, ctx->dgidx, ctx->dsel + 7);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long n = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->dsel + 7, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n > 0) GPRY_TRY(prune_eval(ctx, (int64_t)n));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->prune.evaluated_total += (int64_t)n;
+    ctx->sw_pruned = 0;
+    ctx->prune.completed = 1;
+    return 0;
+}
+
+// The survivors of the contracted set (the n_gidx candidates in ctx->dgidx): tau = the Kp-th best exact acquisition among
+// them outside the exclusions -- a lower bound of the full sweep's Kp-th value -- and *n_surv = the number of candidates whose
+// bound is not below tau; every other candidate is out.  *n_surv = -1 if fewer than Kp of them count.
+static int prune_survivors(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n_exclude, int64_t* n_surv) {
+    const int64_t n = ctx->prune.n_gidx;
+    *n_surv = -1;
+    if (n < Kp || Kp <= 0) return 0;
+    std::vector<double> a((size_t)n);
+    std::vector<int64_t> idx((size_t)n);
+    {
+        StageScope s(ctx, "sweep_prune_select");
+        TmpBuf<double> buf;
+        GPRY_TRY(buf.alloc(ctx, n));
+        hipLaunchKernelGGL(gather_acq_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dacq_all, ctx->dgidx, n, buf.p);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(a.data(), buf.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(idx.data(), ctx->dgidx, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    std::vector<int64_t> ex(exclude, exclude + (n_exclude > 0 ? n_exclude : 0));
+    std::sort(ex.begin(), ex.end());
+    std::vector<double> v;
+    v.reserve((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if (a[(size_t)i] != a[(size_t)i]) return 0;                     // NaN: leave it to the full sweep
+        if (!std::binary_search(ex.begin(), ex.end(), idx[(size_t)i])) v.push_back(a[(size_t)i]);
+    }
+    if ((int64_t)v.size() < Kp) return 0;
+    std::nth_element(v.begin(), v.begin() + (Kp - 1), v.end(), std::greater<double>());
+    const double tau = v[(size_t)(Kp - 1)];
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dsel + 6, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(count_not_below_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->dub, ctx->sw_M, tau, ctx->dsel + 6);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long c = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&c, ctx->dsel + 6, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->prune.tau = tau;
+    ctx->prune.survivors = (int64_t)c;
+    *n_surv = (int64_t)c;
+    return 0;
+}
+
+static int prune_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n_exclude,
+                      gpry_cand* top, int64_t* n_out, double* bound) {
+    const int64_t M = ctx->sw_M;
+    ctx->prune.last_K = Kp;
+    for (;;) {
+        if (ctx->prune.n_eval > 0) {
+            GPRY_TRY(sweep_topk_plain(ctx, Kp, exclude, n_exclude, top, n_out, bound));
+            bool exact = true;
+            for (int64_t i = 0; i < *n_out && exact; i++) exact = !(top[i].sigma == PRUNED_SIGMA);
+            if (exact) return 0;
+        }
+        // round 1: the top max(4 Kp, 1024) by bound (the threshold stage); round 2: exactly the candidates whose bound is not
+        // below the threshold tau that round 1 found (the survivors); after that the set grows x 8
+        int64_t kq = Kp > 0 ? 4 * Kp : 1;
+        if (kq < 1024) kq = 1024;
+        if (ctx->prune.n_eval > 0) {
+            int64_t ns = -1;
+            if (!ctx->prune.tau_done) {
+                ctx->prune.tau_done = 1;
+                GPRY_TRY(prune_survivors(ctx, Kp, exclude, n_exclude, &ns));
+            }
+            if (ns > ctx->prune.n_eval) kq = ns;
+            else if (kq < 8 * ctx->prune.n_eval) kq = 8 * ctx->prune.n_eval;
+        }
+        if (kq > M / 4 || kq > M - (n_exclude > 0 ? n_exclude : 0)) {      // (cheaper, or no longer possible: the full sweep)
+            GPRY_TRY(prune_complete(ctx));
+            return sweep_topk_plain(ctx, Kp, exclude, n_exclude, top, n_out, bound);
+        }
+        unsigned long long cnt[2] = {0, 0};
+        {
+            StageScope s(ctx, "sweep_prune_select");
+            GPRY_TRY(device_select(ctx, ctx->dub, M, kq, exclude, n_exclude, cnt));
+        }
+        const int64_t nsel = (int64_t)cnt[0];
+        GPRY_TRY(ensure_gidx(ctx, nsel));
+        unsigned long long nn = 0;
+        if (nsel > 0) {         // (the candidates an earlier round contracted are not contracted again)
+            HIP_TRY(ctx, hipMemsetAsync(ctx->dsel + 7, 0, 8, ctx->stream));
+            hipLaunchKernelGGL(cand_idx_kernel, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dcand, nsel,
+                               ctx->dgidx, ctx->dsel + 7);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(&nn, ctx->dsel + 7, 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        const int64_t n = (int64_t)nn;
+        if (n > 0) GPRY_TRY(prune_eval(ctx, n));
+        ctx->prune.n_eval = kq;
+        ctx->prune.n_gidx = n;
+        ctx->prune.rounds++;
+        ctx->prune.evaluated_total += n;
+    }
+}
+
+extern "C" int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n_exclude,
+                               gpry_cand* top, int64_t* n_out, double* bound) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_topk: ctx is NULL");
+    if (!top || !n_out || !bound) return gpry_fail(ctx, -1, "topk: top, n_out and bound must not be NULL");
+    if (n_exclude > 0 && !exclude) return gpry_fail(ctx, -1, "topk: n_exclude > 0 but exclude is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->sw_pruned && ctx->sw_M > 0) return prune_topk(ctx, Kp, exclude, n_exclude, top, n_out, bound);
+    return sweep_topk_plain(ctx, Kp, exclude, n_exclude, top, n_out, bound);
+}
+
+extern "C" int gpry_sweep_prune_info(gpry_ctx* ctx, int64_t* info, double* dinfo) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_prune_info: ctx is NULL");
+    if (!info) return gpry_fail(ctx, -1, "sweep_prune_info: info must not be NULL");
+    info[0] = ctx->sw_pruned;
+    info[1] = ctx->sw_M;
+    info[2] = ctx->prune.n_eval;
+    info[3] = ctx->prune.rounds;
+    info[4] = ctx->prune.evaluated_total;
+    info[5] = ctx->prune.completed;
+    info[6] = ctx->prune.last_K;
+    info[7] = ctx->prune.survivors;
+    if (dinfo) {
+        dinfo[0] = ctx->prune.survivors >= 0 ? ctx->prune.tau : NAN;
+        const char* names[] = {"sweep_mean", "sweep_prune_select", "sweep_compact", "sweep_prune_gemm"};
+        for (int k = 0; k < 4; k++) {
+            double ms = 0.0; int64_t cnt = 0;
+            if (gpry_timing_get(ctx, names[k], &ms, &cnt) != 0) ms = 0.0;
+            dinfo[1 + k] = ms;
+        }
+    }
     return 0;
 }
 

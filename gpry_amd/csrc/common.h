@@ -178,6 +178,40 @@ struct gpry_ctx {
     const double* up_X = nullptr;      // host pool of the sweep in flight whose chunks are still to be uploaded (run_sweep)
     int up_gates = 0;                  // ... and the device gates are evaluated chunk by chunk behind each upload
     int opt_predict_gates = 0;         // 1: gpry_predict ORs the device gates (gpry_set_gates) into the caller's mask, as the sweep does
+    // pruned sweep (option "sweep_prune", api.hip): gpry_sweep_logexp with no arrays wanted leaves y and a per-candidate upper
+    // bound of the acquisition; gpry_sweep_topk contracts only the candidates whose bound can reach the shortlist
+    int opt_sweep_prune = 0;
+    int sw_pruned = 0;                 // 1: the resident sweep is pruned (acq_all holds exact values or bounds, see api.hip)
+    struct PruneState {
+        int have_mask = 0;
+        int form = 0;                  // panel form stage A decided (panel_form codes); compact panels take the same
+        double zeta = 0.0, baseline = 0.0, sigma_n = 0.0;
+        double C = 0.0, y_mean = 0.0, y_std = 0.0, clip_hi = 0.0;   // the model's post-processing the bounds were made with
+        int64_t n_eval = 0;            // candidates evaluated exactly: the top n_eval by bound
+        int64_t rounds = 0, evaluated_total = 0, completed = 0, last_K = 0;
+        int64_t n_gidx = 0;            // candidates in dgidx (the last contracted set)
+        int tau_done = 0;              // the survivor count of a threshold has been made (prune_survivors)
+        double tau = 0.0;              // that threshold, and the candidates whose bound was not below it
+        int64_t survivors = -1;
+    } prune;
+    // the prediction state the pruned sweep was made with, copied at its end (api.hip: prune_snapshot): a later contraction
+    // round or completion evaluates THAT model, whatever gpry_set_train / set_theta / factorize / append_rows did meanwhile
+    struct ModelSnap {
+        double *dV = nullptr, *dalpha_ = nullptr, *dXs = nullptr, *dX = nullptr;
+        int64_t v_cap = 0, a_cap = 0, xs_cap = 0, x_cap = 0;
+        int64_t N = 0, Np = 0;
+        int d = 0, dpad = 0, kernel_id = 0;
+        double theta[1 + GPRY_MAX_DIM] = {0};
+        gpry_affine tf;
+        double xcenter[GPRY_MAX_DIM] = {0};
+        bool xs_foreign = false;
+    } snap;
+    double* dub = nullptr;             // M: upper bound of each candidate's acquisition (prior sigma)
+    int64_t ub_cap = 0;
+    double* dXg = nullptr;             // gathered candidate rows of a compact evaluation (rows padded to 256, zeros)
+    int64_t xg_cap = 0;                // rows
+    int64_t* dgidx = nullptr;          // their pool indices
+    int64_t gidx_cap = 0;
 
     // host pinned staging
     void* hpin = nullptr; void* hpin_dev = nullptr; int64_t hpin_cap = 0;   // host / device view of the same buffer

@@ -246,7 +246,8 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->dsig_all, ctx->dacq_all, ctx->dKst, ctx->dpart, ctx->dkeys, ctx->dhist,
                     ctx->dcand, ctx->dsel, ctx->dU, ctx->dXkb, ctx->dkbout, ctx->pr.dXc, ctx->pr.dmask,
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
-                    ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs};
+                    ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
+                    ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hbres) (void)hipHostFree(ctx->hbres);
@@ -307,6 +308,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("predict_split", opt_predict_split, 0, 1, (void)0),
     OPT_INT("sweep_upload", opt_sweep_upload, 0, 1, (void)0),
     OPT_INT("sweep_overlap", opt_sweep_overlap, 0, 1, (void)0),
+    OPT_INT("sweep_prune", opt_sweep_prune, 0, 1, (void)0),
     OPT_INT("chol_stacked", opt_chol_stacked, 0, BIG, c->lml_cache = false),
     OPT_INT("chol_stacked_dense", opt_chol_stacked_dense, 0, 1, c->lml_cache = false),
     OPT_INT("predict_gates", opt_predict_gates, 0, 1, (void)0),

@@ -240,6 +240,8 @@ int launch_kernel_rows(gpry_ctx* ctx, int64_t row0, int k, int64_t ldk, double* 
 // registers, the training chunk sits in LDS and is read wave-uniformly (broadcast).
 // Output Kst[j*ldk + m] = C k(x*_m, x_j) (rows j >= N are zero) and the per-chunk mean
 // partial  mean_part[jc*mc + m] = sum_{j in chunk} alpha_[j] * Kst[j][m].
+// Kst == NULL (the mean-only pass of a pruned sweep): the same values, only the mean partials are stored -- a candidate's
+// entries and partials depend on its own coordinates alone, never on its position in the launch or on its neighbours.
 // The candidates of a chunk, mapped to the unit cube and divided by the length scales ONCE, coordinate-major:
 // Xcs[k * ldm + ml] = ((x_k - lo_k) / span_k) / l_k (true divisions, in this order, as sklearn and the preprocessor do;
 // zeros beyond the pool and beyond d).  Every one of the Np / 128 row-chunk workgroups of cross_build_kernel used to redo
@@ -302,7 +304,7 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
             v[q] = kp.C * corr_r2_fast<KID>(r2[q]);
             macc = fma(al[j0 + q], v[q], macc);
         }
-        if (in_chunk) {                           // one predicated region for the four stores
+        if (in_chunk && Kst) {                    // one predicated region for the four stores (Kst == NULL: mean partials only)
 #pragma unroll
             for (int q = 0; q < 4; q++) Kst[((int64_t)jc * 128 + j0 + q) * ldk + ml] = v[q];
         }
@@ -319,7 +321,7 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
             v = kp.C * corr_r2_fast<KID>(r2);
             macc = fma(al[jj], v, macc);
         }
-        if (in_chunk) Kst[((int64_t)jc * 128 + jj) * ldk + ml] = v;
+        if (in_chunk && Kst) Kst[((int64_t)jc * 128 + jj) * ldk + ml] = v;
     }
     if (in_chunk && mean_part) mean_part[(int64_t)jc * mc + ml] = macc;
 }
@@ -438,7 +440,7 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
                 if (jj >= nvalid) { v0 = 0.0; v1 = 0.0; }
                 macc[2 * tp] = fma(alq[q], v0, macc[2 * tp]);
                 macc[2 * tp + 1] = fma(alq[q], v1, macc[2 * tp + 1]);
-                if (in_chunk) *reinterpret_cast<double2*>(Kst + ((int64_t)jc * 128 + jj) * ldk + mloc) = make_double2(v0, v1);
+                if (in_chunk && Kst) *reinterpret_cast<double2*>(Kst + ((int64_t)jc * 128 + jj) * ldk + mloc) = make_double2(v0, v1);
             }
         }
     }

@@ -301,13 +301,17 @@ class NORA(GenericGPAcquisition):
     GPUs), a list of device indices (repeats = several contexts on one GPU) or a ready group object
     with the ``gpry_amd._lib.DeviceGroup`` interface.  Candidate shards, model replication and the
     shortlist merge are those of the multi-rank path; results are identical to one context's.
+
+    ``exact_prune`` (default True): a sweep whose arrays stay on the device contracts only the candidates whose
+    acquisition bound (the value at the prior sigma) can reach the shortlist; proposals, shortlist records and every
+    array fetched later are bit for bit those of the full sweep.  ``acq.stats["prune"]`` holds the statistics.
     """
 
     def __init__(self, bounds, preprocessing_X=None, verbose=1, acq_func="LogExp", sampler=None,
                  mc_every="1d", nlive_per_training=3, nlive_max="25d", nlive_per_dim_max=None,
                  num_repeats="5d", num_repeats_per_dim=None, precision_criterion_target=0.01,
                  nprior_per_nlive=10, max_ncalls=None, tmpdir=None, comm=None,
-                 shortlist_size=None, gather_y="auto", devices=None):
+                 shortlist_size=None, gather_y="auto", devices=None, exact_prune=True):
         super().__init__(bounds=np.asarray(bounds), preprocessing_X=preprocessing_X,
                          verbose=verbose, acq_func=acq_func)
         self.log_header = f"[ACQUISITION : {self.__class__.__name__}] "
@@ -339,6 +343,9 @@ class NORA(GenericGPAcquisition):
         self._group = self._group_key = self._group_model = None
         self.shortlist_size = shortlist_size
         self.gather_y = gather_y
+        # lazy sweeps contract only the candidates whose acquisition bound can reach the shortlist (option "sweep_prune" of
+        # the library); the shortlist, its bound rule and every array fetched later are those of the full sweep
+        self.exact_prune = bool(exact_prune)
         self._X_already_proposed = np.empty((0, self.n_d))
         self.stats = {}
 
@@ -474,8 +481,16 @@ class NORA(GenericGPAcquisition):
         lazy = (not sharded and not need_arrays and self.gather_y == "auto"
                 and hasattr(dev, "sweep_fetch"))
         want = ("y", "sigma") if ((gather and sharded) or (not sharded and not lazy)) else ()
-        out = dev.sweep_logexp(None if resident else X[lo:hi], self.acq_func.zeta, gpr.y_max,
-                               noise, mask=mask, M=hi - lo, want=want)
+        prune_on = self._prune_targets(dev, grouped) if (lazy and self.exact_prune) else []
+        for t in prune_on:
+            t.set_option("sweep_prune", 1)
+        try:
+            out = dev.sweep_logexp(None if resident else X[lo:hi], self.acq_func.zeta, gpr.y_max,
+                                   noise, mask=mask, M=hi - lo, want=want)
+        finally:
+            for t in prune_on:
+                t.set_option("sweep_prune", 0)
+        self._pruned_on = prune_on
         self._sweep_dev = dev
         gpr.n_eval += M
         if out["n_nan"]:
@@ -512,6 +527,15 @@ class NORA(GenericGPAcquisition):
                               f"{info['panel_error_variance']:.2g} against a gate of {info['panel_gate']:.2g}); "
                               "see acq.stats['panel_form']", RuntimeWarning)
         return y, s
+
+    @staticmethod
+    def _prune_targets(dev, grouped):
+        """The contexts whose option "sweep_prune" a lazy sweep switches on: the sweeping context or the group's members."""
+        if grouped:
+            if not (hasattr(dev, "member") and hasattr(dev, "size")):
+                return []
+            return [dev.member(i) for i in range(dev.size)]
+        return [dev] if hasattr(dev, "sweep_prune_info") else []
 
     def _shortlist(self, gpr, K, exclude_global):
         """Global descending stream prefix: records (acq, y, sigma, idx) valid down to
@@ -689,6 +713,11 @@ class NORA(GenericGPAcquisition):
                 K *= 4
         self.stats.update(shortlist=fed, cache_models=self.pool.cache_counter,
                           rank_s=time() - t_rank)
+        pruned_on = getattr(self, "_pruned_on", [])
+        if pruned_on:
+            self.stats["prune"] = [t.sweep_prune_info() for t in pruned_on]
+        else:
+            self.stats.pop("prune", None)
         merged = self.pool.copy(drop_empty=True)
         X_pool, y_pool = merged.X[:n_points], merged.y[:n_points]
         with np.errstate(divide="ignore"):

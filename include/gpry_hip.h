@@ -132,6 +132,9 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *                             mc_every-th call); 0: one copy in front of the sweep (the comparator; same bits)
  *     "sweep_overlap" 0/1     1: the cross-kernel panel of chunk c + 1 is built on the side stream underneath the contraction of
  *                             chunk c (two panels; same bits).  Default 0: measured slower (profiles/r06_sweep.md), kept as the comparator
+ *     "sweep_prune" 0/1       1: gpry_sweep_logexp with no arrays wanted builds only y and an exact upper bound of every candidate's
+ *                             acquisition (its prior sigma); gpry_sweep_topk contracts only the candidates whose bound can reach
+ *                             the shortlist (same records, bit for bit; see gpry_sweep_topk).  Default 0: the full sweep
  *     "chol_stacked"          up to this padded training-set size (default 2048; at most 3584) the inverse factor V = L^-1 comes
  *                             out of the launches of the Cholesky factorisation itself (the identity appended to the matrix as
  *                             extra rows); 0: always the recursive inverse behind the factorisation.  Same L; V, and what is
@@ -288,9 +291,21 @@ int gpry_sweep_fetch(gpry_ctx* ctx, int64_t M, double* y_all, double* sigma_all,
  * (gpry/gp_acquisition.py:1328-1329).  exclude (nullable, n_exclude sorted indices):
  * rows dropped as "already proposed" (gpry/gp_acquisition.py:1037-1047).
  * *n_out <= Kp records written, sorted; *bound = largest acq NOT returned (-inf if
- * none): every candidate outside the shortlist has acq <= *bound. */
+ * none): every candidate outside the shortlist has acq <= *bound.
+ * After a pruned sweep (option "sweep_prune") the records are those of the full sweep, bit for bit, and *bound is >= the
+ * full sweep's bound: the largest acq not returned, or the largest upper bound of a candidate that was never contracted.
+ * gpry_sweep_fetch after a pruned sweep runs the full sweep first. */
 int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n_exclude,
                     gpry_cand* top, int64_t* n_out, double* bound);
+/* Statistics of the last pruned sweep: info[0] 1 while it is still pruned (0 once completed or after a full sweep),
+ * [1] pool size, [2] candidates ranked by bound and contracted exactly (K'), [3] contraction rounds, [4] candidates
+ * contracted in all, [5] 1 if the full sweep had to run, [6] Kp of the last gpry_sweep_topk, [7] candidates whose bound
+ * was not below the threshold of the first contraction round (-1: that round answered alone).  dinfo (nullable, 5 doubles):
+ * [0] that threshold (NaN if none), [1..4] device ms so far of the stages "sweep_mean", "sweep_prune_select", "sweep_compact",
+ * "sweep_prune_gemm" (the per-stage timers of gpry_timing_get; 0 while timing is off).  The contraction rounds and the
+ * completion use a copy of the model taken at the end of the sweep: a refit or refactorisation in between does not change
+ * what they compute. */
+int gpry_sweep_prune_info(gpry_ctx* ctx, int64_t* info, double* dinfo);
 
 /* ---- a14/a15: Kriging-believer support (bordered factor instead of deepcopy+refit) - */
 /* Start a session on the current factor; drops any registered candidates. */
