@@ -67,6 +67,8 @@ SIGNATURES = {
     "gpry_set_gates": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int, _vp]),
     "gpry_sweep_logexp": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_double, C.c_double,
                                     C.c_double, _vp, _vp, _vp, _P(C.c_int64)]),
+    "gpry_sweep_logexp_given": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_double, C.c_double,
+                                          C.c_double, _vp, _vp, _vp, _P(C.c_int64)]),
     "gpry_sweep_fetch": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_sweep_prune_info": (C.c_int, [_vp, _vp, _vp]),
     "gpry_sweep_topk": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _P(C.c_int64),
@@ -91,6 +93,8 @@ SIGNATURES = {
     "gpry_group_set_gates": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int, _vp]),
     "gpry_group_sweep_logexp": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_double, C.c_double,
                                           C.c_double, _vp, _vp, _vp, _P(C.c_int64)]),
+    "gpry_group_sweep_logexp_given": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_double, C.c_double,
+                                                C.c_double, _vp, _vp, _vp, _P(C.c_int64)]),
     "gpry_group_sweep_fetch": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_group_sweep_topk": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _P(C.c_int64),
                                         _P(C.c_double), _P(C.c_int)]),
@@ -102,6 +106,21 @@ SIGNATURES = {
     "gpry_debug_gemm": (C.c_int, [_vp, _vp, _vp, _vp] + [C.c_int] * 9),
     "gpry_debug_logexp": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_double, _vp]),
 }
+
+
+def _given_arrays(y_given, sigma_given, M):
+    """The sampler's own (y, sigma_y) as contiguous float64 arrays of M rows; sigma without y is not a case of the
+    reference (it is recomputed there: the caller passes neither)."""
+    if y_given is None:
+        raise ValueError("sigma_given without y_given")
+    y_given = np.ascontiguousarray(y_given, dtype=np.float64)
+    if y_given.shape != (M,):
+        raise ValueError(f"y_given has shape {y_given.shape}, the pool has {M} rows")
+    if sigma_given is not None:
+        sigma_given = np.ascontiguousarray(sigma_given, dtype=np.float64)
+        if sigma_given.shape != (M,):
+            raise ValueError(f"sigma_given has shape {sigma_given.shape}, the pool has {M} rows")
+    return y_given, sigma_given
 
 
 class GpryHipError(RuntimeError):
@@ -424,8 +443,11 @@ class Device:
                                                           _ptr(std), _ptr(mg), _ptr(kg)), "gpry_predict_grad_batch")
         return mean, std, mg, kg
 
-    def sweep_logexp(self, X, zeta, baseline, sigma_n, mask=None, M=None, want=("y", "sigma", "acq")):
-        """Run the fused sweep.  ``X=None`` re-uses the candidate set resident on the device."""
+    def sweep_logexp(self, X, zeta, baseline, sigma_n, mask=None, M=None, want=("y", "sigma", "acq"),
+                     y_given=None, sigma_given=None):
+        """Run the fused sweep.  ``X=None`` re-uses the candidate set resident on the device.  ``y_given`` (and
+        ``sigma_given``): the sampler's own arrays (``gpry_sweep_logexp_given``) -- y is kept as given and only sigma is
+        computed, or with both nothing but the acquisition."""
         if X is not None:
             X = _f64(X)
             M = X.shape[0]
@@ -433,10 +455,17 @@ class Device:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
         out = {k: (np.empty(M) if k in want else None) for k in ("y", "sigma", "acq")}
         n_nan = C.c_int64(0)
-        self._check(self._lib.gpry_sweep_logexp(
-            self._h, _ptr(X), M, _ptr(mask), float(zeta), float(baseline), float(sigma_n),
-            _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["acq"]), C.byref(n_nan)),
-            "gpry_sweep_logexp")
+        if y_given is None and sigma_given is None:
+            self._check(self._lib.gpry_sweep_logexp(
+                self._h, _ptr(X), M, _ptr(mask), float(zeta), float(baseline), float(sigma_n),
+                _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["acq"]), C.byref(n_nan)),
+                "gpry_sweep_logexp")
+        else:
+            y_given, sigma_given = _given_arrays(y_given, sigma_given, M)
+            self._check(self._lib.gpry_sweep_logexp_given(
+                self._h, _ptr(X), M, _ptr(mask), _ptr(y_given), _ptr(sigma_given), float(zeta), float(baseline),
+                float(sigma_n), _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["acq"]), C.byref(n_nan)),
+                "gpry_sweep_logexp_given")
         out["n_nan"] = n_nan.value
         self.sweep_epoch = getattr(self, "sweep_epoch", 0) + 1    # the resident arrays changed
         self._sweep_M = M
@@ -629,7 +658,8 @@ class DeviceGroup:
                                                    float(intercept), int(bool(positive_is_finite)), _ptr(tb)),
                     "gpry_group_set_gates")
 
-    def sweep_logexp(self, X, zeta, baseline, sigma_n, mask=None, M=None, want=("y", "sigma", "acq")):
+    def sweep_logexp(self, X, zeta, baseline, sigma_n, mask=None, M=None, want=("y", "sigma", "acq"),
+                     y_given=None, sigma_given=None):
         if X is not None:
             X = _f64(X)
             M = X.shape[0]
@@ -637,9 +667,16 @@ class DeviceGroup:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
         out = {k: (np.empty(M) if k in want else None) for k in ("y", "sigma", "acq")}
         n_nan = C.c_int64(0)
-        self._check(self._lib.gpry_group_sweep_logexp(
-            self._h, _ptr(X), M, _ptr(mask), float(zeta), float(baseline), float(sigma_n),
-            _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["acq"]), C.byref(n_nan)), "gpry_group_sweep_logexp")
+        if y_given is None and sigma_given is None:
+            self._check(self._lib.gpry_group_sweep_logexp(
+                self._h, _ptr(X), M, _ptr(mask), float(zeta), float(baseline), float(sigma_n),
+                _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["acq"]), C.byref(n_nan)), "gpry_group_sweep_logexp")
+        else:
+            y_given, sigma_given = _given_arrays(y_given, sigma_given, M)
+            self._check(self._lib.gpry_group_sweep_logexp_given(
+                self._h, _ptr(X), M, _ptr(mask), _ptr(y_given), _ptr(sigma_given), float(zeta), float(baseline),
+                float(sigma_n), _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["acq"]), C.byref(n_nan)),
+                "gpry_group_sweep_logexp_given")
         out["n_nan"] = n_nan.value
         self.sweep_epoch += 1
         self._sweep_M = M

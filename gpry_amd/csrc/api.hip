@@ -651,6 +651,29 @@ __global__ void sweep_finish_kernel(const double* __restrict__ mean_part, const 
     acq_all[m] = logexp_value(y, sd, fp.zeta, fp.baseline, fp.sigma_n);
 }
 
+// The finish of a sweep whose y the caller supplied (gpry_sweep_logexp_given; the reference's mpi.compute_y_parallel with y
+// given and sigma_y None, gpry/mpi.py:182-218 -> gpr.predict_std, gpry/gpr.py:1275-1352): y is the caller's, already in
+// y_all, and is neither mapped, clipped nor masked; sigma and acq are sweep_finish_kernel's arithmetic on the same per-tile
+// sums in the same order, so sigma is bit for bit the ordinary sweep's.  predict_std has no trust-region gate: only the
+// classifier bit zeroes sigma.
+__global__ void sweep_given_finish_kernel(const double* __restrict__ ss_part, int nt, int64_t ldp, int64_t m0, int64_t mc,
+                                          const uint8_t* __restrict__ mask, const double* __restrict__ y_all,
+                                          double* __restrict__ sig_all, double* __restrict__ acq_all, FinishParams fp) {
+    int64_t ml = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ml >= mc) return;
+    int64_t m = m0 + ml;
+    unsigned mk = mask ? mask[m] : 0u;
+    double ss = 0.0;
+#pragma unroll 8
+    for (int t = 0; t < nt; t++) ss += ss_part[(int64_t)t * ldp + ml];
+    double var = fp.C - ss;
+    if (var < 0.0) var = 0.0;
+    double sd = sqrt(var) * fp.y_std;
+    if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
+    sig_all[m] = sd;
+    acq_all[m] = logexp_value(y_all[m], sd, fp.zeta, fp.baseline, fp.sigma_n);
+}
+
 // A pruned sweep (option "sweep_prune"): the sigma of a candidate that is not (yet) contracted.  No evaluated std takes this
 // value (sqrt(var) * y_std >= 0, or NaN), so a shortlist record with it is known to carry a bound, not an exact acquisition.
 #define PRUNED_SIGMA (-1.0)
@@ -679,6 +702,29 @@ __global__ void sweep_mean_kernel(const double* __restrict__ mean_part, int nt_m
     double sd = sqrt(var) * fp.y_std;
     if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
     const double a = logexp_value(y, sd, fp.zeta, fp.baseline, fp.sigma_n);
+    ub[m] = a;
+    acq_all[m] = a;
+    sig_all[m] = PRUNED_SIGMA;
+}
+
+// Stage A of a pruned sweep whose y the caller supplied (gpry_sweep_logexp_given): it replaces the mean pass -- no panel, no
+// cross build, no candidate centring.  ub = acq_all = the acquisition at the caller's y and the prior sigma (0 on classifier-
+// inf rows, as the finish gives them), sig_all = PRUNED_SIGMA.  The bound is exact bit for bit by the argument at
+// sweep_mean_kernel: the finish (sweep_given_finish_kernel, sweep_scatter_finish_kernel) sums non-negative per-tile terms, so
+// var = C - ss <= C, and sqrt, * y_std, the rounded square, - sigma_n^2, max and log are monotone under round-to-nearest;
+// y and the linear term are the same operations on the same values.
+__global__ void sweep_given_bound_kernel(int64_t m0, int64_t mc, const uint8_t* __restrict__ mask,
+                                         const double* __restrict__ y_all, double* __restrict__ sig_all,
+                                         double* __restrict__ acq_all, double* __restrict__ ub, FinishParams fp) {
+    int64_t ml = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ml >= mc) return;
+    int64_t m = m0 + ml;
+    unsigned mk = mask ? mask[m] : 0u;
+    double var = fp.C - 0.0;
+    if (var < 0.0) var = 0.0;
+    double sd = sqrt(var) * fp.y_std;
+    if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
+    const double a = logexp_value(y_all[m], sd, fp.zeta, fp.baseline, fp.sigma_n);
     ub[m] = a;
     acq_all[m] = a;
     sig_all[m] = PRUNED_SIGMA;
@@ -780,8 +826,12 @@ static int64_t sweep_chunk(const gpry_ctx* ctx, int64_t M) {
 // runs the chunked sweep over candidates resident in ctx->dXc
 // mean_only: stage A of a pruned sweep -- the same panel-form decision and the same panel kernels, but the panel is not
 // stored and nothing is contracted: y, the bound ub (ctx->dub) and the initial acq / sigma (sweep_mean_kernel)
+// y_given: y is the caller's, resident in ctx->dy_all (or going up chunk by chunk from ctx->up_y): the panel is built without
+// mean partials and finished by sweep_given_finish_kernel; with mean_only, stage A is sweep_given_bound_kernel alone (the
+// panel-form decision is still taken from the model: the contraction rounds build the panel in that form)
 static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bool want_acq,
-                     double zeta, double baseline, double sigma_n, bool allow_split = false, bool mean_only = false) {
+                     double zeta, double baseline, double sigma_n, bool allow_split = false, bool mean_only = false,
+                     bool y_given = false) {
     const int64_t Np = ctx->Np;
     const int nt = (int)(Np / 128);
     const int64_t chunk = sweep_chunk(ctx, M);
@@ -878,13 +928,15 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
             fprintf(stderr, "\n");
         }
     }
-    if (fast_panel || hybrid_panel) GPRY_TRY(launch_cross_prepare(ctx));
+    const bool no_panel = mean_only && y_given;
+    if ((fast_panel || hybrid_panel) && !no_panel) GPRY_TRY(launch_cross_prepare(ctx));
     if (mean_only) ctx->prune.form = ctx->panel_form;
     // A fresh pool (gpry_sweep_logexp with a host array, option "sweep_upload"): the rows of chunk c go up on stream2 while
     // the main stream still works on chunk c - 1 -- 4.2 MB against 7.7 ms of kernels at N = 4096 -- and the main stream
     // waits for nothing but its own chunk (one event per chunk, never re-recorded within a call).  From pageable memory
     // hipMemcpyAsync returns when the rows are staged, so the host is one chunk ahead of the GPU, which is all it takes.
     const double* up_X = ctx->up_X;
+    const double* up_y = ctx->up_y;
     const size_t nchunk = (size_t)((M + chunk - 1) / chunk);
     if (up_X || overlap) {
         while (ctx->ev_pool.size() < 3 * nchunk + 1) {
@@ -905,6 +957,7 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
         const int64_t m0 = (int64_t)ci * chunk, mc = (M - m0 < chunk) ? M - m0 : chunk;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dXc + m0 * ctx->d, up_X + m0 * ctx->d, sizeof(double) * mc * ctx->d,
                                     hipMemcpyHostToDevice, side));
+        if (up_y) HIP_TRY(ctx, hipMemcpyAsync(ctx->dy_all + m0, up_y + m0, sizeof(double) * mc, hipMemcpyHostToDevice, side));
         if (gates_on_side && ctx->up_gates) {
             StreamSwap sw(ctx, side);
             StageScope s(ctx, "gates");
@@ -917,6 +970,7 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
         const int64_t m0 = (int64_t)ci * chunk, mc = (M - m0 < chunk) ? M - m0 : chunk, mcp = round_up(mc, 128);
         StageScope s(ctx, mean_only ? "sweep_mean" : "cross_build");
         if (mean_only) Kst = nullptr;       // (the kernels store the mean partials only)
+        if (y_given) mean_part = nullptr;   // (... or the panel only)
         if (small_build) return launch_cross_build_small(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1);
         if (fast_panel || hybrid_panel) return launch_cross_build_mfma(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1, hybrid_panel ? 1 : 0);
         return launch_cross_build(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1);
@@ -957,7 +1011,14 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
                     GPRY_TRY(launch_gates(ctx, ctx->dXc + m0 * ctx->d, mc, ctx->dmask + m0));
                 }
             }
-            GPRY_TRY(build_panel(ci, Kst, mean_part));
+            if (!no_panel) GPRY_TRY(build_panel(ci, Kst, mean_part));
+        }
+        if (no_panel) {
+            StageScope s(ctx, "sweep_given_bound");
+            hipLaunchKernelGGL(sweep_given_bound_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream,
+                               m0, mc, have_mask ? ctx->dmask : nullptr, ctx->dy_all, ctx->dsig_all, ctx->dacq_all, ctx->dub, fp);
+            HIP_TRY(ctx, hipGetLastError());
+            continue;
         }
         if (mean_only) {
             StageScope s(ctx, "sweep_mean");
@@ -1007,7 +1068,13 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
             if (ctx->opt_gemm_dma) GPRY_TRY(sweep_gemm_dma_sp_launch(ctx, g));
             else GPRY_TRY(gemm_f64_launch(ctx, g, false, false, EPI_SUMSQ));
         }
-        {
+        if (y_given) {
+            StageScope s(ctx, "sweep_finish");
+            hipLaunchKernelGGL(sweep_given_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream,
+                               ss_part, nt, mcp, m0, mc, have_mask ? ctx->dmask : nullptr, ctx->dy_all, ctx->dsig_all,
+                               ctx->dacq_all, fp);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
             StageScope s(ctx, "sweep_finish");
             hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream,
                                mean_part, ss_part, nt_mean, nt, mcp, m0, mc, have_mask ? ctx->dmask : nullptr,
@@ -1468,10 +1535,12 @@ int gpry_set_gates(gpry_ctx* ctx, const double* sv, const double* coef, int64_t 
     return 0;
 }
 
-int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* mask, double zeta,
-                      double baseline, double sigma_n, double* y_all, double* sigma_all, double* acq_all,
-                      int64_t* n_nan) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_logexp: ctx is NULL");
+}  // extern "C"
+
+// gpry_sweep_logexp (y_given NULL) and the sigma-only case of gpry_sweep_logexp_given (y_given: the caller's M values, which go
+// up with the pool and take the place of the posterior mean)
+static int sweep_impl(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* mask, const double* y_given, double zeta,
+                      double baseline, double sigma_n, double* y_all, double* sigma_all, double* acq_all, int64_t* n_nan) {
     GPRY_TRY(serve_stop(ctx));
     GPRY_TRY(require_model(ctx, true));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1497,14 +1566,18 @@ int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
     struct UploadScope {        // (cleared on every way out: a later sweep of the resident pool must not upload again)
         gpry_ctx* c; bool done = false;
         ~UploadScope() {
-            c->up_X = nullptr; c->up_gates = 0;
+            c->up_X = nullptr; c->up_y = nullptr; c->up_gates = 0;
             // a sweep that did not complete leaves no resident pool behind: with the chunked upload part of dXc would be
             // stale, and a later call with X == NULL must not pass the size check; the side stream is drained as well
             if (!done) { c->sw_M = 0; if (c->stream2) (void)hipStreamSynchronize(c->stream2); (void)hipStreamSynchronize(c->stream); }
         }
     } upload_scope{ctx};
     if (piped) { ctx->up_X = X; ctx->up_gates = ctx->gates_on ? 1 : 0; }
-    GPRY_TRY(run_sweep(ctx, M, have_mask, true, true, zeta, baseline, sigma_n, false, prune));
+    if (y_given) {
+        if (piped) ctx->up_y = y_given;     // (chunk by chunk beside the rows)
+        else HIP_TRY(ctx, hipMemcpyAsync(ctx->dy_all, y_given, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
+    }
+    GPRY_TRY(run_sweep(ctx, M, have_mask, true, true, zeta, baseline, sigma_n, false, prune, y_given != nullptr));
     if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, 64));
     HIP_TRY(ctx, hipMemsetAsync(ctx->dsel, 0, 8, ctx->stream));
     // (pruned: the bound is NaN exactly where y is.  The exact acquisition of a candidate with a finite y is not NaN either: a
@@ -1531,6 +1604,54 @@ int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
         GPRY_TRY(prune_snapshot(ctx));
         ctx->sw_pruned = 1;
     }
+    return 0;
+}
+
+extern "C" {
+
+int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* mask, double zeta,
+                      double baseline, double sigma_n, double* y_all, double* sigma_all, double* acq_all,
+                      int64_t* n_nan) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_logexp: ctx is NULL");
+    return sweep_impl(ctx, X, M, mask, nullptr, zeta, baseline, sigma_n, y_all, sigma_all, acq_all, n_nan);
+}
+
+int gpry_sweep_logexp_given(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* mask, const double* y_given,
+                            const double* sigma_given, double zeta, double baseline, double sigma_n, double* y_all,
+                            double* sigma_all, double* acq_all, int64_t* n_nan) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_logexp_given: ctx is NULL");
+    if (!y_given) return gpry_fail(ctx, -1, "sweep_logexp_given: y_given must not be NULL");
+    if (!sigma_given)
+        return sweep_impl(ctx, X, M, mask, y_given, zeta, baseline, sigma_n, y_all, sigma_all, acq_all, n_nan);
+    // both given: acq = LogExp.f(y, sigma_y) and nothing else -- no panel, no gates, no mask (the mask argument is ignored).
+    // No factor is read, so none is required; the pool rows are still taken (X != NULL) so that the resident pool stays
+    // the one the arrays belong to, which needs the row width of gpry_set_train.
+    GPRY_TRY(serve_stop(ctx));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (M <= 0) return gpry_fail(ctx, -1, "sweep: M must be > 0");
+    if (X && ctx->d <= 0) return gpry_fail(ctx, -1, "sweep_logexp_given: set_train before a pool of rows");
+    ctx->sw_pruned = 0;
+    GPRY_TRY(upload_candidates(ctx, X, M, nullptr));
+    ctx->sw_M = 0;                          // (until the call completes: no resident pool behind a failed one)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dy_all, y_given, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dsig_all, sigma_given, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
+    {
+        StageScope s(ctx, "sweep_finish");
+        hipLaunchKernelGGL(logexp_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream,
+                           ctx->dy_all, ctx->dsig_all, M, zeta, baseline, sigma_n, ctx->dacq_all);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, 64));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dsel, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(count_nan_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->dacq_all, M, ctx->dsel);
+    unsigned long long nn = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&nn, ctx->dsel, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (y_all) HIP_TRY(ctx, hipMemcpyAsync(y_all, ctx->dy_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
+    if (sigma_all) HIP_TRY(ctx, hipMemcpyAsync(sigma_all, ctx->dsig_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
+    if (acq_all) HIP_TRY(ctx, hipMemcpyAsync(acq_all, ctx->dacq_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sw_M = M;
+    if (n_nan) *n_nan = (int64_t)nn;
     return 0;
 }
 

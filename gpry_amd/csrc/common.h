@@ -176,6 +176,7 @@ struct gpry_ctx {
     int opt_sweep_overlap = 0;         // 1: the cross-kernel panel of chunk c + 1 is built on the side stream underneath the contraction of chunk c (two panels)
     int opt_sweep_upload = 1;          // 1: a fresh candidate pool is uploaded chunk by chunk on stream2, chunk c + 1 underneath the kernels of chunk c
     const double* up_X = nullptr;      // host pool of the sweep in flight whose chunks are still to be uploaded (run_sweep)
+    const double* up_y = nullptr;      // ... and the caller's y of a sweep with given y (gpry_sweep_logexp_given), beside them
     int up_gates = 0;                  // ... and the device gates are evaluated chunk by chunk behind each upload
     int opt_predict_gates = 0;         // 1: gpry_predict ORs the device gates (gpry_set_gates) into the caller's mask, as the sweep does
     // pruned sweep (option "sweep_prune", api.hip): gpry_sweep_logexp with no arrays wanted leaves y and a per-candidate upper

@@ -203,6 +203,29 @@ int gpry_group_sweep_logexp(gpry_group* g, const double* X, int64_t M, const uin
     return 0;
 }
 
+int gpry_group_sweep_logexp_given(gpry_group* g, const double* X, int64_t M, const uint8_t* mask, const double* y_given,
+                                  const double* sigma_given, double zeta, double baseline, double sigma_n, double* y_all,
+                                  double* sigma_all, double* acq_all, int64_t* n_nan) {
+    if (!g) return group_fail(nullptr, -1, "gpry_group_sweep_logexp_given: group is NULL");
+    if (M <= 0) return group_fail(g, -1, "group sweep: M must be > 0");
+    if (!y_given) return group_fail(g, -1, "group sweep_logexp_given: y_given must not be NULL");
+    if (!X && M != g->M) return group_fail(g, -1, "X == NULL but the resident candidate set has %lld rows, not %lld",
+                                          (long long)g->M, (long long)M);
+    if (X) group_shards(g, M);
+    std::vector<int64_t> nn(g->members.size(), 0);
+    GPRY_TRY(for_members(g, [&](int i) -> int {
+        gpry_ctx* c = g->members[i];
+        const int64_t lo = g->lo[i], m = g->hi[i] - lo;
+        if (m <= 0) return 0;
+        return gpry_sweep_logexp_given(c, X ? X + lo * c->d : nullptr, m, mask ? mask + lo : nullptr, y_given + lo,
+                                       sigma_given ? sigma_given + lo : nullptr, zeta, baseline, sigma_n,
+                                       y_all ? y_all + lo : nullptr, sigma_all ? sigma_all + lo : nullptr,
+                                       acq_all ? acq_all + lo : nullptr, &nn[i]);
+    }));
+    if (n_nan) { *n_nan = 0; for (int64_t v : nn) *n_nan += v; }
+    return 0;
+}
+
 int gpry_group_sweep_fetch(gpry_group* g, int64_t M, double* y_all, double* sigma_all, double* acq_all) {
     if (!g) return group_fail(nullptr, -1, "gpry_group_sweep_fetch: group is NULL");
     if (M <= 0 || M != g->M) return group_fail(g, -1, "group sweep_fetch: the resident sweep has %lld candidates, not %lld",

@@ -441,12 +441,19 @@ class NORA(GenericGPAcquisition):
         self._group_key, self._group_model = gpr.device, None
         return self._group, True
 
-    def _device_sweep(self, gpr, X, need_arrays=False):
+    def _device_sweep(self, gpr, X, need_arrays=False, y_given=None, sigma_given=None):
         """Mean, std and LogExp acquisition of every row of X (this rank's shard on the
-        device; y and sigma all-gathered so that every rank holds the full arrays)."""
+        device; y and sigma all-gathered so that every rank holds the full arrays).
+
+        ``y_given`` / ``sigma_given``: the sampler's own arrays (mpi.compute_y_parallel,
+        gpry/mpi.py:182-218).  With ``y_given`` alone the device computes sigma only (predict_std: no
+        trust-region gate) and the caller's y is returned as it is; with both it computes the
+        acquisition alone."""
         t0 = time()
         X = np.ascontiguousarray(X, dtype=float)
         M = len(X)
+        given = y_given is not None
+        both = given and sigma_given is not None
         gpr._ensure_factor()
         gpr._push_affine()
         dev, grouped = self._sweeper(gpr)
@@ -461,12 +468,14 @@ class NORA(GenericGPAcquisition):
                     raise np.linalg.LinAlgError(f"a group member could not factorise the model (info={info})")
                 self._group_model = key
         # classifier / trust-region verdicts: on the device if they have a device form
+        # (y given: the classifier alone -- predict_std has no trust-region gate, and the device ignores that bit then;
+        # both given: no gates at all)
         mask = None
-        if hi > lo:
+        if hi > lo and not both:
             on_device = hasattr(gpr, "_push_gates") and (gpr._push_gates(sinks=[gpr.device, dev]) if grouped
                                                          else gpr._push_gates())
             if not on_device:
-                mask = gpr._masks(X[lo:hi], False, False)
+                mask = gpr._masks(X[lo:hi], False, given)
         noise = gpr.noise_level
         if np.iterable(noise):
             raise ValueError("NORA needs a scalar noise_level (the reference passes it raw to "
@@ -481,22 +490,39 @@ class NORA(GenericGPAcquisition):
         lazy = (not sharded and not need_arrays and self.gather_y == "auto"
                 and hasattr(dev, "sweep_fetch"))
         want = ("y", "sigma") if ((gather and sharded) or (not sharded and not lazy)) else ()
-        prune_on = self._prune_targets(dev, grouped) if (lazy and self.exact_prune) else []
+        if given:                   # (the caller's arrays are not fetched back)
+            want = () if both else tuple(k for k in want if k != "y")
+        prune_on = self._prune_targets(dev, grouped) if (lazy and self.exact_prune and not both) else []
         for t in prune_on:
             t.set_option("sweep_prune", 1)
+        kw = {}
+        if given:
+            kw = dict(y_given=np.asarray(y_given, dtype=float)[lo:hi],
+                      sigma_given=None if sigma_given is None else np.asarray(sigma_given, dtype=float)[lo:hi])
         try:
             out = dev.sweep_logexp(None if resident else X[lo:hi], self.acq_func.zeta, gpr.y_max,
-                                   noise, mask=mask, M=hi - lo, want=want)
+                                   noise, mask=mask, M=hi - lo, want=want, **kw)
         finally:
             for t in prune_on:
                 t.set_option("sweep_prune", 0)
         self._pruned_on = prune_on
         self._sweep_dev = dev
-        gpr.n_eval += M
+        if not both:
+            gpr.n_eval += M         # (predict / predict_std count; the acquisition alone does not)
         if out["n_nan"]:
             raise ValueError("Acquisition function value not a number: nan")
-        y, s = (out.get("y"), out.get("sigma")) if want else (None, None)
-        if sharded and gather:
+        if given:
+            y, s = y_given, (sigma_given if both else (out.get("sigma") if want else None))
+            if sharded and gather and not both:
+                # only sigma is gathered: every rank holds the caller's y
+                per = -(-M // self.comm.world)
+                buf = np.zeros(per)
+                buf[:hi - lo] = s
+                alls = self.comm.allgather(buf)
+                s = np.concatenate([alls[r, :max(0, min(per, M - r * per))] for r in range(self.comm.world)])
+        else:
+            y, s = (out.get("y"), out.get("sigma")) if want else (None, None)
+        if sharded and gather and not given:
             per = -(-M // self.comm.world)
             buf = np.zeros((2, per))
             buf[0, :hi - lo], buf[1, :hi - lo] = y, s
@@ -584,25 +610,32 @@ class NORA(GenericGPAcquisition):
         """Materialise ``_y_mc`` / ``_sigma_y_mc`` of the last (un-reweighted) sweep if they were
         left on the device and are still there."""
         lazy = getattr(self, "_lazy", None)
-        if lazy is None or self._y_mc is not None:
+        if lazy is None or (self._y_mc is not None and self._sigma_y_mc is not None):
             return
         dev, epoch = lazy
         if dev.sweep_epoch != epoch:
             raise RuntimeError("the sweep arrays of the last MC sample are no longer on the device")
-        out = dev.sweep_fetch(("y", "sigma"))
-        self._y_mc, self._sigma_y_mc = out["y"], out["sigma"]
+        if self._y_mc is not None:          # the sampler's own y: sigma alone was left on the device
+            self._sigma_y_mc = dev.sweep_fetch(("sigma",))["sigma"]
+        else:
+            out = dev.sweep_fetch(("y", "sigma"))
+            self._y_mc, self._sigma_y_mc = out["y"], out["sigma"]
         self._lazy = None
 
     def _set_MC_sample(self, X, y, sigma_y, w, ensure_y_sigma_y=False, gpr=None):
-        """gp_acquisition.py:858-873; the (y, sigma) evaluation is the device sweep."""
+        """gp_acquisition.py:858-873; the (y, sigma) evaluation is the device sweep, in the three
+        cases of mpi.compute_y_parallel (gpry/mpi.py:182-218): no y -- mean and sigma computed
+        (a sigma_y without y is ignored); y alone -- kept as given, sigma computed (predict_std);
+        both -- kept, only the acquisition computed."""
         self.is_last_MC_reweighted = False
         self._X_mc, self._y_mc, self._sigma_y_mc, self._w_mc = X, y, sigma_y, w
         if ensure_y_sigma_y:
-            if y is not None or sigma_y is not None:
-                raise NotImplementedError("samplers that return their own y / sigma_y are not "
-                                          "supported by the device sweep (all of the reference's "
-                                          "samplers return None for both)")
-            self._y_mc, self._sigma_y_mc = self._device_sweep(gpr, X)
+            if y is None:
+                self._y_mc, self._sigma_y_mc = self._device_sweep(gpr, X)
+            else:
+                _, s = self._device_sweep(gpr, X, y_given=y, sigma_given=sigma_y)
+                if sigma_y is None:
+                    self._sigma_y_mc = s        # (None while it waits on the device: _fetch_lazy)
             self._dev_index = np.arange(len(X))
 
     def _reweight_last_MC_sample(self, gpr, bounds=None, ensure_sigma_y=False):

@@ -273,6 +273,25 @@ int gpry_sweep_logexp(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
                       double zeta, double baseline, double sigma_n,
                       double* y_all, double* sigma_all, double* acq_all,
                       int64_t* n_nan);
+/* The sweep of a pool whose sampler supplied y, or y and sigma_y (NORA._set_MC_sample, gpry/gp_acquisition.py:858-873 ->
+ * mpi.compute_y_parallel, gpry/mpi.py:182-218; the acquisition is LogExp.f on those arrays, gp_acquisition.py:1049-1054).
+ * y_given (M values) is required; X == NULL re-uses the resident pool as in gpry_sweep_logexp.
+ *   sigma_given == NULL: y is the caller's as it is -- no y map, no clip, and a masked row does NOT get -inf; sigma is
+ *     gpr.predict_std (gpry/gpr.py:1275-1352): exactly the sigma of gpry_sweep_logexp on the same pool (same panel form,
+ *     contraction and per-tile summation order), 0 where GPRY_MASK_CLASSIFIED_INF is set.  predict_std has no trust-region
+ *     gate: GPRY_MASK_OUTSIDE_TRUST (the caller's or the device gates') changes neither y nor sigma, and such a row keeps a
+ *     finite acquisition.  acq = LogExp.f(y_given, sigma).  Option "sweep_prune" with no arrays wanted: the bound of every
+ *     candidate comes from y_given and the prior sigma, without a mean pass; gpry_sweep_topk / gpry_sweep_fetch then work as
+ *     after a pruned gpry_sweep_logexp.
+ *   sigma_given != NULL: acq = LogExp.f(y_given, sigma_given) and nothing else -- no panel, no contraction, no gates, no mask
+ *     (mask is ignored).  No factor is needed (the rows of X need the width of gpry_set_train).
+ * y_all / sigma_all / acq_all / n_nan and the resident arrays as for gpry_sweep_logexp: gpry_sweep_fetch and
+ * gpry_sweep_topk work unchanged on them. */
+int gpry_sweep_logexp_given(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* mask,
+                            const double* y_given, const double* sigma_given,
+                            double zeta, double baseline, double sigma_n,
+                            double* y_all, double* sigma_all, double* acq_all,
+                            int64_t* n_nan);
 /* How the cross-kernel panel K(X*, X_train) (gpry/gpr.py:1179) of the context's last sweep / panel predict was built, and the
  * error estimates of the model that decided it.  *panel_form: 0 none yet, 1 distances from the matrix pipe (expanded form
  * |x|^2 + |y|^2 - 2 x.y on centred coordinates), 2 difference form (as scipy's cdist), 3 the small-batch kernel (difference
@@ -367,6 +386,11 @@ int gpry_group_set_gates(gpry_group* group, const double* sv, const double* coef
 int gpry_group_sweep_logexp(gpry_group* group, const double* X, int64_t M, const uint8_t* mask,
                             double zeta, double baseline, double sigma_n, double* y_all,
                             double* sigma_all, double* acq_all, int64_t* n_nan);
+/* gpry_sweep_logexp_given over the whole pool likewise: member i gets rows [lo_i, hi_i) of y_given (and sigma_given). */
+int gpry_group_sweep_logexp_given(gpry_group* group, const double* X, int64_t M, const uint8_t* mask,
+                                  const double* y_given, const double* sigma_given,
+                                  double zeta, double baseline, double sigma_n, double* y_all,
+                                  double* sigma_all, double* acq_all, int64_t* n_nan);
 int gpry_group_sweep_fetch(gpry_group* group, int64_t M, double* y_all, double* sigma_all,
                            double* acq_all);
 /* Global shortlist: every member selects its Kp best (gpry_sweep_topk, exclusions = sorted GLOBAL
