@@ -2012,13 +2012,14 @@ static int prune_eval(gpry_ctx* ctx, int64_t n) {
         ctx->kst_cap = Np * np_max;
     }
     GPRY_TRY(ensure_part(ctx, (int64_t)nt * np_max));
-    const int64_t rows = round_up(np_max, 256);
-    if (rows > ctx->xg_cap) {
+    // (in doubles, not rows: a later model may have more dimensions than the one the buffer was made for)
+    const int64_t xg_need = round_up(np_max, 256) * ctx->d;
+    if (xg_need > ctx->xg_cap) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->dXg) GPRY_TRY(dev_free(ctx, ctx->dXg));
         ctx->dXg = nullptr; ctx->xg_cap = 0;
-        GPRY_TRY(dev_alloc(ctx, &ctx->dXg, rows * ctx->d));
-        ctx->xg_cap = rows;
+        GPRY_TRY(dev_alloc(ctx, &ctx->dXg, xg_need));
+        ctx->xg_cap = xg_need;
     }
     const int form = ctx->prune.form;       // the panel form of stage A (a gpry_predict in between may have built another)
     if (form == 1 || form == 4) GPRY_TRY(launch_cross_prepare(ctx));

@@ -210,7 +210,7 @@ struct gpry_ctx {
     double* dub = nullptr;             // M: upper bound of each candidate's acquisition (prior sigma)
     int64_t ub_cap = 0;
     double* dXg = nullptr;             // gathered candidate rows of a compact evaluation (rows padded to 256, zeros)
-    int64_t xg_cap = 0;                // rows
+    int64_t xg_cap = 0;                // doubles
     int64_t* dgidx = nullptr;          // their pool indices
     int64_t gidx_cap = 0;
 
