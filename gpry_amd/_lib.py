@@ -61,6 +61,9 @@ SIGNATURES = {
     "gpry_lml_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "gpry_predict": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_debug_serve_stats": (C.c_int, [_vp, _P(C.c_int64), _P(C.c_int64)]),
+    "gpry_ns_prior": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int64, _vp, _vp, _P(C.c_double)]),
+    "gpry_ns_generation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64, C.c_int64,
+                                     C.c_int, C.c_int, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -388,6 +391,30 @@ class Device:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.gpry_debug_serve_stats(self._h, C.byref(a), C.byref(b)), "gpry_debug_serve_stats")
         return a.value, b.value
+
+    # -- nested sampling of the mean (gpry_amd/nested.py drives these two) ----------------
+    def ns_prior(self, lo, hi, seed, n):
+        """``n`` points uniform on the box [lo, hi] and their ``predict`` values: ``(X (n, d), y (n,), device_ms)``."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X, y, ms = np.empty((int(n), self.d)), np.empty(int(n)), C.c_double(0.0)
+        self._check(self._lib.gpry_ns_prior(self._h, _ptr(lo), _ptr(hi), int(seed), int(n), _ptr(X), _ptr(y),
+                                            C.byref(ms)), "gpry_ns_prior")
+        return X, y, ms.value
+
+    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats):
+        """One generation of ``k`` slice-sampling chains above ``lstar``: ``(X_new (k, d), y_new (k,), ncalls (k,),
+        device_ms)``."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X_surv = _f64(X_surv)
+        n = X_surv.shape[0]
+        if X_surv.ndim != 2 or X_surv.shape[1] != self.d:
+            raise ValueError(f"expected survivors of shape (n, {self.d}), got {X_surv.shape}")
+        y_surv, W = _f64(y_surv, (n,)), _f64(W, (self.d, self.d))
+        X_new, y_new, cnt, ms = np.empty((int(k), self.d)), np.empty(int(k)), np.zeros(int(k), np.int64), C.c_double(0.0)
+        self._check(self._lib.gpry_ns_generation(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n, float(lstar),
+                                                 _ptr(W), int(seed), int(generation), int(k), int(num_repeats),
+                                                 _ptr(X_new), _ptr(y_new), _ptr(cnt), C.byref(ms)), "gpry_ns_generation")
+        return X_new, y_new, cnt, ms.value
 
     def set_gates(self, sv=None, coef=None, gamma=0.0, intercept=0.0, positive_is_finite=True,
                   trust_bounds=None):

@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <functional>
 
-static int require_model(gpry_ctx* ctx, bool need_factor) {
+int require_model(gpry_ctx* ctx, bool need_factor) {
     if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
     if (!ctx->have_theta) return gpry_fail(ctx, -1, "no hyperparameters (call gpry_set_theta)");
     if (need_factor && !ctx->factor_valid) return gpry_fail(ctx, -1, "model not factorised (call gpry_factorize)");

@@ -414,6 +414,7 @@ int logdet_and_quad(gpry_ctx* ctx, const double* L, const double* z, int64_t Np,
 int rocsolver_potrf_trtri(gpry_ctx* ctx, double* A, double* V, int64_t Np, int want_v);
 
 // ---- server.hip: resident predict kernel --------------------------------------------
+int require_model(gpry_ctx* ctx, bool need_factor);   // api.hip: training set, theta and (need_factor) factor present
 int serve_stop(gpry_ctx* ctx);          // no-op when nothing is running; every model-changing entry point calls it first
 void serve_free(gpry_ctx* ctx);
 void serve_stats(gpry_ctx* ctx, int64_t* launches, int64_t* requests);

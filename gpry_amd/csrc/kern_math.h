@@ -248,3 +248,59 @@ __device__ __forceinline__ double mean_slice(const double* x, const double* __re
     __syncthreads();          // `red` may be reused by the caller's next point
     return out;
 }
+
+
+// ------------------------------------------------------------------------------------
+// Gates of ONE point (gpry_set_gates), shared by the resident predict kernel (server.hip) and the nested sampler
+// (nested.hip), so that a point gets the same verdict whichever of the two evaluates it.
+struct GateParams {
+    const double* sv; const double* coef; const double* trust;
+    int64_t nsv; double gamma, intercept;
+    int positive_finite, has_trust;
+};
+static GateParams make_gp(gpry_ctx* ctx) {
+    GateParams g;
+    g.sv = ctx->gate_sv; g.coef = ctx->gate_coef; g.trust = ctx->gate_trust;
+    g.nsv = ctx->gate_nsv; g.gamma = ctx->gate_gamma; g.intercept = ctx->gate_intercept;
+    g.positive_finite = ctx->gate_positive_finite; g.has_trust = ctx->gate_has_trust;
+    return g;
+}
+// GPRY_MASK_* bits of one point (raw coordinates x in LDS): the trust box on the raw coordinates, the SVM decision
+// function sum_r coef_r exp(-gamma |x_ - sv_r|^2) + intercept on the transformed ones -- the per-pair arithmetic of
+// gates_kernel (kernel_build.hip), the support vectors dealt out over the 256 threads and their terms added by the
+// fixed LDS tree.  Valid in every thread.
+__device__ __forceinline__ unsigned point_gate_bits(const double* x, const GateParams& a, const KernParams& kp,
+                                                    const AffParams& ap, double* red) {
+    const int t = threadIdx.x;
+    unsigned bits = 0;
+    if (a.has_trust) {
+        for (int k = 0; k < kp.d; k++) {
+            const double v = x[k];
+            if (!(v >= a.trust[2 * k] && v <= a.trust[2 * k + 1])) bits |= GPRY_MASK_OUTSIDE_TRUST;
+        }
+    }
+    if (a.nsv > 0) {
+        double part = 0.0;
+        for (int64_t r = t; r < a.nsv; r += 256) {
+            double r2 = 0.0;
+            for (int k = 0; k < kp.d; k++) {
+                double v = x[k];
+                if (kp.has_aff) v = (v - ap.lo[k]) / ap.span[k];
+                const double df = v - a.sv[r * kp.d + k];
+                r2 = fma(df, df, r2);
+            }
+            part = fma(a.coef[r], fast_exp_neg(a.gamma * r2), part);
+        }
+        red[t] = part;
+        __syncthreads();
+        for (int s2 = 128; s2 >= 1; s2 >>= 1) {
+            if (t < s2) red[t] += red[t + s2];
+            __syncthreads();
+        }
+        const double dec = red[0] + a.intercept;
+        __syncthreads();
+        const bool finite = a.positive_finite ? dec > 0.0 : !(dec > 0.0);
+        if (!finite) bits |= GPRY_MASK_CLASSIFIED_INF;
+    }
+    return bits;
+}

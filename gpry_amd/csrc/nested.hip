@@ -1,0 +1,347 @@
+// Nested sampling of the surrogate's posterior mean on the device: the two kernels behind gpry_ns_prior and
+// gpry_ns_generation.  The bookkeeping (sorting, prior volumes, whitening matrix, stopping, weights, evidence) is
+// host-side, in gpry_amd/nested.py; it replaces the PolyChord / UltraNest runs of gpry/gp_acquisition.py:760-856,
+// which call gpr.predict once per point.
+//
+// Likelihood.  y(x) is gpr.predict(x[None]) bit for bit: the slices of the one-point path (nsplit = clamp(N / 1024, 1, 8),
+// the same rows_per_split, mean_slice of kern_math.h), added in slice order from 0.0; then fmin(mu * y_std + y_mean,
+// clip_hi) written with explicit roundings (the library builds with -ffp-contract=fast, which would fuse it into an FMA
+// on the device while the host computes a product and a sum -- and __dmul_rn / __dadd_rn are plain operators in this
+// toolchain's headers, which it contracts all the same: ns_rn() hides the product from the combiner); then the gates of
+// point_gate_bits (what the resident predict kernel applies), -inf for a gated point.
+//
+// Randomness.  Philox4x32-10 keyed by the seed; every draw has a fixed counter (phase, generation, chain, step, draw)
+// -- word 0 = phase << 24 | draw, 1 = generation, 2 = chain (the point's index in the prior phase), 3 = step -- so no
+// value depends on how workgroups are scheduled.  tests/tools/ns_philox.py restates it in numpy.
+//
+// Chains.  One 256-thread workgroup per chain, the whole walk of `num_repeats` slice-sampling steps (Neal 2003:
+// stepping out, then shrinkage) inside the kernel.  Chains never communicate; the host launches one kernel per
+// generation.
+#include "kern_math.h"
+
+#define NS_PHASE_PRIOR 0u
+#define NS_PHASE_START 1u
+#define NS_PHASE_STEP 2u
+#define NS_STEP_OUT_MAX 32
+#define NS_SHRINK_MAX 64
+#define NS_DRAW_OFFSET 16u          // draws 0..15 of a step: the normal vector z (two coordinates per draw)
+#define NS_DRAW_SHRINK 17u          // draws 17..17+63: the shrinkage tries
+
+struct NsU2 { double a, b; };
+
+// the value of a product as it was rounded: an empty asm statement the combiner cannot look through, so that the sum
+// it feeds is not fused into an FMA (-ffp-contract=fast) and rounds as the host's two operations do
+__device__ __forceinline__ double ns_rn(double v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// Philox4x32-10 (Salmon et al. 2011): two uniforms in [0, 1), 53 bits each, from words (0, 1) and (2, 3)
+__device__ __forceinline__ NsU2 ns_philox(unsigned long long seed, unsigned phase, unsigned draw, unsigned gen,
+                                          unsigned chain, unsigned step) {
+    unsigned c0 = (phase << 24) | draw, c1 = gen, c2 = chain, c3 = step;
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0, hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    NsU2 u;
+    u.a = (double)((((unsigned long long)c0 << 32) | c1) >> 11) * 0x1.0p-53;
+    u.b = (double)((((unsigned long long)c2 << 32) | c3) >> 11) * 0x1.0p-53;
+    return u;
+}
+
+struct NsArgs {
+    const double* Xs; const double* alpha_;
+    int64_t rows_per_split;
+    int nsplit, gates;
+    double y_std, y_mean, clip_hi;
+    GateParams gate;
+    unsigned long long seed;
+    double lo[GPRY_MAX_DIM], hi[GPRY_MAX_DIM];
+};
+
+// y of the point x (raw coordinates in LDS), valid in every thread.  Same slices, sums and finish as gpry_predict's
+// one-point path (api.hip) and the resident kernel's (server.hip).
+template <int DP, int KID>
+__device__ double ns_eval(const double* x, const NsArgs& a, const KernParams& kp, const AffParams& ap, double* r2s,
+                          double* red, double* s_y) {
+    double mu = 0.0;
+    for (int s = 0; s < a.nsplit; s++) {
+        const double v = mean_slice<DP, KID>(x, a.Xs, a.alpha_, (int64_t)s * a.rows_per_split, a.rows_per_split, kp, ap, r2s, red);
+        mu = mu + v;                         // (thread 0 holds the slice sums)
+    }
+    const unsigned bits = a.gates ? point_gate_bits(x, a.gate, kp, ap, red) : 0u;
+    if (threadIdx.x == 0) {
+        double y = fmin(ns_rn(mu * a.y_std) + a.y_mean, a.clip_hi);
+        if (bits) y = -INFINITY;
+        *s_y = y;
+    }
+    __syncthreads();
+    const double y = *s_y;
+    __syncthreads();
+    return y;
+}
+
+// Prior draws: point i (one workgroup) is lo + u * (hi - lo), u from the counter (PRIOR, draw j, 0, i, 0) for
+// coordinates 2j and 2j + 1, clamped to hi.
+template <int DP, int KID>
+__global__ __launch_bounds__(256) void ns_prior_kernel(NsArgs a, KernParams kp, AffParams ap, double* __restrict__ X_out,
+                                                       double* __restrict__ y_out) {
+    __shared__ double r2s[MEAN_SLICE_CH];
+    __shared__ double red[256];
+    __shared__ double s_x[GPRY_MAX_DIM];
+    __shared__ double s_y;
+    const int t = threadIdx.x;
+    const unsigned i = blockIdx.x;
+    if (t < kp.d) {
+        const NsU2 u = ns_philox(a.seed, NS_PHASE_PRIOR, (unsigned)(t / 2), 0u, i, 0u);
+        const double span = a.hi[t] - a.lo[t];
+        const double x = fmin(a.lo[t] + ns_rn(((t & 1) ? u.b : u.a) * span), a.hi[t]);
+        s_x[t] = x;
+        X_out[(int64_t)i * kp.d + t] = x;
+    }
+    __syncthreads();
+    const double y = ns_eval<DP, KID>(s_x, a, kp, ap, r2s, red, &s_y);
+    if (t == 0) y_out[i] = y;
+}
+
+// One generation: chain c starts from a survivor drawn uniformly (counter (START, 0, gen, c, 0)) and makes
+// `num_repeats` slice-sampling steps on {x in the box : y(x) > lstar}.  Step s: direction v = W z / |z|, z ~ N(0, I) by
+// Box-Muller from draws 0..(d-1)/2; the interval [-r, 1 - r] along v (r: draw 16) stepped out by whole widths, at most
+// 32 per side; then up to 64 shrinkage tries (draws 17..), each uniform on the interval.  A step that hits a cap keeps
+// the current point.  Outputs: the chain's last point, its y and the number of evaluations it made.
+template <int DP, int KID>
+__global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, AffParams ap,
+                                                       const double* __restrict__ X_surv, const double* __restrict__ y_surv,
+                                                       int64_t nsurv, const double* __restrict__ W, double lstar, unsigned gen,
+                                                       int num_repeats, double* __restrict__ X_new, double* __restrict__ y_new,
+                                                       int64_t* __restrict__ ncalls) {
+    __shared__ double r2s[MEAN_SLICE_CH];
+    __shared__ double red[256];
+    __shared__ double s_W[GPRY_MAX_DIM * GPRY_MAX_DIM];
+    __shared__ double s_x[GPRY_MAX_DIM], s_u[GPRY_MAX_DIM], s_v[GPRY_MAX_DIM], s_z[GPRY_MAX_DIM];
+    __shared__ double s_xt[GPRY_MAX_DIM], s_ut[GPRY_MAX_DIM];
+    __shared__ double s_y;
+    const int t = threadIdx.x, d = kp.d;
+    const unsigned c = blockIdx.x;
+    // the starting survivor
+    const NsU2 us = ns_philox(a.seed, NS_PHASE_START, 0u, gen, c, 0u);
+    int64_t j = (int64_t)(us.a * (double)nsurv);
+    if (j > nsurv - 1) j = nsurv - 1;
+    for (int e = t; e < d * d; e += 256) s_W[e] = W[e];
+    double y_cur = y_surv[j];
+    if (t < d) {
+        s_x[t] = X_surv[j * d + t];
+        s_u[t] = (s_x[t] - a.lo[t]) / (a.hi[t] - a.lo[t]);
+    }
+    __syncthreads();
+    int64_t n_eval = 0;
+    // the point at position tt along v: inside the box and above lstar?  (evaluates only inside the box)
+    auto try_at = [&](double tt, double* y_out) -> bool {
+        if (t < d) {
+            const double u = s_u[t] + tt * s_v[t];
+            s_ut[t] = u;
+            s_xt[t] = a.lo[t] + u * (a.hi[t] - a.lo[t]);
+        }
+        __syncthreads();
+        bool inside = true;
+        for (int k = 0; k < d; k++)
+            inside = inside && s_ut[k] >= 0.0 && s_ut[k] <= 1.0 && s_xt[k] >= a.lo[k] && s_xt[k] <= a.hi[k];
+        if (!inside) { __syncthreads(); return false; }
+        const double y = ns_eval<DP, KID>(s_xt, a, kp, ap, r2s, red, &s_y);
+        n_eval++;
+        *y_out = y;
+        return y > lstar;
+    };
+    for (int s = 0; s < num_repeats; s++) {
+        // direction
+        if (t < (d + 1) / 2) {
+            const NsU2 u = ns_philox(a.seed, NS_PHASE_STEP, (unsigned)t, gen, c, (unsigned)s);
+            const double rad = sqrt(-2.0 * log(1.0 - u.a)), ang = 6.283185307179586 * u.b;
+            s_z[2 * t] = rad * cos(ang);
+            if (2 * t + 1 < d) s_z[2 * t + 1] = rad * sin(ang);
+        }
+        __syncthreads();
+        double nz = 0.0;
+        for (int k = 0; k < d; k++) nz += s_z[k] * s_z[k];
+        nz = sqrt(nz);
+        if (t < d) {
+            double v = 0.0;
+            for (int k = 0; k <= t; k++) v += s_W[t * d + k] * s_z[k];
+            s_v[t] = nz > 0.0 ? v / nz : 0.0;
+        }
+        __syncthreads();
+        // stepping out
+        const double r = ns_philox(a.seed, NS_PHASE_STEP, NS_DRAW_OFFSET, gen, c, (unsigned)s).a;
+        double lt = -r, rt = 1.0 - r, yt = 0.0;
+        for (int q = 0; q < NS_STEP_OUT_MAX && try_at(lt, &yt); q++) lt -= 1.0;
+        for (int q = 0; q < NS_STEP_OUT_MAX && try_at(rt, &yt); q++) rt += 1.0;
+        // shrinkage towards the current point (position 0)
+        for (int q = 0; q < NS_SHRINK_MAX; q++) {
+            const double u = ns_philox(a.seed, NS_PHASE_STEP, NS_DRAW_SHRINK + (unsigned)q, gen, c, (unsigned)s).a;
+            const double tt = lt + u * (rt - lt);
+            if (try_at(tt, &yt)) {
+                if (t < d) { s_x[t] = s_xt[t]; s_u[t] = s_ut[t]; }
+                y_cur = yt;
+                break;
+            }
+            if (tt < 0.0) lt = tt; else rt = tt;
+        }
+        __syncthreads();
+    }
+    if (t < d) X_new[(int64_t)c * d + t] = s_x[t];
+    if (t == 0) { y_new[c] = y_cur; ncalls[c] = n_eval; }
+}
+
+// ---- host side -----------------------------------------------------------------------------------
+static int ns_args(gpry_ctx* ctx, const double* lo, const double* hi, unsigned long long seed, NsArgs* a, KernParams* kp,
+                   AffParams* ap) {
+    if (ctx->d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "nested sampler: d = %d > %d", ctx->d, GPRY_MAX_DIM);
+    GPRY_TRY(ensure_pred_xs(ctx));
+    *kp = make_kp(ctx);
+    *ap = make_ap(ctx, kp->has_aff);
+    int nsplit = (int)(ctx->N / 1024);            // the slices of the one-point path (api.hip: gpry_predict)
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > 8) nsplit = 8;
+    a->Xs = ctx->dXs; a->alpha_ = ctx->dalpha_;
+    a->nsplit = nsplit;
+    a->rows_per_split = round_up((ctx->N + nsplit - 1) / nsplit, 32);
+    a->gates = ctx->gates_on;
+    a->gate = make_gp(ctx);
+    a->y_std = ctx->tf.y_std; a->y_mean = ctx->tf.y_mean; a->clip_hi = ctx->tf.clip_hi;
+    a->seed = seed;
+    for (int k = 0; k < GPRY_MAX_DIM; k++) {
+        a->lo[k] = k < ctx->d ? lo[k] : 0.0;
+        a->hi[k] = k < ctx->d ? hi[k] : 1.0;
+        if (k < ctx->d && !(lo[k] < hi[k]))
+            return gpry_fail(ctx, -1, "nested sampler: bounds of dimension %d are [%g, %g]", k, lo[k], hi[k]);
+    }
+    return 0;
+}
+
+struct NsTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~NsTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+static int ns_begin(gpry_ctx* ctx, NsTimer* tm) {
+    GPRY_TRY(serve_stop(ctx));          // the resident predict kernel would share the CUs
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventCreate(&tm->e0));
+    HIP_TRY(ctx, hipEventCreate(&tm->e1));
+    HIP_TRY(ctx, hipEventRecord(tm->e0, ctx->stream));
+    return 0;
+}
+
+static int ns_end(gpry_ctx* ctx, NsTimer* tm, double* device_ms) {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(tm->e1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, tm->e0, tm->e1));
+    if (device_ms) *device_ms = ms;
+    return 0;
+}
+
+extern "C" {
+
+int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t seed, int64_t n, double* X_out,
+                  double* y_out, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_prior: ctx is NULL");
+    if (!lo || !hi || !X_out || !y_out) return gpry_fail(ctx, -1, "gpry_ns_prior: NULL argument");
+    if (n < 0 || n > 0x7fffffffll) return gpry_fail(ctx, -1, "gpry_ns_prior: n = %lld", (long long)n);
+    GPRY_TRY(require_model(ctx, true));
+    NsArgs a; KernParams kp; AffParams ap;
+    GPRY_TRY(ns_args(ctx, lo, hi, seed, &a, &kp, &ap));
+    NsTimer tm;
+    GPRY_TRY(ns_begin(ctx, &tm));
+    if (n > 0) {
+        const int64_t xb = round_up(sizeof(double) * n * ctx->d, 256);
+        GPRY_TRY(ensure_pinned(ctx, xb + (int64_t)sizeof(double) * n));
+        char* hd = (char*)ctx->hpin_dev;
+        double* dX = (double*)hd;
+        double* dy = (double*)(hd + xb);
+#define NP(DP, KID) hipLaunchKernelGGL((ns_prior_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX, dy)
+#define NP_4(KID) NP(4, KID)
+#define NP_8(KID) NP(8, KID)
+#define NP_16(KID) NP(16, KID)
+#define NP_32(KID) NP(32, KID)
+        if (ctx->d <= 4) { DISPATCH_KID(ctx->kernel_id, NP_4) }
+        else if (ctx->d <= 8) { DISPATCH_KID(ctx->kernel_id, NP_8) }
+        else if (ctx->d <= 16) { DISPATCH_KID(ctx->kernel_id, NP_16) }
+        else { DISPATCH_KID(ctx->kernel_id, NP_32) }
+#undef NP_4
+#undef NP_8
+#undef NP_16
+#undef NP_32
+#undef NP
+    }
+    GPRY_TRY(ns_end(ctx, &tm, device_ms));
+    if (n > 0) {
+        const int64_t xb = round_up(sizeof(double) * n * ctx->d, 256);
+        memcpy(X_out, ctx->hpin, sizeof(double) * n * ctx->d);
+        memcpy(y_out, (char*)ctx->hpin + xb, sizeof(double) * n);
+    }
+    return 0;
+}
+
+int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv, const double* y_surv,
+                       int64_t nsurv, double lstar, const double* W, uint64_t seed, int64_t generation, int k,
+                       int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation: ctx is NULL");
+    if (!lo || !hi || !X_surv || !y_surv || !W || !X_new || !y_new || !ncalls)
+        return gpry_fail(ctx, -1, "gpry_ns_generation: NULL argument");
+    if (nsurv < 1 || k < 0 || num_repeats < 0 || generation < 0 || generation > 0xffffffffll)
+        return gpry_fail(ctx, -1, "gpry_ns_generation: nsurv = %lld, k = %d, num_repeats = %d, generation = %lld",
+                         (long long)nsurv, k, num_repeats, (long long)generation);
+    GPRY_TRY(require_model(ctx, true));
+    NsArgs a; KernParams kp; AffParams ap;
+    GPRY_TRY(ns_args(ctx, lo, hi, seed, &a, &kp, &ap));
+    const int d = ctx->d;
+    // one pinned, mapped buffer: [survivors | their y | W | new points | their y | counts]
+    const int64_t bx = round_up(sizeof(double) * nsurv * d, 256), by = round_up(sizeof(double) * nsurv, 256),
+                  bw = round_up(sizeof(double) * d * d, 256), bn = round_up(sizeof(double) * (int64_t)k * d, 256),
+                  bny = round_up(sizeof(double) * (int64_t)k, 256), bc = round_up(sizeof(int64_t) * (int64_t)k, 256);
+    GPRY_TRY(ensure_pinned(ctx, bx + by + bw + bn + bny + bc));
+    char* h = (char*)ctx->hpin;
+    char* hd = (char*)ctx->hpin_dev;
+    memcpy(h, X_surv, sizeof(double) * nsurv * d);
+    memcpy(h + bx, y_surv, sizeof(double) * nsurv);
+    memcpy(h + bx + by, W, sizeof(double) * d * d);
+    const double* dXs_ = (const double*)hd;
+    const double* dys_ = (const double*)(hd + bx);
+    const double* dW = (const double*)(hd + bx + by);
+    double* dXn = (double*)(hd + bx + by + bw);
+    double* dyn = (double*)(hd + bx + by + bw + bn);
+    int64_t* dcn = (int64_t*)(hd + bx + by + bw + bn + bny);
+    NsTimer tm;
+    GPRY_TRY(ns_begin(ctx, &tm));
+    if (k > 0) {
+#define NC(DP, KID) hipLaunchKernelGGL((ns_chain_kernel<DP, KID>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, ap, \
+                                       dXs_, dys_, nsurv, dW, lstar, (unsigned)generation, num_repeats, dXn, dyn, dcn)
+#define NC_4(KID) NC(4, KID)
+#define NC_8(KID) NC(8, KID)
+#define NC_16(KID) NC(16, KID)
+#define NC_32(KID) NC(32, KID)
+        if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NC_4) }
+        else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NC_8) }
+        else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NC_16) }
+        else { DISPATCH_KID(ctx->kernel_id, NC_32) }
+#undef NC_4
+#undef NC_8
+#undef NC_16
+#undef NC_32
+#undef NC
+    }
+    GPRY_TRY(ns_end(ctx, &tm, device_ms));
+    memcpy(X_new, h + bx + by + bw, sizeof(double) * (int64_t)k * d);
+    memcpy(y_new, h + bx + by + bw + bn, sizeof(double) * (int64_t)k);
+    memcpy(ncalls, h + bx + by + bw + bn + bny, sizeof(int64_t) * (int64_t)k);
+    return 0;
+}
+
+}  // extern "C"

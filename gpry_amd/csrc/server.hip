@@ -58,50 +58,9 @@ struct SrvArgs {
     int64_t rows_per_split;
     int cached;                // this launch keeps its slices of Xs / alpha_ in LDS
     // gates (gpry_set_gates) evaluated per point by the leader when the context applies them to gpry_predict
-    const double* gate_sv; const double* gate_coef; const double* gate_trust;
-    int64_t gate_nsv; double gate_gamma, gate_intercept;
-    int gate_positive_finite, gate_has_trust, gates;
+    GateParams gate;
+    int gates;
 };
-
-// GPRY_MASK_* bits of one point (raw coordinates x in LDS): the trust box on the raw coordinates, the SVM decision
-// function sum_r coef_r exp(-gamma |x_ - sv_r|^2) + intercept on the transformed ones -- the per-pair arithmetic of
-// gates_kernel (kernel_build.hip), the support vectors dealt out over the 256 threads and their terms added by the
-// fixed LDS tree.  Valid in every thread.
-__device__ __forceinline__ unsigned srv_gate_bits(const double* x, const SrvArgs& a, const KernParams& kp, const AffParams& ap,
-                                                  double* red) {
-    const int t = threadIdx.x;
-    unsigned bits = 0;
-    if (a.gate_has_trust) {
-        for (int k = 0; k < kp.d; k++) {
-            const double v = x[k];
-            if (!(v >= a.gate_trust[2 * k] && v <= a.gate_trust[2 * k + 1])) bits |= GPRY_MASK_OUTSIDE_TRUST;
-        }
-    }
-    if (a.gate_nsv > 0) {
-        double part = 0.0;
-        for (int64_t r = t; r < a.gate_nsv; r += 256) {
-            double r2 = 0.0;
-            for (int k = 0; k < kp.d; k++) {
-                double v = x[k];
-                if (kp.has_aff) v = (v - ap.lo[k]) / ap.span[k];
-                const double df = v - a.gate_sv[r * kp.d + k];
-                r2 = fma(df, df, r2);
-            }
-            part = fma(a.gate_coef[r], fast_exp_neg(a.gate_gamma * r2), part);
-        }
-        red[t] = part;
-        __syncthreads();
-        for (int s2 = 128; s2 >= 1; s2 >>= 1) {
-            if (t < s2) red[t] += red[t + s2];
-            __syncthreads();
-        }
-        const double dec = red[0] + a.gate_intercept;
-        __syncthreads();
-        const bool finite = a.gate_positive_finite ? dec > 0.0 : !(dec > 0.0);
-        if (!finite) bits |= GPRY_MASK_CLASSIFIED_INF;
-    }
-    return bits;
-}
 
 #define SRV_CACHE_ROWS 1024
 #define SRV_CACHE_DOUBLES 16384           // 128 KB of the 160 KB of a CU
@@ -223,7 +182,7 @@ __global__ __launch_bounds__(256) void predict_server_kernel(SrvArgs a, KernPara
                 : mean_slice<DP, KID>(s_x + m * kp.d, a.Xs, a.alpha_, row_lo, a.rows_per_split, kp, ap, xs_c, red);   // (xs_c: free, serves as the 4096-row r2 buffer)
             if (t == 0) srv_store_sys(a.res + g * SRV_MAXM + m, (unsigned long long)__double_as_longlong(v), seq);
             if (a.gates && g == 0) {
-                const unsigned bits = srv_gate_bits(s_x + m * kp.d, a, kp, ap, red);
+                const unsigned bits = point_gate_bits(s_x + m * kp.d, a.gate, kp, ap, red);
                 if (t == 0) srv_store_sys(a.res + SRV_MAX_SLICES * SRV_MAXM + m, (unsigned long long)bits, seq);
             }
         }
@@ -321,9 +280,7 @@ static int srv_launch(gpry_ctx* ctx, SrvHost* s) {
     a.cached = a.rows_per_split <= SRV_CACHE_ROWS && a.rows_per_split * ctx->dpad <= SRV_CACHE_DOUBLES;
     a.gates = ctx->gates_on && ctx->opt_predict_gates;
     s->gates = a.gates;
-    a.gate_sv = ctx->gate_sv; a.gate_coef = ctx->gate_coef; a.gate_trust = ctx->gate_trust;
-    a.gate_nsv = ctx->gate_nsv; a.gate_gamma = ctx->gate_gamma; a.gate_intercept = ctx->gate_intercept;
-    a.gate_positive_finite = ctx->gate_positive_finite; a.gate_has_trust = ctx->gate_has_trust;
+    a.gate = make_gp(ctx);
 #define SV2(DP, KID) hipLaunchKernelGGL((predict_server_kernel<DP, KID>), dim3((unsigned)nsplit), dim3(256), 0, s->stream, a, kp, ap)
 #define SV4(KID) { if (ctx->d <= 4) SV2(4, KID); else if (ctx->d <= 8) SV2(8, KID); \
                    else if (ctx->d <= 16) SV2(16, KID); else SV2(32, KID); }

@@ -305,13 +305,19 @@ class NORA(GenericGPAcquisition):
     ``exact_prune`` (default True): a sweep whose arrays stay on the device contracts only the candidates whose
     acquisition bound (the value at the prior sigma) can reach the shortlist; proposals, shortlist records and every
     array fetched later are bit for bit those of the full sweep.  ``acq.stats["prune"]`` holds the statistics.
+
+    ``sampler="nested"``: the package's own nested sampler of the surrogate's mean, on the device (``gpry_amd/nested.py``),
+    with the settings of ``update_NS_precision``; ``nested_batch``: its chains per generation (default nlive / 2).  The
+    pool's y is ``gpr.predict`` bit for bit and goes to the sweep as given; ``acq.stats["sampler_info"]`` holds logZ, its
+    error, the evaluations, the generations and the device time.
     """
 
     def __init__(self, bounds, preprocessing_X=None, verbose=1, acq_func="LogExp", sampler=None,
                  mc_every="1d", nlive_per_training=3, nlive_max="25d", nlive_per_dim_max=None,
                  num_repeats="5d", num_repeats_per_dim=None, precision_criterion_target=0.01,
                  nprior_per_nlive=10, max_ncalls=None, tmpdir=None, comm=None,
-                 shortlist_size=None, gather_y="auto", devices=None, exact_prune=True):
+                 shortlist_size=None, gather_y="auto", devices=None, exact_prune=True,
+                 nested_batch=None):
         super().__init__(bounds=np.asarray(bounds), preprocessing_X=preprocessing_X,
                          verbose=verbose, acq_func=acq_func)
         self.log_header = f"[ACQUISITION : {self.__class__.__name__}] "
@@ -346,6 +352,8 @@ class NORA(GenericGPAcquisition):
         # lazy sweeps contract only the candidates whose acquisition bound can reach the shortlist (option "sweep_prune" of
         # the library); the shortlist, its bound rule and every array fetched later are those of the full sweep
         self.exact_prune = bool(exact_prune)
+        # chains per generation of sampler="nested" (None: gpry_amd.nested.default_batch)
+        self.nested_batch = nested_batch
         self._X_already_proposed = np.empty((0, self.n_d))
         self.stats = {}
 
@@ -358,10 +366,11 @@ class NORA(GenericGPAcquisition):
         s = self.sampler
         if s is None:
             s = "uniform"   # no external sampler ships with this package
-        if s.lower() not in ("uniform",):
+        if s.lower() not in ("uniform", "nested"):
             raise NestedSamplerNotInstalledError(
                 f"Nested sampler '{s}' is an external package outside this hot-path package; "
-                "pass sampler='uniform' or override do_MC_sample to inject the candidate pool.")
+                "pass sampler='nested' (the package's own, on the device), sampler='uniform' or override do_MC_sample "
+                "to inject the candidate pool.")
         self.sampler = s
 
     def update_NS_precision(self, gpr):
@@ -378,8 +387,41 @@ class NORA(GenericGPAcquisition):
         """Returns ``(X, y, sigma_y, weights)``; any of the last three may be None."""
         sampler = sampler or self.sampler
         if sampler.lower() == "uniform":
+            self.stats.pop("sampler_info", None)
             return self._do_MC_sample_uniform(gpr, bounds=bounds, rng=rng)
+        if sampler.lower() == "nested":
+            return self._do_MC_sample_nested(gpr, bounds=bounds, rng=rng)
         raise ValueError(f"Sampler '{sampler}' not known.")
+
+    def _do_MC_sample_nested(self, gpr, bounds=None, rng=None):
+        """Nested sampling of the surrogate's mean on the device (gpry_amd/nested.py), in place of the reference's
+        PolyChord / UltraNest runs (gp_acquisition.py:760-856) with the settings of ``update_NS_precision``.  Returns
+        ``(X, y, None, w)``: y is ``gpr.predict`` of every row, bit for bit, and goes to the sweep as given.  The seed is
+        ``rng.integers(2**31 - 1)`` (fresh entropy without an rng); with several ranks, rank 0's, and every rank runs the
+        same sampler on its own context -- the same bits everywhere."""
+        from gpry_amd.nested import run_nested
+        b = np.asarray(self.bounds_ if bounds is None else bounds, dtype=float)
+        if rng is None:
+            rng = np.random.default_rng()
+        seed = int(rng.integers(2**31 - 1))
+        if self.comm is not None and getattr(self.comm, "world", 1) > 1:
+            seed = int(self.comm.allgather(np.array([seed], dtype=np.int64))[0][0])
+        gpr._ensure_factor()
+        gpr._push_affine()
+        # classifier / trust box on the device, as gpr.predict applies them to one point
+        if not gpr._push_gates():
+            raise ValueError("sampler='nested' evaluates the classifier on the device, and this classifier has no device "
+                             "form: use sampler='uniform', or override do_MC_sample to supply the pool")
+        prec = self.update_NS_precision(gpr)
+        res = run_nested(gpr.device, b, seed, prec["nlive"], prec["num_repeats"],
+                         precision_criterion=prec["precision_criterion"], nprior=prec["nprior"],
+                         max_ncalls=prec["max_ncalls"], batch=self.nested_batch,
+                         minus_inf_value=gpr.minus_inf_value)
+        gpr.n_eval += res.ncalls
+        self.stats["sampler_info"] = {"logZ": res.logZ, "logZ_err": res.logZ_err, "ncalls": res.ncalls,
+                                      "generations": res.ngen, "device_s": res.device_s, "wall_s": res.wall_s,
+                                      "seed": seed, "nlive": prec["nlive"], "rows": len(res.y)}
+        return res.X, res.y, None, res.w
 
     def _do_MC_sample_uniform(self, gpr, bounds=None, rng=None):
         """1000 d points drawn one at a time, as gp_acquisition.py:750-758 does."""
