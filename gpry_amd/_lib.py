@@ -517,7 +517,8 @@ class Device:
                                                _ptr(out["acq"])), "gpry_sweep_fetch")
         return out
 
-    PRUNE_INFO = ("pruned", "M", "K_prime", "rounds", "contracted", "completed", "K", "survivors")
+    PRUNE_INFO = ("pruned", "M", "K_prime", "rounds", "contracted", "completed", "K", "survivors", "y_bound", "live_blocks",
+                  "blocks")
 
     def sweep_prune_info(self):
         """Statistics of the last pruned sweep (option ``sweep_prune``, ``gpry_sweep_prune_info``)."""

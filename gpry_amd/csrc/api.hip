@@ -707,6 +707,40 @@ __global__ void sweep_mean_kernel(const double* __restrict__ mean_part, int nt_m
     sig_all[m] = PRUNED_SIGMA;
 }
 
+// Stage A of a pruned sweep with the bound pass (option "sweep_mean_bound"; run_sweep explains the slack D1 + g3 * S): an
+// upper bound of y instead of y, the same finish behind it.  Each candidate's bound partials are summed as the exact partials
+// are (same order), the slack is added and the sum rounded up; y = mu * y_std + y_mean, the clip, and every step behind them
+// to the acquisition are monotone in mu under round-to-nearest (y_std > 0, zeta >= 0), masks give -inf as in
+// sweep_mean_kernel, and NaN comes out exactly where the exact y is NaN (a NaN term is never skipped).  y_all holds the bound
+// until the candidate is contracted (sweep_scatter_finish_kernel with mean partials writes the exact y).
+__global__ void sweep_mean_bound_kernel(const double* __restrict__ mean_part, const double* __restrict__ sabs_part, int nt_mean,
+                                        int64_t ldp, int64_t m0, int64_t mc, const uint8_t* __restrict__ mask,
+                                        double* __restrict__ y_all, double* __restrict__ sig_all, double* __restrict__ acq_all,
+                                        double* __restrict__ ub, FinishParams fp, double D1, double g3) {
+    int64_t ml = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ml >= mc) return;
+    int64_t m = m0 + ml;
+    double mu_ = 0.0, sa = 0.0;
+#pragma unroll 8
+    for (int t = 0; t < nt_mean; t++) mu_ += mean_part[(int64_t)t * ldp + ml];
+#pragma unroll 8
+    for (int t = 0; t < nt_mean; t++) sa += sabs_part[(int64_t)t * ldp + ml];
+    mu_ = nextafter(mu_ + (D1 + g3 * sa), INFINITY);
+    double y = mu_ * fp.y_std + fp.y_mean;
+    y = fmin(y, fp.clip_hi);
+    unsigned mk = mask ? mask[m] : 0u;
+    if (mk) y = -INFINITY;
+    y_all[m] = y;
+    double var = fp.C - 0.0;
+    if (var < 0.0) var = 0.0;
+    double sd = sqrt(var) * fp.y_std;
+    if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
+    const double a = logexp_value(y, sd, fp.zeta, fp.baseline, fp.sigma_n);
+    ub[m] = a;
+    acq_all[m] = a;
+    sig_all[m] = PRUNED_SIGMA;
+}
+
 // Stage A of a pruned sweep whose y the caller supplied (gpry_sweep_logexp_given): it replaces the mean pass -- no panel, no
 // cross build, no candidate centring.  ub = acq_all = the acquisition at the caller's y and the prior sigma (0 on classifier-
 // inf rows, as the finish gives them), sig_all = PRUNED_SIGMA.  The bound is exact bit for bit by the argument at
@@ -731,13 +765,24 @@ __global__ void sweep_given_bound_kernel(int64_t m0, int64_t mc, const uint8_t* 
 }
 
 // The finish of a compact batch (pool indices gidx[0..n)): sigma and acq as sweep_finish_kernel computes them from the same
-// per-tile partials, summed in the same order, with the y stage A stored
+// per-tile partials, summed in the same order, with the y stage A stored -- or, after the bound pass (mean_part != NULL), y
+// from the batch's own mean partials as sweep_finish_kernel computes it (stored over the bound)
 __global__ void sweep_scatter_finish_kernel(const double* __restrict__ ss_part, int nt, int64_t ldp, const int64_t* __restrict__ gidx,
-                                            int64_t n, const uint8_t* __restrict__ mask, const double* __restrict__ y_all,
-                                            double* __restrict__ sig_all, double* __restrict__ acq_all, FinishParams fp) {
+                                            int64_t n, const uint8_t* __restrict__ mask, double* __restrict__ y_all,
+                                            double* __restrict__ sig_all, double* __restrict__ acq_all, FinishParams fp,
+                                            const double* __restrict__ mean_part) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t m = gidx[i];
+    if (mean_part) {
+        double mu_ = 0.0;
+#pragma unroll 8
+        for (int t = 0; t < nt; t++) mu_ += mean_part[(int64_t)t * ldp + i];
+        double y = mu_ * fp.y_std + fp.y_mean;
+        y = fmin(y, fp.clip_hi);
+        if (mask && mask[m]) y = -INFINITY;
+        y_all[m] = y;
+    }
     double ss = 0.0;
 #pragma unroll 8
     for (int t = 0; t < nt; t++) ss += ss_part[(int64_t)t * ldp + i];
@@ -795,6 +840,15 @@ __global__ __launch_bounds__(1024) void splitk_sumsq_kernel(const double* __rest
         for (int k = 0; k < 16; k++) s += red[k][col];
         ss_part[(int64_t)ti * ldp + c] = s;
     }
+}
+
+// the correlation at the scaled argument u = corr_scale * r^2 (kern_math.h: corr_scaled_fast), from libm
+static double corr_scaled_host(int kid, double u) {
+    if (kid == GPRY_RBF) return exp(-u);
+    const double t = sqrt(u);
+    if (kid == GPRY_MATERN12) return exp(-t);
+    if (kid == GPRY_MATERN32) return (1.0 + t) * exp(-t);
+    return (1.0 + t + t * t / 3.0) * exp(-t);
 }
 
 static int ensure_sweep_buffers(gpry_ctx* ctx, int64_t M) {
@@ -931,6 +985,53 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
     const bool no_panel = mean_only && y_given;
     if ((fast_panel || hybrid_panel) && !no_panel) GPRY_TRY(launch_cross_prepare(ctx));
     if (mean_only) ctx->prune.form = ctx->panel_form;
+    // THE BOUND PASS (option "sweep_mean_bound"; stage A of a pruned sweep in the hybrid form, cross_build_mfma_kernel<.., BND>).
+    // The hybrid form is taken by models with length scales far below the extent of their data, whose candidates have next to
+    // no training row nearby: the pass skips every block of 16 rows x 32 candidates whose expanded u all lie in [ubnd, uhi]
+    // and sums the terms alpha_j v_j of the other blocks, each one the exact pass's to the bit (same code).  y is bounded by
+    //   * D = 2 C ||alpha_||_1 k(ubnd) >= the skipped terms in all: ubnd >= the hybrid form's cut, so the exact pass takes
+    //     those pairs' u as it is, and its v = C corr_scaled_fast(u) is within a few ulps of C k(u) <= C k(ubnd) up to
+    //     t = sqrt(u) = 763 (Matern) and 0 beyond (kern_math.h: the exponential underflows through ldexp; uhi keeps the
+    //     argument reduction exact, t <= 1e6).  ubnd is chosen for D = 1e-13 of the normalised targets.
+    //   * rounding: the exact y and the bound's partial sum are recursive sums of depth <= n = 128 rows + Np / 128 partials
+    //     + 4 (the shuffles), so each is within gamma = n eps of its exact value times the sum of |terms|.  With S the
+    //     (computed) sum of |alpha_j v_j| over the live terms:  y <= y_part + (1 + gamma) D + 2 gamma S (1 + gamma)
+    //     <= y_part + (1 + 2 gamma) D + 3 gamma S -- the slack, added and rounded up (sweep_mean_bound_kernel).
+    // A bound only moves the candidate up the ranking (more survivors); it never changes a record.  Not taken for a model
+    // whose weights or scales are not finite, y_std <= 0 or zeta < 0 (the acquisition would not be monotone in y).
+    const bool ybound_ok = mean_only && !y_given && hybrid_panel && ctx->opt_sweep_mean_bound;
+    bool ybound = false;
+    double ubnd = 0.0, bD1 = 0.0, bg3 = 0.0;
+    const double uhi = ctx->kernel_id == GPRY_RBF ? 1e6 : 1e12;
+    if (ybound_ok) {
+        const double C = exp(ctx->theta[0]), a1 = ctx->alpha_l1;
+        const double sc = ctx->kernel_id == GPRY_RBF ? 0.5 : ctx->kernel_id == GPRY_MATERN32 ? 3.0 : 5.0;    // corr_scale
+        const double scale = 2.0 * C * a1, target = 1e-13;
+        if (std::isfinite(C) && C > 0.0 && std::isfinite(a1) && fp.y_std > 0.0 && std::isfinite(fp.y_std) && zeta >= 0.0 &&
+            scale * corr_scaled_host(ctx->kernel_id, uhi) <= target) {
+            double lo = 100.0 * sc, hi = uhi;
+            if (scale * corr_scaled_host(ctx->kernel_id, lo) <= target) hi = lo;
+            for (int it = 0; it < 200 && hi > lo * (1.0 + 1e-9); it++) {
+                const double mid = sqrt(lo * hi);
+                if (scale * corr_scaled_host(ctx->kernel_id, mid) <= target) hi = mid; else lo = mid;
+            }
+            ubnd = hi;
+            const double D = scale * corr_scaled_host(ctx->kernel_id, ubnd);
+            const double gamma = (double)(128 + nt + 4) * 2.220446049250313e-16;
+            bD1 = (1.0 + 2.0 * gamma) * D;
+            bg3 = 3.0 * gamma;
+            ybound = true;
+        }
+    }
+    unsigned long long* live_cnt = nullptr;
+    if (mean_only) { ctx->prune.ybound = ybound ? 1 : 0; ctx->prune.live_blocks = 0; ctx->prune.blocks = 0; }
+    if (ybound) {
+        if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, 64));
+        live_cnt = ctx->dsel + 8;
+        HIP_TRY(ctx, hipMemsetAsync(live_cnt, 0, 8, ctx->stream));
+        if (getenv("GPRY_HIP_DEBUG_PANEL"))
+            fprintf(stderr, "gpry: bound pass: u in [%.6g, %.3g] skipped, D %.3g, gamma %.3g\n", ubnd, uhi, bD1, bg3 / 3.0);
+    }
     // A fresh pool (gpry_sweep_logexp with a host array, option "sweep_upload"): the rows of chunk c go up on stream2 while
     // the main stream still works on chunk c - 1 -- 4.2 MB against 7.7 ms of kernels at N = 4096 -- and the main stream
     // waits for nothing but its own chunk (one event per chunk, never re-recorded within a call).  From pageable memory
@@ -971,6 +1072,10 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
         StageScope s(ctx, mean_only ? "sweep_mean" : "cross_build");
         if (mean_only) Kst = nullptr;       // (the kernels store the mean partials only)
         if (y_given) mean_part = nullptr;   // (... or the panel only)
+        if (ybound) {                       // (bound partials, the sums of |terms| in the place of the sigma partials)
+            ctx->prune.blocks += (int64_t)((mcp + 255) / 256) * 4 * nt * 16;
+            return launch_cross_mean_bound(ctx, ctx->dXc, m0, mcp, mean_part, mean_part + (int64_t)nt_mean * chunk, ubnd, uhi, live_cnt);
+        }
         if (small_build) return launch_cross_build_small(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1);
         if (fast_panel || hybrid_panel) return launch_cross_build_mfma(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1, hybrid_panel ? 1 : 0);
         return launch_cross_build(ctx, ctx->dXc, m0, mcp, mcp, Kst, mean_part, 1);
@@ -1017,6 +1122,14 @@ static int run_sweep(gpry_ctx* ctx, int64_t M, bool have_mask, bool want_std, bo
             StageScope s(ctx, "sweep_given_bound");
             hipLaunchKernelGGL(sweep_given_bound_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream,
                                m0, mc, have_mask ? ctx->dmask : nullptr, ctx->dy_all, ctx->dsig_all, ctx->dacq_all, ctx->dub, fp);
+            HIP_TRY(ctx, hipGetLastError());
+            continue;
+        }
+        if (ybound) {
+            StageScope s(ctx, "sweep_mean");
+            hipLaunchKernelGGL(sweep_mean_bound_kernel, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream,
+                               mean_part, ss_part, nt_mean, mcp, m0, mc, have_mask ? ctx->dmask : nullptr,
+                               ctx->dy_all, ctx->dsig_all, ctx->dacq_all, ctx->dub, fp, bD1, bg3);
             HIP_TRY(ctx, hipGetLastError());
             continue;
         }
@@ -1497,7 +1610,8 @@ int gpry_sweep_fetch(gpry_ctx* ctx, int64_t M, double* y_all, double* sigma_all,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (M <= 0 || M != ctx->sw_M) return gpry_fail(ctx, -1, "sweep_fetch: the resident sweep has %lld candidates, not %lld",
                                                   (long long)ctx->sw_M, (long long)M);
-    if (ctx->sw_pruned) GPRY_TRY(prune_complete(ctx));      // the arrays of the full sweep, bit for bit
+    // (test hook "panel_debug" & 256: the arrays as they stand -- bounds where nothing was contracted -- and no completion)
+    if (ctx->sw_pruned && !(ctx->opt_panel_debug & 256)) GPRY_TRY(prune_complete(ctx));      // the arrays of the full sweep, bit for bit
     if (y_all) HIP_TRY(ctx, hipMemcpyAsync(y_all, ctx->dy_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (sigma_all) HIP_TRY(ctx, hipMemcpyAsync(sigma_all, ctx->dsig_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (acq_all) HIP_TRY(ctx, hipMemcpyAsync(acq_all, ctx->dacq_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
@@ -1585,8 +1699,9 @@ static int sweep_impl(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
     // picks up every entry of V in alpha_[0], and a NaN panel entry enters the mean partial through fma(alpha_j, k, .), NaN
     // for any alpha_j.  The rest of the finish keeps var in [0, C]: the acquisition is finite or -inf.)
     hipLaunchKernelGGL(count_nan_kernel, dim3(1024), dim3(256), 0, ctx->stream, prune ? ctx->dub : ctx->dacq_all, M, ctx->dsel);
-    unsigned long long nn = 0;
+    unsigned long long nn = 0, live = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&nn, ctx->dsel, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (prune && ctx->prune.ybound) HIP_TRY(ctx, hipMemcpyAsync(&live, ctx->dsel + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (y_all) HIP_TRY(ctx, hipMemcpyAsync(y_all, ctx->dy_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (sigma_all) HIP_TRY(ctx, hipMemcpyAsync(sigma_all, ctx->dsig_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (acq_all) HIP_TRY(ctx, hipMemcpyAsync(acq_all, ctx->dacq_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
@@ -1594,9 +1709,13 @@ static int sweep_impl(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
     upload_scope.done = true;
     if (n_nan) *n_nan = (int64_t)nn;
     if (prune) {
-        const int form = ctx->prune.form;
+        const int form = ctx->prune.form, ybound = ctx->prune.ybound;
+        const int64_t blocks = ctx->prune.blocks;
         ctx->prune = gpry_ctx::PruneState();
         ctx->prune.form = form;
+        ctx->prune.ybound = ybound;
+        ctx->prune.live_blocks = ybound ? (int64_t)live : 0;
+        ctx->prune.blocks = ybound ? blocks : 0;
         ctx->prune.have_mask = have_mask ? 1 : 0;
         ctx->prune.zeta = zeta; ctx->prune.baseline = baseline; ctx->prune.sigma_n = sigma_n;
         ctx->prune.C = exp(ctx->theta[0]); ctx->prune.y_mean = ctx->tf.y_mean; ctx->prune.y_std = ctx->tf.y_std;
@@ -2011,7 +2130,10 @@ static int prune_eval(gpry_ctx* ctx, int64_t n) {
         GPRY_TRY(dev_alloc(ctx, &ctx->dKst, Np * np_max));
         ctx->kst_cap = Np * np_max;
     }
-    GPRY_TRY(ensure_part(ctx, (int64_t)nt * np_max));
+    // (after the bound pass the batch's mean partials as well, behind its sigma partials: y of the full sweep, bit for bit --
+    // the panel kernels give a candidate's mean partials from its own coordinates alone)
+    const bool want_y = ctx->prune.ybound != 0;
+    GPRY_TRY(ensure_part(ctx, (int64_t)nt * np_max * (want_y ? 2 : 1)));
     // (in doubles, not rows: a later model may have more dimensions than the one the buffer was made for)
     const int64_t xg_need = round_up(np_max, 256) * ctx->d;
     if (xg_need > ctx->xg_cap) {
@@ -2033,8 +2155,9 @@ static int prune_eval(gpry_ctx* ctx, int64_t n) {
                                ctx->dXc, ctx->d, gidx, nc, npad, ctx->dXg);
             HIP_TRY(ctx, hipGetLastError());
             // (the builders read rows below min(sw_M, round_up(ncp, 256)) = npad at most: dXg holds npad rows)
-            if (form == 1 || form == 4) GPRY_TRY(launch_cross_build_mfma(ctx, ctx->dXg, 0, ncp, ncp, ctx->dKst, nullptr, 1, form == 4 ? 1 : 0));
-            else GPRY_TRY(launch_cross_build(ctx, ctx->dXg, 0, ncp, ncp, ctx->dKst, nullptr, 1));
+            double* mean_part = want_y ? ctx->dpart + (int64_t)nt * ncp : nullptr;
+            if (form == 1 || form == 4) GPRY_TRY(launch_cross_build_mfma(ctx, ctx->dXg, 0, ncp, ncp, ctx->dKst, mean_part, 1, form == 4 ? 1 : 0));
+            else GPRY_TRY(launch_cross_build(ctx, ctx->dXg, 0, ncp, ncp, ctx->dKst, mean_part, 1));
         }
         StageScope s(ctx, "sweep_prune_gemm");
         GemmArgs g = {};
@@ -2045,7 +2168,7 @@ static int prune_eval(gpry_ctx* ctx, int64_t n) {
         else GPRY_TRY(gemm_f64_launch(ctx, g, false, false, EPI_SUMSQ));
         hipLaunchKernelGGL(sweep_scatter_finish_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream,
                            ctx->dpart, nt, ncp, gidx, nc, ctx->prune.have_mask ? ctx->dmask : nullptr, ctx->dy_all,
-                           ctx->dsig_all, ctx->dacq_all, fp);
+                           ctx->dsig_all, ctx->dacq_all, fp, want_y ? ctx->dpart + (int64_t)nt * ncp : nullptr);
         HIP_TRY(ctx, hipGetLastError());
     }
     return 0;
@@ -2186,6 +2309,9 @@ extern "C" int gpry_sweep_prune_info(gpry_ctx* ctx, int64_t* info, double* dinfo
     info[5] = ctx->prune.completed;
     info[6] = ctx->prune.last_K;
     info[7] = ctx->prune.survivors;
+    info[8] = ctx->prune.ybound;
+    info[9] = ctx->prune.live_blocks;
+    info[10] = ctx->prune.blocks;
     if (dinfo) {
         dinfo[0] = ctx->prune.survivors >= 0 ? ctx->prune.tau : NAN;
         const char* names[] = {"sweep_mean", "sweep_prune_select", "sweep_compact", "sweep_prune_gemm"};

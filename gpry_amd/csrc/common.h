@@ -182,6 +182,9 @@ struct gpry_ctx {
     // pruned sweep (option "sweep_prune", api.hip): gpry_sweep_logexp with no arrays wanted leaves y and a per-candidate upper
     // bound of the acquisition; gpry_sweep_topk contracts only the candidates whose bound can reach the shortlist
     int opt_sweep_prune = 0;
+    // 1 (default): in the hybrid panel form, stage A of a pruned sweep bounds y instead of computing it (the bound pass,
+    // api.hip: run_sweep); exact y only for the candidates that are contracted
+    int opt_sweep_mean_bound = 1;
     int sw_pruned = 0;                 // 1: the resident sweep is pruned (acq_all holds exact values or bounds, see api.hip)
     struct PruneState {
         int have_mask = 0;
@@ -194,6 +197,8 @@ struct gpry_ctx {
         int tau_done = 0;              // the survivor count of a threshold has been made (prune_survivors)
         double tau = 0.0;              // that threshold, and the candidates whose bound was not below it
         int64_t survivors = -1;
+        int ybound = 0;                // stage A bounded y (the bound pass): every contraction computes y as well
+        int64_t live_blocks = 0, blocks = 0;    // blocks of 16 training rows x 32 candidates the bound pass evaluated / saw
     } prune;
     // the prediction state the pruned sweep was made with, copied at its end (api.hip: prune_snapshot): a later contraction
     // round or completion evaluates THAT model, whatever gpry_set_train / set_theta / factorize / append_rows did meanwhile
@@ -376,6 +381,8 @@ int launch_cross_build(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc,
 int launch_cross_prepare(gpry_ctx* ctx);               // centred scaled training rows for ...
 int launch_cross_build_mfma(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, int64_t ldk, double* Kst, double* mean_part,
                             int raw_affine, int hybrid = 0);           // ... the panel with MFMA distances (sweep, large predict batches); hybrid: near pairs from the coordinates
+int launch_cross_mean_bound(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, double* mean_part, double* sabs_part,
+                            double ubnd, double uhi, unsigned long long* live_cnt);     // the bound pass of a pruned sweep
 int launch_cross_build_small(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, int64_t ldk,
                              double* Kst, double* mean_part, int raw_affine);     // 4 x (Np/128) mean partials
 int launch_predict_mean_small(gpry_ctx* ctx, const double* Xc, int64_t M, int nsplit, double* part_out);

@@ -300,7 +300,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("lml_schedule", opt_lml_schedule, 0, 1, (void)0),
     OPT_INT("lml_streams", opt_lml_streams, 1, 8, (void)0),
     OPT_INT("chol_tp_segments", opt_chol_tp_segments, 0, 1, c->lml_cache = false),
-    OPT_INT("panel_debug", opt_panel_debug, 0, 255, c->lml_cache = false),
+    OPT_INT("panel_debug", opt_panel_debug, 0, 511, c->lml_cache = false),
     OPT_INT("tp_left", opt_tp_left, 0, 1, (void)0),
     OPT_INT("tp_block", opt_tp_block, 128, BIG, c->opt_tp_block = round_up(c->opt_tp_block, 128); overlap_plan_free(c)),
     OPT_INT("tp_tail", opt_tp_tail, 128, BIG, c->opt_tp_tail = round_up(c->opt_tp_tail, 128); overlap_plan_free(c)),
@@ -309,6 +309,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("sweep_upload", opt_sweep_upload, 0, 1, (void)0),
     OPT_INT("sweep_overlap", opt_sweep_overlap, 0, 1, (void)0),
     OPT_INT("sweep_prune", opt_sweep_prune, 0, 1, (void)0),
+    OPT_INT("sweep_mean_bound", opt_sweep_mean_bound, 0, 1, (void)0),
     OPT_INT("chol_stacked", opt_chol_stacked, 0, BIG, c->lml_cache = false),
     OPT_INT("chol_stacked_dense", opt_chol_stacked_dense, 0, 1, c->lml_cache = false),
     OPT_INT("predict_gates", opt_predict_gates, 0, 1, (void)0),

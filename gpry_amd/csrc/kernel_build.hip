@@ -353,11 +353,19 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
 // branch is taken by the waves that hold a candidate on or next to a training point, and the panel costs what the expanded
 // form costs.  (A model that fails it with ordinary length scales -- huge weights -- has nothing but near pairs; the caller
 // then takes cross_build_kernel.)
-template <int DP, int KID, bool HYB>
+// BND (the bound pass of a pruned sweep, option "sweep_mean_bound"; HYB only, Kst == NULL): per 16 training rows x 32
+// candidates of a wave the expanded u of all 512 pairs first, exactly as above.  A block whose every pair has u in
+// [ubnd, uhi] -- ubnd >= ucut, so the hybrid form would take none of them again from the coordinates -- adds nothing (a
+// wave-uniform branch); any other block goes through the code of the exact pass unchanged, so that each of its terms
+// alpha_j v_j is the exact pass's to the bit.  mean_part then holds the partial sums over the live terms and sabs_part the
+// sums of |alpha_j v_j| over them; live_cnt counts the live blocks.  The caller (api.hip: run_sweep) bounds what was left out.
+template <int DP, int KID, bool HYB, bool BND = false>
 __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
     const double* __restrict__ Xcs, int64_t ldm, int64_t mc,
     const double* __restrict__ Ycs, const double* __restrict__ alpha_,
-    double* __restrict__ Kst, int64_t ldk, double* __restrict__ mean_part, KernParams kp, double ucut) {
+    double* __restrict__ Kst, int64_t ldk, double* __restrict__ mean_part, KernParams kp, double ucut,
+    double ubnd = 0.0, double uhi = 0.0, double* __restrict__ sabs_part = nullptr,
+    unsigned long long* __restrict__ live_cnt = nullptr) {
     constexpr int S = DP + 2, KS = DP / 4;
     constexpr double SC = corr_scale<KID>();
     __shared__ __attribute__((aligned(16))) double Yl[128 * S];
@@ -401,6 +409,8 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
     const int64_t left = kp.N - (int64_t)jc * 128;
     const int nvalid = left >= 128 ? 128 : (left > 0 ? (int)left : 0);      // training rows of this chunk (the rest: zero padding)
     double macc[4] = {0.0, 0.0, 0.0, 0.0};
+    double sacc[4] = {0.0, 0.0, 0.0, 0.0};
+    unsigned nlive = 0;
 #pragma unroll 1
     for (int j0 = 0; j0 < 128; j0 += 16) {
         double a[KS], ynq[4], alq[4];
@@ -417,11 +427,24 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
             for (int kk = 0; kk < KS; kk++) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[2 * tp + 1][kk], acc1, 0, 0, 0);
             const int64_t mloc = mb + 32 * tp + 2 * r;      // this lane's pair of candidates (mc is a multiple of 128: both or neither)
             const bool in_chunk = mloc < mc;
+            double ue0[4], ue1[4];
+            bool live = false;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                ue0[q] = fma(-2.0 * SC, acc0[q], xn[2 * tp] + ynq[q]);
+                ue1[q] = fma(-2.0 * SC, acc1[q], xn[2 * tp + 1] + ynq[q]);
+                // (NaN and anything beyond uhi count as live: the exact pass's term is then NaN, or not known to be small)
+                if (BND) live = live || !(ue0[q] >= ubnd && ue0[q] <= uhi) || !(ue1[q] >= ubnd && ue1[q] <= uhi);
+            }
+            if (BND) {
+                if (!__any(live)) continue;
+                nlive++;
+            }
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int jj = j0 + g + 4 * q;
-                double u0 = fma(-2.0 * SC, acc0[q], xn[2 * tp] + ynq[q]);
-                double u1 = fma(-2.0 * SC, acc1[q], xn[2 * tp + 1] + ynq[q]);
+                double u0 = ue0[q];
+                double u1 = ue1[q];
                 if (HYB && (u0 < ucut || u1 < ucut)) {      // a near pair: its distance again, from the coordinates
                     double r0 = 0.0, r1 = 0.0;
 #pragma unroll 2
@@ -440,6 +463,10 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
                 if (jj >= nvalid) { v0 = 0.0; v1 = 0.0; }
                 macc[2 * tp] = fma(alq[q], v0, macc[2 * tp]);
                 macc[2 * tp + 1] = fma(alq[q], v1, macc[2 * tp + 1]);
+                if (BND) {
+                    sacc[2 * tp] = fma(fabs(alq[q]), fabs(v0), sacc[2 * tp]);
+                    sacc[2 * tp + 1] = fma(fabs(alq[q]), fabs(v1), sacc[2 * tp + 1]);
+                }
                 if (in_chunk && Kst) *reinterpret_cast<double2*>(Kst + ((int64_t)jc * 128 + jj) * ldk + mloc) = make_double2(v0, v1);
             }
         }
@@ -452,8 +479,15 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
             s += __shfl_xor(s, 32);
             const int64_t ml = mb + 32 * (tl >> 1) + 2 * r + (tl & 1);
             if (g == 0 && ml < mc) mean_part[(int64_t)jc * mc + ml] = s;
+            if (BND) {
+                double sa = sacc[tl];
+                sa += __shfl_xor(sa, 16);
+                sa += __shfl_xor(sa, 32);
+                if (g == 0 && ml < mc) sabs_part[(int64_t)jc * mc + ml] = sa;
+            }
         }
     }
+    if (BND && lane == 0 && nlive) atomicAdd(live_cnt, (unsigned long long)nlive);
 }
 // centred scaled training rows for cross_build_mfma_kernel: Ycs[i][k] = (X[i][k] - c_k) / l_k, zero rows / columns as padding
 __global__ __launch_bounds__(256) void center_train_kernel(const double* __restrict__ X, double* __restrict__ Ycs, int64_t N, int64_t Np, int d,
@@ -497,13 +531,12 @@ int launch_cross_prepare(gpry_ctx* ctx) {
     return 0;
 }
 
-// after launch_cross_prepare (same theta, same training set)
-int launch_cross_build_mfma(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, int64_t ldk, double* Kst, double* mean_part,
-                            int raw_affine, int hybrid) {
-    hipStream_t st = ctx->stream;
-    KernParams kp = make_kp(ctx);
-    kp.has_aff = raw_affine && ctx->tf.has_x_affine;
-    AffParams ap = make_ap(ctx, kp.has_aff), cen;
+// the centred scaled candidates m0 .. m0 + mc of Xc in ctx->dXcs (coordinate-major, ldm rows) for the two launchers below
+static int center_cands(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, int raw_affine, KernParams* kp, int* dsel_,
+                        int64_t* ldm_) {
+    *kp = make_kp(ctx);
+    kp->has_aff = raw_affine && ctx->tf.has_x_affine;
+    AffParams ap = make_ap(ctx, kp->has_aff), cen;
     for (int k = 0; k < GPRY_MAX_DIM; k++) { cen.ls[k] = 1.0; cen.span[k] = 1.0; cen.lo[k] = k < ctx->d ? ctx->xcenter[k] : 0.0; }
     if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
     const int dsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
@@ -514,8 +547,20 @@ int launch_cross_build_mfma(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t
         GPRY_TRY(dev_alloc(ctx, &ctx->dXcs, dsel * ldm));
         ctx->xcs_cap = dsel * ldm;
     }
-    hipLaunchKernelGGL(center_cand_kernel, dim3((unsigned)((ldm * dsel + 255) / 256)), dim3(256), 0, st, Xc, ctx->sw_M, m0, ldm, ctx->d, dsel,
-                       kp.has_aff, ap, cen, ctx->dXcs, ldm);
+    hipLaunchKernelGGL(center_cand_kernel, dim3((unsigned)((ldm * dsel + 255) / 256)), dim3(256), 0, ctx->stream, Xc, ctx->sw_M, m0, ldm,
+                       ctx->d, dsel, kp->has_aff, ap, cen, ctx->dXcs, ldm);
+    *dsel_ = dsel; *ldm_ = ldm;
+    return 0;
+}
+
+// after launch_cross_prepare (same theta, same training set)
+int launch_cross_build_mfma(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, int64_t ldk, double* Kst, double* mean_part,
+                            int raw_affine, int hybrid) {
+    hipStream_t st = ctx->stream;
+    KernParams kp;
+    int dsel = 0;
+    int64_t ldm = 0;
+    GPRY_TRY(center_cands(ctx, Xc, m0, mc, raw_affine, &kp, &dsel, &ldm));
     dim3 grid((unsigned)((mc + 255) / 256), (unsigned)(ctx->Np / 128));
     // near pairs of the hybrid form: r^2 < 100 (in units of the kernel's scaled argument u = corr_scale * r^2)
 #define CM2(DP, KID) do { const double ucut = 100.0 * corr_scale<KID>();                                                                  \
@@ -528,6 +573,27 @@ int launch_cross_build_mfma(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t
     DISPATCH_KID(ctx->kernel_id, CM4)
 #undef CM4
 #undef CM2
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// The bound pass of a pruned sweep (cross_build_mfma_kernel<.., HYB, BND>): mean partials over the live blocks, their sums of
+// |alpha_j v_j| (sabs_part, same layout) and the live-block count (added to *live_cnt).  After launch_cross_prepare.
+int launch_cross_mean_bound(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, double* mean_part, double* sabs_part,
+                            double ubnd, double uhi, unsigned long long* live_cnt) {
+    hipStream_t st = ctx->stream;
+    KernParams kp;
+    int dsel = 0;
+    int64_t ldm = 0;
+    GPRY_TRY(center_cands(ctx, Xc, m0, mc, 1, &kp, &dsel, &ldm));
+    dim3 grid((unsigned)((mc + 255) / 256), (unsigned)(ctx->Np / 128));
+#define CB2(DP, KID) hipLaunchKernelGGL((cross_build_mfma_kernel<DP, KID, true, true>), grid, dim3(256), 0, st, ctx->dXcs, ldm, mc, ctx->dYcs, \
+                                        ctx->dalpha_, nullptr, mc, mean_part, kp, 100.0 * corr_scale<KID>(), ubnd, uhi, sabs_part, live_cnt)
+#define CB4(KID) { if (dsel == 4) CB2(4, KID); else if (dsel == 8) CB2(8, KID); else if (dsel == 16) CB2(16, KID); \
+                   else if (dsel == 24) CB2(24, KID); else CB2(32, KID); }
+    DISPATCH_KID(ctx->kernel_id, CB4)
+#undef CB4
+#undef CB2
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

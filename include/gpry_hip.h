@@ -122,7 +122,9 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *                             far below the extent of its data takes the hybrid form (matrix-pipe distances, every pair nearer than
  *                             r^2 = 100 again from the coordinates) instead of the difference form; 0: always the difference form
  *     "panel_debug"           test hooks, ORed bits: 32 the matrix-pipe panel whatever the estimates say, 64 every Cholesky panel step
- *                             reports a timed-out wait, 128 the scratch sets of a batched objective start as NaNs (default 0)
+ *                             reports a timed-out wait, 128 the scratch sets of a batched objective start as NaNs, 256 gpry_sweep_fetch
+ *                             of a pruned sweep returns the arrays as they stand (bounds of y and acq where nothing was contracted)
+ *                             without completing it (default 0)
  *     "topk_host"             largest pool that gpry_sweep_topk selects on the host from one kernel's records
  *                             (default 16384; 0 = always the device radix select)
  *     "predict_small"         mean-only gpry_predict of at most this many points is one fused launch (default 2048)
@@ -135,6 +137,11 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *     "sweep_prune" 0/1       1: gpry_sweep_logexp with no arrays wanted builds only y and an exact upper bound of every candidate's
  *                             acquisition (its prior sigma); gpry_sweep_topk contracts only the candidates whose bound can reach
  *                             the shortlist (same records, bit for bit; see gpry_sweep_topk).  Default 0: the full sweep
+ *     "sweep_mean_bound" 0/1  1 (default): such a sweep in the hybrid panel form (gpry_sweep_info) bounds y as well: its mean pass
+ *                             skips every block of pairs too far apart to move y by more than ~1e-13 of the normalised targets,
+ *                             adds a rigorous slack for them and for rounding, and computes y exactly only for the candidates it
+ *                             contracts (same records and, after gpry_sweep_fetch, the same arrays bit for bit).  0: y exactly for
+ *                             every candidate in the mean pass
  *     "chol_stacked"          up to this padded training-set size (default 2048; at most 3584) the inverse factor V = L^-1 comes
  *                             out of the launches of the Cholesky factorisation itself (the identity appended to the matrix as
  *                             extra rows); 0: always the recursive inverse behind the factorisation.  Same L; V, and what is
@@ -340,7 +347,9 @@ int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n
 /* Statistics of the last pruned sweep: info[0] 1 while it is still pruned (0 once completed or after a full sweep),
  * [1] pool size, [2] candidates ranked by bound and contracted exactly (K'), [3] contraction rounds, [4] candidates
  * contracted in all, [5] 1 if the full sweep had to run, [6] Kp of the last gpry_sweep_topk, [7] candidates whose bound
- * was not below the threshold of the first contraction round (-1: that round answered alone).  dinfo (nullable, 5 doubles):
+ * was not below the threshold of the first contraction round (-1: that round answered alone), [8] 1 if the mean pass bounded y
+ * (option "sweep_mean_bound"): the survivors of [7] were then ranked by bounds of y as well, [9] blocks of 16 training rows x
+ * 32 candidates that pass evaluated, [10] blocks it saw (info: 11 values).  dinfo (nullable, 5 doubles):
  * [0] that threshold (NaN if none), [1..4] device ms so far of the stages "sweep_mean", "sweep_prune_select", "sweep_compact",
  * "sweep_prune_gemm" (the per-stage timers of gpry_timing_get; 0 while timing is off).  The contraction rounds and the
  * completion use a copy of the model taken at the end of the sweep: a refit or refactorisation in between does not change
