@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the GP refit + NORA acquisition cycle (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cycle|farm] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload cycle|farm] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, dumps (``--dump-outputs``) and prints its line: every figure in it comes
+from the setup or from the timed steps themselves.  ``--full`` adds, behind the timed region, what takes runs of its own:
+the resident-pool cycle, the serial and pipelined factor chains, the back-to-back kernel-build launches and the measured
+peaks of the GPU, the 1-GPU scaling check of an N-GPU run, ``refit_extras`` and ``small_n`` (``--extras off`` drops these
+two and the scaling check), ``cpu_baseline`` (``--cpu-baseline off`` drops it); config1: the predict through the host
+boundary, its comparison with the sweep and the CPU port beside it.
 
 ``--workload cycle`` (default; BASELINE configs[2] at N=1, configs[3] at N>1).  One *step* is one
 active-learning cycle of GPry's hot path at EXACTLY N_train = 4096 (16-d synthetic posterior,
@@ -16,7 +23,7 @@ every refit, factorisation and sweep of every timed step runs at N_train = N; ``
 N_train_per_step`` lists what each step saw and the run aborts if one differs.  Every timed step gets a
 FRESH candidate pool (two pre-generated pools in turn, SURVEY.md 8d / gpry/gp_acquisition.py:1023-1031): its
 upload (128 MB) is inside the timed region, chunk by chunk underneath the sweep; ``cycle.
-resident_pool_ms_per_step`` is the same cycle on a pool that stays in HBM (what rounds 1-4 reported as the
+resident_pool_ms_per_step`` (``--full``) is the same cycle on a pool that stays in HBM (what rounds 1-4 reported as the
 headline).  With N > 1 GPUs (one process per GPU, self-launched or by
 torch.distributed.run) the refit is replicated and the SAME pool of M candidates is sharded N-way
 (``--scaling strong``, the default: configs[3]); ``--scaling weak`` gives every rank M candidates.
@@ -733,16 +740,10 @@ def run_config1(args):
     names = ("kernel_build", "potrf", "trtri", "cross_build", "sweep_gemm", "sweep_gemm_splitk", "sweep_finish")
     T = {k_: dev.timing(k_) for k_ in names}
     dev.set_option("timing", 0)
-    res = dev.sweep_fetch(want=("y", "sigma"))
+    if args.dump_outputs or args.full:
+        res = dev.sweep_fetch(want=("y", "sigma"))
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, {"mean": res["y"], "std": res["sigma"]})
-    same = {"bit_identical": bool(np.array_equal(res["y"], mean0) and np.array_equal(res["sigma"], std0)),
-            "max_abs_mean": float(np.max(np.abs(res["y"] - mean0))), "max_abs_std": float(np.max(np.abs(res["sigma"] - std0)))}
-    # through the host boundary
-    t1 = time.perf_counter()
-    for _ in range(3):
-        gpr.predict(Xc, return_std=True)
-    predict_host_ms = (time.perf_counter() - t1) / 3 * 1e3
     Np = (N + 127) // 128 * 128
     per = lambda k_: T[k_][0] / max(T[k_][1], 1)            # ms per launch
     per_step = lambda k_: T[k_][0] / K
@@ -763,7 +764,6 @@ def run_config1(args):
                                f"+ Cholesky + V = L^-1 + predict(return_std=True) over M={M} resident candidates, fixed theta",
                    "N_train": N, "Np": Np, "d": d, "M_total": M, "kernel": "ConstantKernel*RBF", "rccl_ranks": 0},
         "stage_ms_per_step": {k_: per_step(k_) for k_ in names if T[k_][1]},
-        "results_equal_predict": same, "predict_through_host_boundary_ms": predict_host_ms,
         "roofline": {"kernel": "sweep contraction (V lower-triangular x K*^T panel, sum-of-squares epilogue)", "bound": "mfma",
                      "achieved": achieved, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / F64_MFMA_PEAK_TFLOPS,
                      "traffic": measured_traffic("config1", Np, M)[0], "traffic_note": measured_traffic("config1", Np, M)[1],
@@ -777,6 +777,15 @@ def run_config1(args):
                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "avg_launch_ms": per("cross_build"), "bytes_per_launch": cb_bytes},
     }
     result["cross_build"]["frac"] = result["cross_build"]["achieved"] / HBM_PEAK_GBPS
+    if args.full:
+        result["results_equal_predict"] = {
+            "bit_identical": bool(np.array_equal(res["y"], mean0) and np.array_equal(res["sigma"], std0)),
+            "max_abs_mean": float(np.max(np.abs(res["y"] - mean0))), "max_abs_std": float(np.max(np.abs(res["sigma"] - std0)))}
+        # through the host boundary
+        t1 = time.perf_counter()
+        for _ in range(3):
+            gpr.predict(Xc, return_std=True)
+        result["predict_through_host_boundary_ms"] = (time.perf_counter() - t1) / 3 * 1e3
     if args.cpu_baseline == "auto":
         try:
             from oracle import gpry_oracle as orc
@@ -994,8 +1003,11 @@ def main(argv=None):
     ap.add_argument("--restarts", type=int, default=32)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
     ap.add_argument("--allow-gloo", action="store_true")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
-    ap.add_argument("--extras", choices=["auto", "off"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also measure what the headline does not need (module docstring)")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto", help="with --full: the CPU port beside the GPU")
+    ap.add_argument("--extras", choices=["auto", "off"], default="auto",
+                    help="with --full: refit_extras, small_n and the 1-GPU scaling check")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args(argv)
@@ -1003,6 +1015,8 @@ def main(argv=None):
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not args.full:          # a plain run: the headline and nothing behind it
+        args.extras = args.cpu_baseline = "off"
 
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     group_mode = args.workload == "farm" and args.mode == "group"
@@ -1132,12 +1146,12 @@ def main(argv=None):
              "sweep_finish", "topk")
     T = {k: dev.timing(k) for k in names}
     sweep_flops_timed, n_seen_timed, host_timed = work["sweep_flops"], list(n_seen), dict(host_t)
-    # ---- the same cycle on ONE pool that stays resident in HBM (rounds 1-4 timed this): min(K, 5) steps behind the
-    # headline loop, every rank alike
+    # ---- --full: the same cycle on ONE pool that stays resident in HBM (rounds 1-4 timed this): min(K, 5) steps behind
+    # the headline loop
     # (one-GPU runs only: behind the timed region of an N-GPU run nothing collective may follow before rank 0 has printed
     # its line -- a peer that dies there must not take the measurement with it)
     K_res, resident_elapsed = 0, None
-    if world == 1:
+    if world == 1 and args.full:
         acq.do_MC_sample = lambda gpr, bounds=None, rng=None, sampler=None: (pools[0], None, None, None)
         step()                                          # (the first one uploads pools[0])
         fence()
@@ -1234,7 +1248,7 @@ def main(argv=None):
                               "frac": tf / F64_MFMA_PEAK_TFLOPS, "avg_ms": po_ms / po_n, "calls": po_n,
                               "flops_per_call": float(Np) ** 3 / 3.0,
                               "factor_chain_tflops": float(Np) ** 3 / (chain_ms * 1e-3) / 1e12}
-    if rank == 0 and po_n:
+    if rank == 0 and po_n and args.full:
         # From Np = 4096 on the first three quarters of V = L^-1 run on a second stream underneath the
         # panel chain of potrf (csrc/chol.hip: trtri_pipeline_*): the `potrf` stage above then contains
         # the price of sharing the GPU, the `trtri` stage only what is left after it.  Quote the same
@@ -1262,7 +1276,7 @@ def main(argv=None):
             result["cholesky"]["serial_chain_error"] = repr(e)
         finally:
             dev.set_option("factor_pipeline", 1)
-    if rank == 0:
+    if rank == 0 and args.full:
         # the build is one 40-us launch per LML evaluation: two events around a single launch also
         # time the dispatch gap, so quote the steady-state duration (50 launches back to back) too
         try:

@@ -103,6 +103,35 @@ def test_one_rank_dumps_the_outputs_of_its_last_timed_step(tmp_path):
         np.testing.assert_array_equal(a[k], b[k])
 
 
+def test_a_plain_run_stops_at_its_line_and_full_adds_the_rest(tmp_path):
+    """A plain run times its steps and prints; ``--full`` measures more behind the timed region (the resident-pool cycle,
+    the measured peaks) and leaves the headline's outputs as they were."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    base = ["--gpus", "1", "--N", "96", "--d", "3", "--M", "3000", "--steps", "3", "--warmup", "1"]
+    lines, dumps = {}, {}
+    for run, extra in (("plain", []), ("full", ["--full", "--extras", "off", "--cpu-baseline", "off"])):
+        out = subprocess.run([sys.executable, DOUBLE] + base + extra + ["--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, env=env, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[run] = json.loads([ln for ln in out.stdout.splitlines() if ln.lstrip().startswith("{")][-1])
+        dumps[run] = {f.stem: np.load(f) for f in (tmp_path / run).glob("*.npy")}
+    plain, full = lines["plain"], lines["full"]
+    for r in (plain, full):
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+        assert r["config"]["N_train_per_step"] == [96] * 3
+    assert plain["cycle"]["resident_pool_steps"] == 0 and plain["cycle"]["resident_pool_ms_per_step"] is None
+    for key in ("measured_peaks", "refit_extras", "small_n", "cpu_baseline"):
+        assert key not in plain, key
+    assert full["cycle"]["resident_pool_steps"] == 3 and full["cycle"]["resident_pool_ms_per_step"] > 0
+    assert "measured_peaks" in full
+    assert sorted(dumps["plain"]) == sorted(dumps["full"]) == ["acq", "lml", "proposals", "theta", "y_lies"]
+    for k in dumps["plain"]:
+        np.testing.assert_array_equal(dumps["plain"][k], dumps["full"][k])
+
+
 def test_dump_outputs_keeps_the_same_seeded_rows_under_the_size_limit(tmp_path, monkeypatch):
     import numpy as np
     import bench
