@@ -64,6 +64,8 @@ SIGNATURES = {
     "gpry_ns_prior": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int64, _vp, _vp, _P(C.c_double)]),
     "gpry_ns_generation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64, C.c_int64,
                                      C.c_int, C.c_int, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_mcmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_double, C.c_uint64,
+                                   C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -415,6 +417,33 @@ class Device:
                                                  _ptr(W), int(seed), int(generation), int(k), int(num_repeats),
                                                  _ptr(X_new), _ptr(y_new), _ptr(cnt), C.byref(ms)), "gpry_ns_generation")
         return X_new, y_new, cnt, ms.value
+
+    # -- Metropolis MCMC of the mean (gpry_amd/mcmc.py drives this one) ---------------------
+    def mcmc_chains(self, lo, hi, X0, y0, Lp, T, minus_inf_value, seed, batch, nsteps, thin, proposals=False):
+        """``nsteps`` Metropolis steps of ``len(X0)`` chains from the states (X0, y0) (y0 NaN: evaluated first), proposal
+        u' = u + Lp z in unit-cube coordinates: a dict with ``X`` (nchains, nsteps // thin, d) and ``y`` (nchains,
+        nsteps // thin), the states after every thin-th step; ``X_last`` / ``y_last``, ``naccept`` / ``ncalls`` per chain;
+        ``device_ms``; with ``proposals`` also ``X_prop`` (nchains, nsteps, d) and ``y_prop`` (NaN: not evaluated)."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X0 = _f64(X0)
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise ValueError(f"expected start states of shape (nchains, {self.d}), got {X0.shape}")
+        n, d = X0.shape
+        y0, Lp = _f64(y0, (n,)), _f64(Lp, (d, d))
+        nsteps, thin = int(nsteps), int(thin)
+        nrec = nsteps // thin if thin > 0 else 0
+        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
+                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64))
+        if proposals:
+            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_mcmc_chains(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(Lp), float(T),
+                                               float(minus_inf_value), int(seed), int(batch), nsteps, thin,
+                                               _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]), _ptr(out["y_last"]),
+                                               _ptr(out["naccept"]), _ptr(out["ncalls"]), _ptr(out.get("X_prop")),
+                                               _ptr(out.get("y_prop")), C.byref(ms)), "gpry_mcmc_chains")
+        out["device_ms"] = ms.value
+        return out
 
     def set_gates(self, sv=None, coef=None, gamma=0.0, intercept=0.0, positive_is_finite=True,
                   trust_bounds=None):

@@ -171,6 +171,8 @@ struct gpry_ctx {
     void* srv = nullptr;
     int opt_predict_serve = 1;         // mean-only gpry_predict of <= 8 points goes through the resident kernel
     int64_t opt_serve_idle_us = 2000;  // the kernel leaves after this long without a request
+    int opt_mcmc_mapped = 0;           // gpry_mcmc_chains: 1 = the chains write their records to mapped pinned memory, 0 = to
+                                       // device memory, copied back once per call (profiles/mcmc.md)
     int64_t opt_chol_stacked = 2048;   // up to this Np the inverse factor comes out of the Cholesky launches themselves (potrf_stacked, chol_panel.hip); 0: never
     int opt_chol_stacked_dense = 0;    // 1: potrf_stacked without use of the zero structure of the appended rows (comparator)
     int opt_sweep_overlap = 0;         // 1: the cross-kernel panel of chunk c + 1 is built on the side stream underneath the contraction of chunk c (two panels)
@@ -218,6 +220,8 @@ struct gpry_ctx {
     int64_t xg_cap = 0;                // doubles
     int64_t* dgidx = nullptr;          // their pool indices
     int64_t gidx_cap = 0;
+    char* dmc = nullptr;               // gpry_mcmc_chains: start states, proposal factor and outputs (bytes)
+    int64_t mc_cap = 0;
 
     // host pinned staging
     void* hpin = nullptr; void* hpin_dev = nullptr; int64_t hpin_cap = 0;   // host / device view of the same buffer

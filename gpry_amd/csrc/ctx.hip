@@ -247,7 +247,7 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->dcand, ctx->dsel, ctx->dU, ctx->dXkb, ctx->dkbout, ctx->pr.dXc, ctx->pr.dmask,
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
-                    ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX};
+                    ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hbres) (void)hipHostFree(ctx->hbres);
@@ -315,6 +315,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("predict_gates", opt_predict_gates, 0, 1, (void)0),
     OPT_INT("predict_serve", opt_predict_serve, 0, 1, (void)0),
     OPT_INT("serve_idle_us", opt_serve_idle_us, 10, 1000000, (void)0),
+    OPT_INT("mcmc_mapped", opt_mcmc_mapped, 0, 1, (void)0),
 };
 #undef OPT_INT
 const OptionSpec* find_option(const char* key) {

@@ -1,0 +1,116 @@
+// What the two device samplers of the surrogate's mean share: nested.hip (nested sampling) and mcmc.hip (Metropolis).
+// ns_eval is gpry_predict(x[None]) bit for bit (see nested.hip for the argument); ns_philox is the counter-based
+// generator both draw from, restated in numpy by tests/tools/ns_philox.py.  Phases of the counter's word 0: 0-2 belong
+// to the nested sampler (nested.hip), 3 to the Metropolis chains (mcmc.hip).
+#pragma once
+#include "kern_math.h"
+
+struct NsU2 { double a, b; };
+
+// the value of a product as it was rounded: an empty asm statement the combiner cannot look through, so that the sum
+// it feeds is not fused into an FMA (-ffp-contract=fast) and rounds as the host's two operations do
+__device__ __forceinline__ double ns_rn(double v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// Philox4x32-10 (Salmon et al. 2011): two uniforms in [0, 1), 53 bits each, from words (0, 1) and (2, 3)
+__device__ __forceinline__ NsU2 ns_philox(unsigned long long seed, unsigned phase, unsigned draw, unsigned gen,
+                                          unsigned chain, unsigned step) {
+    unsigned c0 = (phase << 24) | draw, c1 = gen, c2 = chain, c3 = step;
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0, hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    NsU2 u;
+    u.a = (double)((((unsigned long long)c0 << 32) | c1) >> 11) * 0x1.0p-53;
+    u.b = (double)((((unsigned long long)c2 << 32) | c3) >> 11) * 0x1.0p-53;
+    return u;
+}
+
+struct NsArgs {
+    const double* Xs; const double* alpha_;
+    int64_t rows_per_split;
+    int nsplit, gates;
+    double y_std, y_mean, clip_hi;
+    GateParams gate;
+    unsigned long long seed;
+    double lo[GPRY_MAX_DIM], hi[GPRY_MAX_DIM];
+};
+
+// y of the point x (raw coordinates in LDS), valid in every thread.  Same slices, sums and finish as gpry_predict's
+// one-point path (api.hip) and the resident kernel's (server.hip).
+template <int DP, int KID>
+__device__ double ns_eval(const double* x, const NsArgs& a, const KernParams& kp, const AffParams& ap, double* r2s,
+                          double* red, double* s_y) {
+    double mu = 0.0;
+    for (int s = 0; s < a.nsplit; s++) {
+        const double v = mean_slice<DP, KID>(x, a.Xs, a.alpha_, (int64_t)s * a.rows_per_split, a.rows_per_split, kp, ap, r2s, red);
+        mu = mu + v;                         // (thread 0 holds the slice sums)
+    }
+    const unsigned bits = a.gates ? point_gate_bits(x, a.gate, kp, ap, red) : 0u;
+    if (threadIdx.x == 0) {
+        double y = fmin(ns_rn(mu * a.y_std) + a.y_mean, a.clip_hi);
+        if (bits) y = -INFINITY;
+        *s_y = y;
+    }
+    __syncthreads();
+    const double y = *s_y;
+    __syncthreads();
+    return y;
+}
+
+// ---- host side -----------------------------------------------------------------------------------
+static int ns_args(gpry_ctx* ctx, const char* who, const double* lo, const double* hi, unsigned long long seed, NsArgs* a, KernParams* kp,
+                   AffParams* ap) {
+    if (ctx->d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "%s: d = %d > %d", who, ctx->d, GPRY_MAX_DIM);
+    GPRY_TRY(ensure_pred_xs(ctx));
+    *kp = make_kp(ctx);
+    *ap = make_ap(ctx, kp->has_aff);
+    int nsplit = (int)(ctx->N / 1024);            // the slices of the one-point path (api.hip: gpry_predict)
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > 8) nsplit = 8;
+    a->Xs = ctx->dXs; a->alpha_ = ctx->dalpha_;
+    a->nsplit = nsplit;
+    a->rows_per_split = round_up((ctx->N + nsplit - 1) / nsplit, 32);
+    a->gates = ctx->gates_on;
+    a->gate = make_gp(ctx);
+    a->y_std = ctx->tf.y_std; a->y_mean = ctx->tf.y_mean; a->clip_hi = ctx->tf.clip_hi;
+    a->seed = seed;
+    for (int k = 0; k < GPRY_MAX_DIM; k++) {
+        a->lo[k] = k < ctx->d ? lo[k] : 0.0;
+        a->hi[k] = k < ctx->d ? hi[k] : 1.0;
+        if (k < ctx->d && !(lo[k] < hi[k]))
+            return gpry_fail(ctx, -1, "%s: bounds of dimension %d are [%g, %g]", who, k, lo[k], hi[k]);
+    }
+    return 0;
+}
+
+struct NsTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~NsTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+static int ns_begin(gpry_ctx* ctx, NsTimer* tm) {
+    GPRY_TRY(serve_stop(ctx));          // the resident predict kernel would share the CUs
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventCreate(&tm->e0));
+    HIP_TRY(ctx, hipEventCreate(&tm->e1));
+    HIP_TRY(ctx, hipEventRecord(tm->e0, ctx->stream));
+    return 0;
+}
+
+static int ns_end(gpry_ctx* ctx, NsTimer* tm, double* device_ms) {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(tm->e1, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, tm->e0, tm->e1));
+    if (device_ms) *device_ms = ms;
+    return 0;
+}
+

@@ -25,3 +25,16 @@ def patch_gpry():
     gpry.run.Normalize_bounds = Normalize_bounds
     gpry.run.Normalize_y = Normalize_y
     return gpry
+
+
+def patch_gpry_mc():
+    """Opt-in: after this call ``gpry.mc.mc_sample_from_gp_ns`` is the device nested sampler
+    (``gpry_amd.mc.mc_sample_from_gp_ns``), so an unmodified ``Runner.generate_mc_sample()`` -- its "nested" default,
+    gpry/run.py:1655-1681 -- samples the surrogate on the device.  The Runner's "mcmc" branch builds Cobaya objects and is
+    not rebound; call ``gpry_amd.mc.mc_sample_from_gp(gpr, sampler="mcmc")`` for the device MCMC instead.  Returns the
+    patched ``gpry.mc`` module."""
+    import gpry.mc
+    from gpry_amd.mc import mc_sample_from_gp_ns
+
+    gpry.mc.mc_sample_from_gp_ns = mc_sample_from_gp_ns
+    return gpry.mc

@@ -1,0 +1,141 @@
+"""The Monte Carlo sample of the surrogate that a run ends with (gpry/mc.py), made on the device.
+
+``mc_sample_from_gp(gpr, sampler="nested" | "mcmc")`` runs one of the two device samplers of the surrogate's mean:
+the nested sampler of ``gpry_amd/nested.py`` in place of PolyChord / UltraNest (gpry/mc.py:328-456), or the Metropolis
+chains of ``gpry_amd/mcmc.py`` in place of Cobaya's MCMC (gpry/mc.py:173-327).  Both evaluate ``gpr.predict(x[None])``
+bit for bit, the classifier and trust region included.  ``mc_sample_from_gp_ns`` keeps the reference's signature, so
+that ``gpry_amd.integration.patch_gpry_mc`` can put it under an unmodified ``Runner.generate_mc_sample``.
+"""
+import os
+import warnings
+
+import numpy as np
+
+from gpry_amd.tools import generic_params_names, get_Xnumber
+
+# PolyChord's defaults (the Runner passes nlive = 50d)
+NESTED_DEFAULTS = {"nlive": "25d", "num_repeats": "5d", "precision_criterion": 0.001, "nprior": None, "max_ncalls": None}
+# Cobaya's names where they exist -> run_mcmc's arguments
+MCMC_KEYS = {"Rminus1_stop": "Rminus1_stop", "temperature": "temperature", "covmat": "covmat",
+             "max_samples": "max_ncalls", "max_ncalls": "max_ncalls", "nchains": "nchains", "learn_every": "learn_every",
+             "learn_batches": "learn_batches", "batch_steps": "batch_steps", "max_batches": "max_batches",
+             "thin": "thin", "skip": "skip", "reset_temperature": "reset_temperature"}
+
+
+def _known(options, keys, sampler):
+    """The entries of ``options`` whose key is in ``keys``; a warning for the rest (gpry/ns_interfaces.py:160-170)."""
+    options = dict(options or {})
+    unknown = [k for k in options if k not in keys]
+    if unknown:
+        warnings.warn(f"Options {unknown} not recognised by the device sampler '{sampler}'; they are ignored. "
+                      f"Known: {sorted(keys)}")
+    return {k: v for k, v in options.items() if k in keys}
+
+
+def nested_settings(d, sampler_options=None):
+    """run_nested's settings from PolyChord-style options; Xnumber strings such as ``"50d"`` are multiples of d."""
+    opts = dict(NESTED_DEFAULTS)
+    opts.update(_known(sampler_options, NESTED_DEFAULTS, "nested"))
+    out = {}
+    for k in ("nlive", "num_repeats"):
+        out[k] = get_Xnumber(opts[k], "d", d, int, k)
+    out["precision_criterion"] = float(opts["precision_criterion"])
+    out["nprior"] = out["nlive"] if opts["nprior"] is None else get_Xnumber(opts["nprior"], "d", d, int, "nprior")
+    out["max_ncalls"] = None if opts["max_ncalls"] is None else get_Xnumber(opts["max_ncalls"], "d", d, int, "max_ncalls")
+    return out
+
+
+def mcmc_settings(d, sampler_options=None):
+    """run_mcmc's keyword arguments from Cobaya-style options (``Rminus1_cl_stop`` and other unknown keys: a warning)."""
+    out = {}
+    for k, v in _known(sampler_options, MCMC_KEYS, "mcmc").items():
+        if k in ("max_samples", "max_ncalls", "nchains", "learn_every", "batch_steps", "thin") and v is not None:
+            v = get_Xnumber(v, "d", d, int, k)
+        out[MCMC_KEYS[k]] = v
+    return out
+
+
+def _bounds(gpr, bounds):
+    if bounds is None:
+        bounds = gpr.trust_bounds if getattr(gpr, "trust_bounds", None) is not None else gpr.bounds
+    return np.asarray(bounds, dtype=float)
+
+
+def _push_model(gpr, sampler):
+    """The model, its affine maps and the gates on the device, as NORA._do_MC_sample_nested pushes them."""
+    gpr._ensure_factor()
+    gpr._push_affine()
+    if not gpr._push_gates():
+        raise ValueError(f"sampler='{sampler}' evaluates the classifier on the device, and this classifier has no device "
+                         "form")
+
+
+def write_sample(output, X, y, w, params=None):
+    """The reference's file (gpry/mc.py:427-455): header ``w minuslogp x_1 ...``, columns [w, -y, X]; ``.txt`` is
+    appended to a name without extension and ``mc_samples.txt`` used for a bare directory.  Returns the path."""
+    base_dir, file_name = os.path.split(output)
+    base_dir = os.path.abspath(base_dir or os.path.curdir)
+    os.makedirs(base_dir, exist_ok=True)
+    root, ext = os.path.splitext(file_name or "mc_samples.txt")
+    path = os.path.join(base_dir, root + (ext or ".txt"))
+    if params is None:
+        params = generic_params_names(X.shape[1])
+    w_write = w if w is not None else np.ones(len(y))
+    np.savetxt(path, np.concatenate([np.atleast_2d(w_write), np.atleast_2d(-np.asarray(y)), np.asarray(X).T]).T,
+               header="w minuslogp " + " ".join(params))
+    return path
+
+
+def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, output=None, seed=None, params=None):
+    """Monte Carlo sample of the surrogate's posterior mean, on the device: ``(X, y, w)``, w normalised.
+
+    bounds: default ``gpr.trust_bounds``, else ``gpr.bounds`` (gpry/mc.py:381-382).  sampler: ``"nested"`` (options
+    nlive, num_repeats, precision_criterion, nprior, max_ncalls; PolyChord's defaults 25d, 5d, 0.001, nlive) or
+    ``"mcmc"`` (options Rminus1_stop, temperature, covmat, max_samples -> max_ncalls, and run_mcmc's nchains,
+    learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature).  Unknown options are warned
+    about and ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.  The
+    run's details are kept in ``mc_sample_from_gp.last_result``."""
+    if not isinstance(sampler, str) or sampler.lower() not in ("nested", "mcmc"):
+        raise ValueError(f"sampler must be 'nested' or 'mcmc', got {sampler!r}")
+    sampler = sampler.lower()
+    b = _bounds(gpr, bounds)
+    d = len(b)
+    if seed is None:
+        seed = int(np.random.default_rng().integers(2**31 - 1))
+    seed = int(seed)
+    if sampler == "nested":
+        from gpry_amd.nested import run_nested
+        s = nested_settings(d, sampler_options)
+        _push_model(gpr, sampler)
+        res = run_nested(gpr.device, b, seed, s["nlive"], s["num_repeats"], precision_criterion=s["precision_criterion"],
+                         nprior=s["nprior"], max_ncalls=s["max_ncalls"], minus_inf_value=gpr.minus_inf_value)
+    else:
+        from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
+        s = mcmc_settings(d, sampler_options)
+        nchains = s.pop("nchains", DEFAULT_NCHAINS)
+        _push_model(gpr, sampler)
+        res = run_mcmc(gpr.device, b, seed, nchains, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value, **s)
+    gpr.n_eval += res.ncalls
+    mc_sample_from_gp.last_result = res
+    if output is not None:
+        write_sample(output, res.X, res.y, res.w, params)
+    return res.X, res.y, res.w
+
+
+mc_sample_from_gp.last_result = None
+
+
+def mc_sample_from_gp_ns(gpr, bounds=None, params=None, sampler=None, sampler_options=None, output=None, run=True,
+                         verbose=3, seed=None):
+    """gpry/mc.py:328-456 with the device nested sampler in place of PolyChord / UltraNest: ``(X, y, w)``.  ``sampler``
+    may be None, "nested", "polychord" or "ultranest" (all run the device sampler; their options are PolyChord's);
+    ``run=False`` has no initialised sampler object to return and raises."""
+    if not run:
+        raise ValueError("run=False returns an initialised PolyChord / UltraNest sampler in the reference; the device "
+                         "nested sampler has no such object: call with run=True")
+    if sampler is not None and (not isinstance(sampler, str)
+                                or sampler.lower() not in ("nested", "polychord", "ultranest")):
+        raise ValueError(f"Nested sampler {sampler!r} unknown: the device sampler stands for 'nested', 'polychord' "
+                         "and 'ultranest'")
+    return mc_sample_from_gp(gpr, bounds=bounds, sampler="nested", sampler_options=sampler_options, output=output,
+                             seed=seed, params=params)

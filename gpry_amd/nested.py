@@ -49,6 +49,13 @@ def whitening(U):
     U = np.asarray(U, dtype=float)
     d = U.shape[1]
     C = np.atleast_2d(np.cov(U, rowvar=False, ddof=0)) if len(U) > 1 else np.zeros((d, d))
+    return cholesky_ridged(C)
+
+
+def cholesky_ridged(C):
+    """Lower Cholesky factor of the covariance matrix C, with a growing ridge while C is singular."""
+    C = np.atleast_2d(np.asarray(C, dtype=float))
+    d = C.shape[0]
     scale = max(float(np.trace(C)) / d, 1e-12)
     ridge = 0.0
     for _ in range(30):

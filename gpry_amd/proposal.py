@@ -2,12 +2,14 @@
 
 Only what ``BatchOptimizer`` needs: the proposer interface (``get`` / ``update`` / ``update_bounds``),
 the uniform proposer, the centroids proposer and their mixture -- the default of
-gpry/gp_acquisition.py:219-221.  A seeded run has to propose the reference's points, so the draws consume the
+gpry/gp_acquisition.py:219-221 -- and the short-chain proposer, whose chains run on the device.  A seeded run has to propose the reference's points, so the draws consume the
 generator exactly as the reference's frozen scipy distributions do -- ``uniform(loc, scale).rvs`` is
 ``uniform(0, 1, size) * scale + loc`` and ``expon(scale=s).rvs`` is ``standard_exponential(size) * s`` on the
 generator that is passed in -- but are written as those two expressions (a frozen-distribution ``rvs`` costs 50 us
 of argument checking per call; tests/test_fit_farm_cpu.py compares both with scipy bit for bit).
 """
+from warnings import warn
+
 import numpy as np
 
 from gpry_amd.tools import check_random_state, is_in_bounds
@@ -111,3 +113,73 @@ class PartialProposer(Proposer):
     def update_bounds(self, bounds):
         for p in self._both:
             p.update_bounds(bounds)
+
+
+class SmallChainProposer(Proposer):
+    """Points from the end of a short Metropolis chain of the surrogate's mean (gpry/proposal.py:359-443), run on the
+    device (``gpry_amd/mcmc.py``).  ``update(gpr)`` keeps the model.  ``get`` hands out the stored points from the end and
+    calls ``resample`` when none are left: one chain of ``npoints`` steps from a random training point, proposal
+    u' = u + 2.38 / sqrt(d) chol(C) z with C the exp(y - y_max)-weighted covariance of the training set; the points kept
+    are ``chain[::-nsteps]``.  After ``nretries`` chains without an accepted step, ``nsteps`` uniform points instead.
+
+    The reference runs Cobaya's sampler for the chain, so a seeded run here draws other points than the reference's:
+    the start comes from ``rng.choice`` as there, the chain from the device's counter-based draws seeded by ``rng``."""
+
+    def __init__(self, bounds, npoints=100, nsteps=20, nretries=3):
+        self.samples = []
+        self.gpr = None
+        self.update_bounds(bounds)
+        self.nretries = nretries
+        self.npoints = npoints
+        self.nsteps = nsteps
+
+    def update_bounds(self, bounds):
+        Proposer.update_bounds(self, bounds)
+        self.random_proposer = UniformProposer(bounds)
+
+    def update(self, gpr):
+        self.samples = []
+        self.gpr = gpr
+
+    def get(self, rng=None):
+        """The next stored point inside the box (the reference's ``check_in_bounds``: a start outside it is skipped)."""
+        tries = 0
+        while True:
+            if len(self.samples) == 0:
+                self.resample(rng)
+            last, self.samples = self.samples[-1], self.samples[:-1]
+            if is_in_bounds(last, self.bounds)[0]:
+                return last
+            tries += 1
+            if not tries % 1000:
+                warn(f"[{self.__class__.__name__}] Could produce a proposal within the given bounds after {tries} tries.")
+
+    def resample(self, rng=None):
+        from gpry_amd.mcmc import PROPOSAL_SCALE, _weighted_cov
+        from gpry_amd.nested import cholesky_ridged
+        if self.gpr is None:
+            raise ValueError("SmallChainProposer needs a model: call update(gpr) first")
+        rng = check_random_state(rng)
+        gpr = self.gpr
+        gpr._ensure_factor()
+        gpr._push_affine()
+        if not gpr._push_gates():
+            raise ValueError("SmallChainProposer evaluates the classifier on the device, and this classifier has no "
+                             "device form")
+        lo, hi = self.corners
+        span = hi - lo
+        X, y = np.asarray(gpr.X_train, dtype=float), np.asarray(gpr.y_train, dtype=float)
+        Lp = PROPOSAL_SCALE / np.sqrt(self.d) * cholesky_ridged(_weighted_cov(X, y) / np.outer(span, span))
+        for _ in range(self.nretries):
+            i = rng.choice(range(len(X)))
+            seed = int(rng.integers(2**31 - 1)) if hasattr(rng, "integers") else int(rng.randint(2**31 - 1))
+            out = gpr.device.mcmc_chains(lo, hi, X[i:i + 1], np.array([np.nan]), Lp, 1.0, gpr.minus_inf_value, seed, 0,
+                                         self.npoints, 1)
+            gpr.n_eval += int(np.sum(out["ncalls"]))
+            if out["naccept"][0] > 0:
+                self.samples = out["X"][0][::-self.nsteps]
+                return
+        print("[proposer] WARNING: MC chain got stuck. Taking random uniform points")
+        self.samples = np.empty((self.nsteps, len(self.bounds)))
+        for i in range(self.nsteps):
+            self.samples[i] = self.random_proposer.get()

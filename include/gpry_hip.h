@@ -152,6 +152,8 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *     "predict_serve" 0/1     mean-only gpry_predict of <= 8 points is answered by a RESIDENT kernel (no launch per call;
  *                             default 1); "serve_idle_us" = how long that kernel waits for the next request before it
  *                             leaves (10 ... 1000000, default 2000)
+ *     "mcmc_mapped" 0/1       gpry_mcmc_chains: 1 = the chains write their outputs straight to mapped pinned host memory; 0
+ *                             (default) = to device memory, copied back once at the end of the call (same bits)
  * The environment variable GPRY_HIP_OPTIONS="key=value,key=value" applies options to every context the process
  * creates (gpry_ctx_create fails on an unknown key or a malformed entry). */
 int gpry_ctx_set_option(gpry_ctx* ctx, const char* key, int64_t value);
@@ -246,6 +248,26 @@ int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t se
 int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv, const double* y_surv,
                        int64_t nsurv, double lstar, const double* W, uint64_t seed, int64_t generation, int k,
                        int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms);
+
+/* ---- Metropolis MCMC of the posterior mean (mcmc.hip; adaptation, R - 1 and weights in gpry_amd/mcmc.py) ---------------
+ * Replaces the point-by-point likelihood calls of the reference's Cobaya MCMC runs: the surrogate's final sample
+ * (gpry/mc.py:173-327), GaussianKL's MC fallback at temperature 2 (gpry/convergence.py:430-476) and SmallChainProposer
+ * (gpry/proposal.py:359-443).  The likelihood is that of the nested sampler above (gpry_predict of one point, bit for bit,
+ * gates included).  gpry_mcmc_chains: `nchains` chains, one workgroup each, make `nsteps` Metropolis steps from the states
+ * X0 (nchains x d) / y0 (nchains; NaN: the start is evaluated first and counted in ncalls).  Unit-cube coordinates
+ * u = (x - lo) / (hi - lo); proposal u' = u + Lp z, Lp: d x d lower triangular, row-major, scale included; z ~ N(0, I) by
+ * Box-Muller.  Step s of chain c draws from the counters (3, j, batch, c, s): j = 0..15 for z, 16 for the acceptance
+ * uniform ua.  A proposal outside the box is rejected unevaluated; otherwise it is accepted iff its y' is finite,
+ * y' > minus_inf_value and log(1 - ua) < (y' - y) / T.  Outputs: the state after every thin-th step (X_rec:
+ * nchains x (nsteps / thin) x d, y_rec: nchains x (nsteps / thin); NULL allowed when nsteps < thin), the final states
+ * X_last / y_last, per-chain accepted steps (naccept) and evaluations (ncalls).  X_prop / y_prop (both NULL, or
+ * nchains x nsteps x d and nchains x nsteps): every proposal and its y, NaN where it was not evaluated -- a test hook,
+ * no memory is set aside for it unless asked.  T > 0; d <= 32; lo < hi.  Stops the resident predict kernel first.
+ * device_ms (nullable): device time of the call, copies included. */
+int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0,
+                     int64_t nchains, const double* Lp, double T, double minus_inf_value, uint64_t seed, int64_t batch,
+                     int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
+                     int64_t* naccept, int64_t* ncalls, double* X_prop, double* y_prop, double* device_ms);
 
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
