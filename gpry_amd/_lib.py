@@ -64,6 +64,10 @@ SIGNATURES = {
     "gpry_ns_prior": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int64, _vp, _vp, _P(C.c_double)]),
     "gpry_ns_generation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64, C.c_int64,
                                      C.c_int, C.c_int, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_ns_generation_clustered": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64,
+                                               C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
+                                               _P(C.c_double)]),
+    "gpry_ns_knn": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _P(C.c_double)]),
     "gpry_mcmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_double, C.c_uint64,
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
@@ -403,20 +407,49 @@ class Device:
                                             C.byref(ms)), "gpry_ns_prior")
         return X, y, ms.value
 
-    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats):
+    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels=None):
         """One generation of ``k`` slice-sampling chains above ``lstar``: ``(X_new (k, d), y_new (k,), ncalls (k,),
-        device_ms)``."""
+        device_ms)``.  ``labels`` (nsurv cluster numbers) with ``W`` of shape (n_clusters, d, d): every chain walks with
+        the matrix of its starting survivor's cluster (gpry_ns_generation_clustered)."""
         lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
         X_surv = _f64(X_surv)
         n = X_surv.shape[0]
         if X_surv.ndim != 2 or X_surv.shape[1] != self.d:
             raise ValueError(f"expected survivors of shape (n, {self.d}), got {X_surv.shape}")
-        y_surv, W = _f64(y_surv, (n,)), _f64(W, (self.d, self.d))
+        y_surv = _f64(y_surv, (n,))
         X_new, y_new, cnt, ms = np.empty((int(k), self.d)), np.empty(int(k)), np.zeros(int(k), np.int64), C.c_double(0.0)
-        self._check(self._lib.gpry_ns_generation(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n, float(lstar),
-                                                 _ptr(W), int(seed), int(generation), int(k), int(num_repeats),
-                                                 _ptr(X_new), _ptr(y_new), _ptr(cnt), C.byref(ms)), "gpry_ns_generation")
+        if labels is None:
+            W = _f64(W, (self.d, self.d))
+            self._check(self._lib.gpry_ns_generation(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
+                                                     float(lstar), _ptr(W), int(seed), int(generation), int(k),
+                                                     int(num_repeats), _ptr(X_new), _ptr(y_new), _ptr(cnt),
+                                                     C.byref(ms)), "gpry_ns_generation")
+            return X_new, y_new, cnt, ms.value
+        W = _f64(W)
+        if W.ndim != 3 or W.shape[1:] != (self.d, self.d):
+            raise ValueError(f"expected W of shape (n_clusters, {self.d}, {self.d}), got {W.shape}")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (n,):
+            raise ValueError(f"expected {n} labels, got shape {lab.shape}")
+        self._check(self._lib.gpry_ns_generation_clustered(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
+                                                           float(lstar), _ptr(W), int(seed), int(generation), int(k),
+                                                           int(num_repeats), _ptr(lab), int(W.shape[0]), _ptr(X_new),
+                                                           _ptr(y_new), _ptr(cnt), C.byref(ms)),
+                    "gpry_ns_generation_clustered")
         return X_new, y_new, cnt, ms.value
+
+    def ns_knn(self, lo, hi, X, k):
+        """The ``k`` nearest other points of every row of ``X`` in unit-cube coordinates, in order of (squared distance,
+        index): ``(nbr (n, k) int32, device_ms)`` (gpry_ns_knn)."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X = _f64(X)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError(f"expected points of shape (n, {self.d}), got {X.shape}")
+        n, k = X.shape[0], int(k)
+        nbr, ms = np.empty((n, max(k, 0)), np.int32), C.c_double(0.0)
+        self._check(self._lib.gpry_ns_knn(self._h, _ptr(lo), _ptr(hi), _ptr(X), n, k, _ptr(nbr), C.byref(ms)),
+                    "gpry_ns_knn")
+        return nbr, ms.value
 
     # -- Metropolis MCMC of the mean (gpry_amd/mcmc.py drives this one) ---------------------
     def mcmc_chains(self, lo, hi, X0, y0, Lp, T, minus_inf_value, seed, batch, nsteps, thin, proposals=False):

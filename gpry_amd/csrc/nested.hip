@@ -17,6 +17,12 @@
 // Chains.  One 256-thread workgroup per chain, the whole walk of `num_repeats` slice-sampling steps (Neal 2003:
 // stepping out, then shrinkage) inside the kernel.  Chains never communicate; the host launches one kernel per
 // generation.
+//
+// Clusters.  gpry_ns_knn tables the k nearest neighbours of every live point (unit-cube coordinates) for the host's
+// clustering rule (nested.py: knn_clusters); gpry_ns_generation_clustered then gives every chain the whitening matrix
+// of its starting survivor's cluster.  Without labels the chain kernel is the unclustered one, bit for bit.
+#include <climits>
+
 #include "ns_common.h"
 
 #define NS_PHASE_PRIOR 0u
@@ -26,6 +32,9 @@
 #define NS_SHRINK_MAX 64
 #define NS_DRAW_OFFSET 16u          // draws 0..15 of a step: the normal vector z (two coordinates per draw)
 #define NS_DRAW_SHRINK 17u          // draws 17..17+63: the shrinkage tries
+#define NS_KNN_MAX_K 32
+#define NS_KNN_MAX_N 65536
+#define NS_KNN_LDS_N 7680           // rows of up to this many points keep their distances in LDS (60 KiB + 3.3 KiB static)
 
 // Prior draws: point i (one workgroup) is lo + u * (hi - lo), u from the counter (PRIOR, draw j, 0, i, 0) for
 // coordinates 2j and 2j + 1, clamped to hi.
@@ -51,14 +60,16 @@ __global__ __launch_bounds__(256) void ns_prior_kernel(NsArgs a, KernParams kp, 
 }
 
 // One generation: chain c starts from a survivor drawn uniformly (counter (START, 0, gen, c, 0)) and makes
-// `num_repeats` slice-sampling steps on {x in the box : y(x) > lstar}.  Step s: direction v = W z / |z|, z ~ N(0, I) by
+// `num_repeats` slice-sampling steps on {x in the box : y(x) > lstar}.  Step s: direction v = W z / |z| (with labels: W of
+// the start's cluster, W + labels[j] d d), z ~ N(0, I) by
 // Box-Muller from draws 0..(d-1)/2; the interval [-r, 1 - r] along v (r: draw 16) stepped out by whole widths, at most
 // 32 per side; then up to 64 shrinkage tries (draws 17..), each uniform on the interval.  A step that hits a cap keeps
 // the current point.  Outputs: the chain's last point, its y and the number of evaluations it made.
 template <int DP, int KID>
 __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, AffParams ap,
                                                        const double* __restrict__ X_surv, const double* __restrict__ y_surv,
-                                                       int64_t nsurv, const double* __restrict__ W, double lstar, unsigned gen,
+                                                       int64_t nsurv, const double* __restrict__ W,
+                                                       const int* __restrict__ labels, double lstar, unsigned gen,
                                                        int num_repeats, double* __restrict__ X_new, double* __restrict__ y_new,
                                                        int64_t* __restrict__ ncalls) {
     __shared__ double r2s[MEAN_SLICE_CH];
@@ -73,7 +84,8 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, 
     const NsU2 us = ns_philox(a.seed, NS_PHASE_START, 0u, gen, c, 0u);
     int64_t j = (int64_t)(us.a * (double)nsurv);
     if (j > nsurv - 1) j = nsurv - 1;
-    for (int e = t; e < d * d; e += 256) s_W[e] = W[e];
+    const double* Wc = labels ? W + (int64_t)labels[j] * d * d : W;
+    for (int e = t; e < d * d; e += 256) s_W[e] = Wc[e];
     double y_cur = y_surv[j];
     if (t < d) {
         s_x[t] = X_surv[j * d + t];
@@ -138,6 +150,146 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, 
     if (t == 0) { y_new[c] = y_cur; ncalls[c] = n_eval; }
 }
 
+// ---- k nearest neighbours of the live set ----------------------------------------------------------------------------
+struct NsBox { double lo[GPRY_MAX_DIM], hi[GPRY_MAX_DIM]; };
+
+// u = (x - lo) / (hi - lo) as the chain kernel computes it, stored transposed (UT[k n + i]) so that neighbouring threads
+// read neighbouring points
+__global__ __launch_bounds__(256) void ns_unit_kernel(const double* __restrict__ X, NsBox b, int64_t n, int d,
+                                                      double* __restrict__ UT) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * d) return;
+    const int64_t i = e / d;
+    const int k = (int)(e - i * d);
+    UT[(int64_t)k * n + i] = (X[e] - b.lo[k]) / (b.hi[k] - b.lo[k]);
+}
+
+// squared distance of u_i (in LDS) and u_j: the squares rounded on their own (ns_rn) and added in coordinate order
+__device__ __forceinline__ double ns_knn_d2(const double* __restrict__ UT, int64_t n, int d, const double* ui, int j) {
+    double s = 0.0;
+    for (int k = 0; k < d; k++) {
+        const double df = ui[k] - UT[(int64_t)k * n + j];
+        s = s + ns_rn(df * df);
+    }
+    return s;
+}
+
+// (da, ja) < (db, jb) lexicographically
+__device__ __forceinline__ bool ns_knn_less(double da, int ja, double db, int jb) {
+    return da < db || (da == db && ja < jb);
+}
+
+// Row i (one workgroup): its k nearest other points in order of (distance^2, index).  Round r selects the smallest key
+// strictly above round r - 1's: a strided scan per thread, then a tree in LDS.  CACHE: the row's distances are computed
+// once into LDS (n <= NS_KNN_LDS_N); otherwise every round recomputes them -- the same bits either way.
+template <bool CACHE>
+__global__ __launch_bounds__(256) void ns_knn_kernel(const double* __restrict__ UT, int n, int d, int k,
+                                                     int* __restrict__ nbr) {
+    extern __shared__ double s_dist[];
+    __shared__ double s_ui[GPRY_MAX_DIM];
+    __shared__ double r_d[256];
+    __shared__ int r_j[256];
+    const int t = threadIdx.x;
+    const int i = blockIdx.x;
+    if (t < d) s_ui[t] = UT[(int64_t)t * n + i];
+    __syncthreads();
+    if (CACHE) {
+        for (int j = t; j < n; j += 256) s_dist[j] = ns_knn_d2(UT, n, d, s_ui, j);
+        __syncthreads();
+    }
+    double last_d = -1.0;           // every distance is >= 0: the first round takes the smallest key
+    int last_j = -1;
+    for (int r = 0; r < k; r++) {
+        double bd = INFINITY;
+        int bj = INT_MAX;
+        for (int j = t; j < n; j += 256) {
+            if (j == i) continue;
+            const double dj = CACHE ? s_dist[j] : ns_knn_d2(UT, n, d, s_ui, j);
+            if (ns_knn_less(last_d, last_j, dj, j) && ns_knn_less(dj, j, bd, bj)) { bd = dj; bj = j; }
+        }
+        r_d[t] = bd;
+        r_j[t] = bj;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (t < w && ns_knn_less(r_d[t + w], r_j[t + w], r_d[t], r_j[t])) { r_d[t] = r_d[t + w]; r_j[t] = r_j[t + w]; }
+            __syncthreads();
+        }
+        last_d = r_d[0];
+        last_j = r_j[0];
+        if (t == 0) nbr[(int64_t)i * k + r] = last_j;
+        __syncthreads();
+    }
+}
+
+static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, const double* hi, const double* X_surv,
+                              const double* y_surv, int64_t nsurv, double lstar, const double* W, const int32_t* labels,
+                              int n_clusters, uint64_t seed, int64_t generation, int k, int num_repeats, double* X_new,
+                              double* y_new, int64_t* ncalls, double* device_ms) {
+    if (!lo || !hi || !X_surv || !y_surv || !W || !X_new || !y_new || !ncalls)
+        return gpry_fail(ctx, -1, "%s: NULL argument", who);
+    if (nsurv < 1 || k < 0 || num_repeats < 0 || generation < 0 || generation > 0xffffffffll)
+        return gpry_fail(ctx, -1, "%s: nsurv = %lld, k = %d, num_repeats = %d, generation = %lld", who,
+                         (long long)nsurv, k, num_repeats, (long long)generation);
+    if (labels) {
+        if (n_clusters < 1 || n_clusters > nsurv)
+            return gpry_fail(ctx, -1, "%s: n_clusters = %d for %lld survivors", who, n_clusters, (long long)nsurv);
+        for (int64_t i = 0; i < nsurv; i++)
+            if (labels[i] < 0 || labels[i] >= n_clusters)
+                return gpry_fail(ctx, -1, "%s: labels[%lld] = %d outside 0 .. %d", who, (long long)i, (int)labels[i],
+                                 n_clusters - 1);
+    }
+    GPRY_TRY(require_model(ctx, true));
+    NsArgs a; KernParams kp; AffParams ap;
+    GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
+    const int d = ctx->d;
+    const int64_t nw = labels ? n_clusters : 1;
+    // one pinned, mapped buffer: [survivors | their y | W | labels | new points | their y | counts]
+    const int64_t bx = round_up(sizeof(double) * nsurv * d, 256), by = round_up(sizeof(double) * nsurv, 256),
+                  bw = round_up(sizeof(double) * nw * d * d, 256),
+                  bl = labels ? round_up(sizeof(int32_t) * nsurv, 256) : 0,
+                  bn = round_up(sizeof(double) * (int64_t)k * d, 256), bny = round_up(sizeof(double) * (int64_t)k, 256),
+                  bc = round_up(sizeof(int64_t) * (int64_t)k, 256);
+    GPRY_TRY(ensure_pinned(ctx, bx + by + bw + bl + bn + bny + bc));
+    char* h = (char*)ctx->hpin;
+    char* hd = (char*)ctx->hpin_dev;
+    memcpy(h, X_surv, sizeof(double) * nsurv * d);
+    memcpy(h + bx, y_surv, sizeof(double) * nsurv);
+    memcpy(h + bx + by, W, sizeof(double) * nw * d * d);
+    if (labels) memcpy(h + bx + by + bw, labels, sizeof(int32_t) * nsurv);
+    const double* dXs_ = (const double*)hd;
+    const double* dys_ = (const double*)(hd + bx);
+    const double* dW = (const double*)(hd + bx + by);
+    const int* dlab = labels ? (const int*)(hd + bx + by + bw) : nullptr;
+    const int64_t on = bx + by + bw + bl;
+    double* dXn = (double*)(hd + on);
+    double* dyn = (double*)(hd + on + bn);
+    int64_t* dcn = (int64_t*)(hd + on + bn + bny);
+    NsTimer tm;
+    GPRY_TRY(ns_begin(ctx, &tm));
+    if (k > 0) {
+#define NC(DP, KID) hipLaunchKernelGGL((ns_chain_kernel<DP, KID>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, ap, \
+                                       dXs_, dys_, nsurv, dW, dlab, lstar, (unsigned)generation, num_repeats, dXn, dyn, dcn)
+#define NC_4(KID) NC(4, KID)
+#define NC_8(KID) NC(8, KID)
+#define NC_16(KID) NC(16, KID)
+#define NC_32(KID) NC(32, KID)
+        if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NC_4) }
+        else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NC_8) }
+        else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NC_16) }
+        else { DISPATCH_KID(ctx->kernel_id, NC_32) }
+#undef NC_4
+#undef NC_8
+#undef NC_16
+#undef NC_32
+#undef NC
+    }
+    GPRY_TRY(ns_end(ctx, &tm, device_ms));
+    memcpy(X_new, h + on, sizeof(double) * (int64_t)k * d);
+    memcpy(y_new, h + on + bn, sizeof(double) * (int64_t)k);
+    memcpy(ncalls, h + on + bn + bny, sizeof(int64_t) * (int64_t)k);
+    return 0;
+}
+
 extern "C" {
 
 int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t seed, int64_t n, double* X_out,
@@ -184,54 +336,65 @@ int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const 
                        int64_t nsurv, double lstar, const double* W, uint64_t seed, int64_t generation, int k,
                        int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation: ctx is NULL");
-    if (!lo || !hi || !X_surv || !y_surv || !W || !X_new || !y_new || !ncalls)
-        return gpry_fail(ctx, -1, "gpry_ns_generation: NULL argument");
-    if (nsurv < 1 || k < 0 || num_repeats < 0 || generation < 0 || generation > 0xffffffffll)
-        return gpry_fail(ctx, -1, "gpry_ns_generation: nsurv = %lld, k = %d, num_repeats = %d, generation = %lld",
-                         (long long)nsurv, k, num_repeats, (long long)generation);
-    GPRY_TRY(require_model(ctx, true));
-    NsArgs a; KernParams kp; AffParams ap;
-    GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
+    return ns_generation_impl(ctx, "gpry_ns_generation", lo, hi, X_surv, y_surv, nsurv, lstar, W, nullptr, 1, seed,
+                              generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+}
+
+int gpry_ns_generation_clustered(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
+                                 const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                                 int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
+                                 double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_clustered: ctx is NULL");
+    if (!labels) return gpry_fail(ctx, -1, "gpry_ns_generation_clustered: NULL argument");
+    return ns_generation_impl(ctx, "gpry_ns_generation_clustered", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
+                              n_clusters, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+}
+
+int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double* X, int64_t n, int k, int32_t* nbr_out,
+                double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_knn: ctx is NULL");
+    if (!lo || !hi || !X || !nbr_out) return gpry_fail(ctx, -1, "gpry_ns_knn: NULL argument");
     const int d = ctx->d;
-    // one pinned, mapped buffer: [survivors | their y | W | new points | their y | counts]
-    const int64_t bx = round_up(sizeof(double) * nsurv * d, 256), by = round_up(sizeof(double) * nsurv, 256),
-                  bw = round_up(sizeof(double) * d * d, 256), bn = round_up(sizeof(double) * (int64_t)k * d, 256),
-                  bny = round_up(sizeof(double) * (int64_t)k, 256), bc = round_up(sizeof(int64_t) * (int64_t)k, 256);
-    GPRY_TRY(ensure_pinned(ctx, bx + by + bw + bn + bny + bc));
-    char* h = (char*)ctx->hpin;
-    char* hd = (char*)ctx->hpin_dev;
-    memcpy(h, X_surv, sizeof(double) * nsurv * d);
-    memcpy(h + bx, y_surv, sizeof(double) * nsurv);
-    memcpy(h + bx + by, W, sizeof(double) * d * d);
-    const double* dXs_ = (const double*)hd;
-    const double* dys_ = (const double*)(hd + bx);
-    const double* dW = (const double*)(hd + bx + by);
-    double* dXn = (double*)(hd + bx + by + bw);
-    double* dyn = (double*)(hd + bx + by + bw + bn);
-    int64_t* dcn = (int64_t*)(hd + bx + by + bw + bn + bny);
+    if (d < 1 || d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "gpry_ns_knn: d = %d outside 1 .. %d", d, GPRY_MAX_DIM);
+    if (k < 1 || k > NS_KNN_MAX_K) return gpry_fail(ctx, -1, "gpry_ns_knn: k = %d outside 1 .. %d", k, NS_KNN_MAX_K);
+    if (n < (int64_t)k + 1 || n > NS_KNN_MAX_N)
+        return gpry_fail(ctx, -1, "gpry_ns_knn: n = %lld outside k + 1 = %d .. %d", (long long)n, k + 1, NS_KNN_MAX_N);
+    NsBox b;
+    for (int c = 0; c < GPRY_MAX_DIM; c++) {
+        b.lo[c] = c < d ? lo[c] : 0.0;
+        b.hi[c] = c < d ? hi[c] : 1.0;
+        if (c < d && !(lo[c] < hi[c]) )
+            return gpry_fail(ctx, -1, "gpry_ns_knn: bounds of dimension %d are [%g, %g]", c, lo[c], hi[c]);
+    }
+    // a non-finite coordinate would make the order undefined: refuse it rather than return a table
+    for (int64_t e = 0; e < n * d; e++) {
+        const int c = (int)(e % d);
+        if (!isfinite((X[e] - b.lo[c]) / (b.hi[c] - b.lo[c])))
+            return gpry_fail(ctx, -1, "gpry_ns_knn: point %lld has a non-finite unit-cube coordinate %d", (long long)(e / d), c);
+    }
+    const int64_t bu = round_up(sizeof(double) * n * d, 256), bx = round_up(sizeof(double) * n * d, 256),
+                  bn = round_up(sizeof(int32_t) * n * k, 256);
+    if (bu + bx + bn > ctx->knn_cap) {
+        if (ctx->dknn) HIP_TRY(ctx, hipFree(ctx->dknn));
+        ctx->dknn = nullptr; ctx->knn_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->dknn, (size_t)(bu + bx + bn)));
+        ctx->knn_cap = bu + bx + bn;
+    }
+    double* dUT = (double*)ctx->dknn;
+    double* dX = (double*)(ctx->dknn + bu);
+    int* dnbr = (int*)(ctx->dknn + bu + bx);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    if (k > 0) {
-#define NC(DP, KID) hipLaunchKernelGGL((ns_chain_kernel<DP, KID>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, ap, \
-                                       dXs_, dys_, nsurv, dW, lstar, (unsigned)generation, num_repeats, dXn, dyn, dcn)
-#define NC_4(KID) NC(4, KID)
-#define NC_8(KID) NC(8, KID)
-#define NC_16(KID) NC(16, KID)
-#define NC_32(KID) NC(32, KID)
-        if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NC_4) }
-        else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NC_8) }
-        else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NC_16) }
-        else { DISPATCH_KID(ctx->kernel_id, NC_32) }
-#undef NC_4
-#undef NC_8
-#undef NC_16
-#undef NC_32
-#undef NC
-    }
+    HIP_TRY(ctx, hipMemcpyAsync(dX, X, sizeof(double) * n * d, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(ns_unit_kernel, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, ctx->stream, dX, b, n, d, dUT);
+    if (n <= NS_KNN_LDS_N)
+        hipLaunchKernelGGL(ns_knn_kernel<true>, dim3((unsigned)n), dim3(256), sizeof(double) * n, ctx->stream, dUT, (int)n,
+                           d, k, dnbr);
+    else
+        hipLaunchKernelGGL(ns_knn_kernel<false>, dim3((unsigned)n), dim3(256), 0, ctx->stream, dUT, (int)n, d, k, dnbr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(nbr_out, dnbr, sizeof(int32_t) * n * k, hipMemcpyDeviceToHost, ctx->stream));
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    memcpy(X_new, h + bx + by + bw, sizeof(double) * (int64_t)k * d);
-    memcpy(y_new, h + bx + by + bw + bn, sizeof(double) * (int64_t)k);
-    memcpy(ncalls, h + bx + by + bw + bn + bny, sizeof(int64_t) * (int64_t)k);
     return 0;
 }
 

@@ -309,7 +309,9 @@ class NORA(GenericGPAcquisition):
     ``sampler="nested"``: the package's own nested sampler of the surrogate's mean, on the device (``gpry_amd/nested.py``),
     with the settings of ``update_NS_precision``; ``nested_batch``: its chains per generation (default nlive / 2).  The
     pool's y is ``gpr.predict`` bit for bit and goes to the sweep as given; ``acq.stats["sampler_info"]`` holds logZ, its
-    error, the evaluations, the generations and the device time.
+    error, the evaluations, the generations and the device time.  ``nested_clustering=True``: the sampler clusters its
+    live set and gives each cluster's chains their own whitening matrix (``gpry_amd.nested.knn_clusters``); the largest
+    cluster count of the run is ``sampler_info["clusters"]``.
     """
 
     def __init__(self, bounds, preprocessing_X=None, verbose=1, acq_func="LogExp", sampler=None,
@@ -317,7 +319,7 @@ class NORA(GenericGPAcquisition):
                  num_repeats="5d", num_repeats_per_dim=None, precision_criterion_target=0.01,
                  nprior_per_nlive=10, max_ncalls=None, tmpdir=None, comm=None,
                  shortlist_size=None, gather_y="auto", devices=None, exact_prune=True,
-                 nested_batch=None):
+                 nested_batch=None, nested_clustering=False):
         super().__init__(bounds=np.asarray(bounds), preprocessing_X=preprocessing_X,
                          verbose=verbose, acq_func=acq_func)
         self.log_header = f"[ACQUISITION : {self.__class__.__name__}] "
@@ -354,6 +356,8 @@ class NORA(GenericGPAcquisition):
         self.exact_prune = bool(exact_prune)
         # chains per generation of sampler="nested" (None: gpry_amd.nested.default_batch)
         self.nested_batch = nested_batch
+        # a whitening matrix per cluster of the live set in sampler="nested" (gpry_amd.nested.knn_clusters)
+        self.nested_clustering = bool(nested_clustering)
         self._X_already_proposed = np.empty((0, self.n_d))
         self.stats = {}
 
@@ -416,12 +420,19 @@ class NORA(GenericGPAcquisition):
         res = run_nested(gpr.device, b, seed, prec["nlive"], prec["num_repeats"],
                          precision_criterion=prec["precision_criterion"], nprior=prec["nprior"],
                          max_ncalls=prec["max_ncalls"], batch=self.nested_batch,
-                         minus_inf_value=gpr.minus_inf_value)
+                         minus_inf_value=gpr.minus_inf_value, **self._clustering_kw())
         gpr.n_eval += res.ncalls
         self.stats["sampler_info"] = {"logZ": res.logZ, "logZ_err": res.logZ_err, "ncalls": res.ncalls,
                                       "generations": res.ngen, "device_s": res.device_s, "wall_s": res.wall_s,
                                       "seed": seed, "nlive": prec["nlive"], "rows": len(res.y)}
+        if self.nested_clustering:
+            nc = res.n_clusters
+            self.stats["sampler_info"]["clusters"] = int(np.max(nc)) if nc is not None and len(nc) else 1
         return res.X, res.y, None, res.w
+
+    def _clustering_kw(self):
+        """run_nested's clustering argument: passed only when on, so that the run's calls are those of before without."""
+        return {"clustering": True} if self.nested_clustering else {}
 
     def _do_MC_sample_uniform(self, gpr, bounds=None, rng=None):
         """1000 d points drawn one at a time, as gp_acquisition.py:750-758 does."""

@@ -15,6 +15,10 @@ from gpry_amd.tools import generic_params_names, get_Xnumber
 
 # PolyChord's defaults (the Runner passes nlive = 50d)
 NESTED_DEFAULTS = {"nlive": "25d", "num_repeats": "5d", "precision_criterion": 0.001, "nprior": None, "max_ncalls": None}
+# options of the device nested sampler beyond PolyChord's settings: in nested_settings' result only when given
+NESTED_EXTRA = {"clustering": False}
+# PolyChord's names of those options -> ours, for the warning that ignores them
+NESTED_RENAMED = {"do_clustering": "clustering"}
 # Cobaya's names where they exist -> run_mcmc's arguments
 MCMC_KEYS = {"Rminus1_stop": "Rminus1_stop", "temperature": "temperature", "covmat": "covmat",
              "max_samples": "max_ncalls", "max_ncalls": "max_ncalls", "nchains": "nchains", "learn_every": "learn_every",
@@ -22,26 +26,29 @@ MCMC_KEYS = {"Rminus1_stop": "Rminus1_stop", "temperature": "temperature", "covm
              "thin": "thin", "skip": "skip", "reset_temperature": "reset_temperature"}
 
 
-def _known(options, keys, sampler):
+def _known(options, keys, sampler, renamed=None):
     """The entries of ``options`` whose key is in ``keys``; a warning for the rest (gpry/ns_interfaces.py:160-170)."""
     options = dict(options or {})
     unknown = [k for k in options if k not in keys]
     if unknown:
+        hint = "".join(f" Use '{renamed[k]}' for '{k}'." for k in unknown if renamed and k in renamed)
         warnings.warn(f"Options {unknown} not recognised by the device sampler '{sampler}'; they are ignored. "
-                      f"Known: {sorted(keys)}")
+                      f"Known: {sorted(keys)}.{hint}")
     return {k: v for k, v in options.items() if k in keys}
 
 
 def nested_settings(d, sampler_options=None):
     """run_nested's settings from PolyChord-style options; Xnumber strings such as ``"50d"`` are multiples of d."""
     opts = dict(NESTED_DEFAULTS)
-    opts.update(_known(sampler_options, NESTED_DEFAULTS, "nested"))
+    opts.update(_known(sampler_options, {**NESTED_DEFAULTS, **NESTED_EXTRA}, "nested", NESTED_RENAMED))
     out = {}
     for k in ("nlive", "num_repeats"):
         out[k] = get_Xnumber(opts[k], "d", d, int, k)
     out["precision_criterion"] = float(opts["precision_criterion"])
     out["nprior"] = out["nlive"] if opts["nprior"] is None else get_Xnumber(opts["nprior"], "d", d, int, "nprior")
     out["max_ncalls"] = None if opts["max_ncalls"] is None else get_Xnumber(opts["max_ncalls"], "d", d, int, "max_ncalls")
+    if "clustering" in opts:
+        out["clustering"] = bool(opts["clustering"])
     return out
 
 
@@ -90,7 +97,8 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     """Monte Carlo sample of the surrogate's posterior mean, on the device: ``(X, y, w)``, w normalised.
 
     bounds: default ``gpr.trust_bounds``, else ``gpr.bounds`` (gpry/mc.py:381-382).  sampler: ``"nested"`` (options
-    nlive, num_repeats, precision_criterion, nprior, max_ncalls; PolyChord's defaults 25d, 5d, 0.001, nlive) or
+    nlive, num_repeats, precision_criterion, nprior, max_ncalls; PolyChord's defaults 25d, 5d, 0.001, nlive; and
+    clustering, default False: a whitening matrix per cluster of the live set) or
     ``"mcmc"`` (options Rminus1_stop, temperature, covmat, max_samples -> max_ncalls, and run_mcmc's nchains,
     learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature).  Unknown options are warned
     about and ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.  The
@@ -108,7 +116,8 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
         s = nested_settings(d, sampler_options)
         _push_model(gpr, sampler)
         res = run_nested(gpr.device, b, seed, s["nlive"], s["num_repeats"], precision_criterion=s["precision_criterion"],
-                         nprior=s["nprior"], max_ncalls=s["max_ncalls"], minus_inf_value=gpr.minus_inf_value)
+                         nprior=s["nprior"], max_ncalls=s["max_ncalls"], minus_inf_value=gpr.minus_inf_value,
+                         **({"clustering": True} if s.get("clustering") else {}))
     else:
         from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
         s = mcmc_settings(d, sampler_options)

@@ -11,6 +11,9 @@ for it (the CPU tests use a numpy one):
 ``dev.ns_generation(lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats)
     -> (X_new (k, d), y_new (k,), ncalls (k,), device_ms)``
 
+With ``clustering=True`` it also calls ``dev.ns_knn(lo, hi, X, k) -> (nbr (n, k), device_ms)`` and passes
+``labels=`` (with one W per cluster) to ``ns_generation``.
+
 The algorithm, step by step:
 
 * The sampler works in the unit cube u = (x - lo) / (hi - lo); the prior is uniform on the box.
@@ -19,6 +22,11 @@ The algorithm, step by step:
 * Generation: the live set sorted by (y, index), the ``batch`` lowest become dead points in ascending order, L* is the
   largest y among them, and as many chains, each started from a uniformly drawn survivor, produce one new live point
   above L*.  Every removal with n live points before it shrinks the log prior volume by log(n / (n + 1)).
+* Clustering (opt-in): after the kill, the survivors' k-nearest-neighbour table (device) is cut into clusters by
+  ``knn_clusters``, each cluster gets the whitening matrix of its own points, and every chain walks with the matrix of
+  the cluster its start belongs to.  Starts, kills and volumes are those of the unclustered run, so a cluster receives
+  new points in proportion to its live count and logZ and the weights keep their meaning.  Not done: PolyChord's
+  per-cluster volumes and local evidences, and the choice of a cluster in proportion to its volume.
 * Stop when Z_live / Z < ``precision_criterion`` (Z_live = X mean(L_live), the PolyChord criterion) or, at the end of
   a generation, when the evaluation count has reached ``max_ncalls``.  The final live points get the volume X / n each.
 """
@@ -28,14 +36,18 @@ from time import time
 import numpy as np
 
 NestedResult = namedtuple("NestedResult", ["X", "y", "w", "logZ", "logZ_err", "ncalls", "ngen", "device_s",
-                                           "wall_s", "dead_L", "dead_logX", "n_dead"])
+                                           "wall_s", "dead_L", "dead_logX", "n_dead", "n_clusters"],
+                          defaults=(None,))
 NestedResult.__doc__ = """Output of ``run_nested``.  X, y, w: rows with a finite likelihood, dead points in the order they
 died then the final live points; w sums to 1.  logZ and its error sqrt(H / nlive); ncalls: evaluations of the surrogate;
 ngen: generations; device_s / wall_s: time in the device calls / in the whole run.  dead_L / dead_logX: log-likelihood
-(-inf outside) and log prior volume after each removal, outside points included; n_dead: their count."""
+(-inf outside) and log prior volume after each removal, outside points included; n_dead: their count.  n_clusters: the
+cluster count of each generation (an int array) with clustering on, None without."""
 
 # a run stops after this many generations whatever its other criteria say (a safeguard, never met in practice)
 MAX_GENERATIONS = 100000
+# largest neighbour count the clustering rule tries (profiles/nested_clusters.md)
+DEFAULT_CLUSTER_K_MAX = 10
 
 
 def default_batch(nlive):
@@ -66,6 +78,53 @@ def cholesky_ridged(C):
     return np.ascontiguousarray(np.sqrt(scale) * np.eye(d))
 
 
+def _components(n, a, b):
+    """Connected components of the graph on 0 .. n-1 with the edges a[e]-b[e]: each point's smallest component member.
+    Union-find with the roots as the smaller index, vectorised: every edge hooks the larger of its two roots onto the
+    smaller, then the paths are compressed, until both ends of every edge share a root."""
+    parent = np.arange(n)
+    while True:
+        ra, rb = parent[a], parent[b]
+        if np.array_equal(ra, rb):
+            return parent
+        np.minimum.at(parent, np.maximum(ra, rb), np.minimum(ra, rb))
+        while True:
+            pp = parent[parent]
+            if np.array_equal(pp, parent):
+                break
+            parent = pp
+
+
+def knn_clusters(nbr, d, k_max, min_size=None):
+    """Clusters of a live set from its neighbour table ``nbr`` (n, >= k_max; row i: i's nearest other points, nearest
+    first): ``(labels (n,) int32, n_clusters)``.
+
+    For k = 2 .. k_max: the undirected graph with an edge i-j when j is among the first k neighbours of i or i among
+    those of j, and its connected components, numbered by their smallest member.  The partition is the first one at a
+    k >= 3 that equals the one at k - 1; a single component ends the search at once.  If no partition is stable up to
+    k_max, or a cluster has fewer than ``min_size`` points (default d + 1: too few for a covariance), it is one cluster.
+    After PolyChord's KNN clustering (Handley et al. 2015), without claiming to be it bit for bit."""
+    nbr = np.asarray(nbr)
+    n = nbr.shape[0]
+    one = (np.zeros(n, np.int32), 1)
+    k_max = min(int(k_max), nbr.shape[1] if nbr.ndim == 2 else 0)
+    min_size = int(d) + 1 if min_size is None else int(min_size)
+    prev = None
+    for k in range(2, k_max + 1):
+        a = np.repeat(np.arange(n), k)
+        roots = _components(n, a, nbr[:, :k].reshape(-1).astype(np.int64))
+        _, labels = np.unique(roots, return_inverse=True)
+        if labels.max() == 0:
+            return one
+        if prev is not None and np.array_equal(labels, prev):
+            counts = np.bincount(labels)
+            if counts.min() < min_size:
+                return one
+            return labels.astype(np.int32), len(counts)
+        prev = labels
+    return one
+
+
 def _logL(y, minus_inf_value):
     L = np.asarray(y, dtype=float).copy()
     if np.isfinite(minus_inf_value):
@@ -84,8 +143,10 @@ def _logsumexp(a):
 
 
 def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, nprior=None, max_ncalls=None,
-               batch=None, minus_inf_value=-np.inf):
-    """Nested sampling run of the surrogate on ``dev``; see the module's docstring.  Returns a ``NestedResult``."""
+               batch=None, minus_inf_value=-np.inf, clustering=False, cluster_k_max=None):
+    """Nested sampling run of the surrogate on ``dev``; see the module's docstring.  Returns a ``NestedResult``.
+    ``clustering``: a whitening matrix per cluster of the survivors (``knn_clusters`` with neighbour tables of up to
+    ``cluster_k_max`` points, default ``DEFAULT_CLUSTER_K_MAX``)."""
     t_start = time()
     bounds = np.asarray(bounds, dtype=float)
     lo, hi = np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
@@ -98,6 +159,11 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
         raise ValueError(f"batch = {k_gen} must lie in 1 .. nlive - 1 = {nlive - 1}")
     num_repeats = int(num_repeats)
     seed = int(seed)
+    clustering = bool(clustering)
+    k_max = DEFAULT_CLUSTER_K_MAX if cluster_k_max is None else int(cluster_k_max)
+    if clustering and not 2 <= k_max <= 32:
+        raise ValueError(f"cluster_k_max = {k_max} must lie in 2 .. 32")
+    n_clusters = []
     device_ms = 0.0
     # ---- prior
     X, y, ms = dev.ns_prior(lo, hi, seed, nprior)
@@ -145,10 +211,22 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
         lstar = float(L[rem[-1]])
         logX = kill(rem, X, y, L, logX)
         Xs, ys = np.ascontiguousarray(X[keep]), np.ascontiguousarray(y[keep])
-        W = whitening((Xs - lo) / (hi - lo))
+        Us = (Xs - lo) / (hi - lo)
         # an outside point is never accepted: with a finite minus_inf_value the threshold is at least that value
         thr = lstar if not np.isfinite(minus_inf_value) else max(lstar, float(minus_inf_value))
-        Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats)
+        if not clustering:
+            W = whitening(Us)
+            Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats)
+        else:
+            if len(Xs) >= 3:
+                nbr, ms = dev.ns_knn(lo, hi, Xs, min(k_max, len(Xs) - 1))
+                device_ms += ms
+                labels, nc = knn_clusters(nbr, Xs.shape[1], k_max)
+            else:
+                labels, nc = np.zeros(len(Xs), np.int32), 1
+            W = np.stack([whitening(Us[labels == q]) for q in range(nc)])
+            n_clusters.append(nc)
+            Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats, labels=labels)
         device_ms += ms
         ncalls += int(np.sum(cnt))
         X = np.concatenate([Xs, Xn])
@@ -175,4 +253,5 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
                         device_s=device_ms / 1e3, wall_s=time() - t_start,
                         dead_L=np.concatenate(dead_L) if dead_L else np.empty(0),
                         dead_logX=np.concatenate(dead_logX) if dead_logX else np.empty(0),
-                        n_dead=int(sum(len(a) for a in dead_y)))
+                        n_dead=int(sum(len(a) for a in dead_y)),
+                        n_clusters=np.array(n_clusters, dtype=np.int64) if clustering else None)

@@ -248,6 +248,22 @@ int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t se
 int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv, const double* y_surv,
                        int64_t nsurv, double lstar, const double* W, uint64_t seed, int64_t generation, int k,
                        int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms);
+/* gpry_ns_generation_clustered: gpry_ns_generation with one whitening matrix per cluster of the survivors.  W:
+ *   n_clusters x d x d, row-major; labels: nsurv cluster numbers in 0 .. n_clusters - 1.  Chain c draws its starting
+ *   survivor j as gpry_ns_generation does and walks with W + labels[j] d d; nothing else changes, so chain c equals, bit
+ *   for bit, chain c of gpry_ns_generation called with that matrix.  (The clustering rule: gpry_amd/nested.py.) */
+int gpry_ns_generation_clustered(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
+                                 const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                                 int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
+                                 double* X_new, double* y_new, int64_t* ncalls, double* device_ms);
+/* gpry_ns_knn: the k nearest other points of each of the n points X (n x d) in unit-cube coordinates
+ *   u = (x - lo) / (hi - lo): nbr_out (n x k, row-major) holds row i's neighbours in order of (squared distance, index),
+ *   i itself excluded, ties (duplicated points) broken by the index.  The squared distance is the sum over the
+ *   coordinates, in their order, of the rounded squares (u_i - u_j)^2 -- a numpy restatement gives the same table.
+ *   1 <= k <= 32, k + 1 <= n <= 65536; a non-finite u is refused.  Needs no model.  device_ms (nullable): device time of
+ *   the call, copies included. */
+int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double* X, int64_t n, int k, int32_t* nbr_out,
+                double* device_ms);
 
 /* ---- Metropolis MCMC of the posterior mean (mcmc.hip; adaptation, R - 1 and weights in gpry_amd/mcmc.py) ---------------
  * Replaces the point-by-point likelihood calls of the reference's Cobaya MCMC runs: the surrogate's final sample
