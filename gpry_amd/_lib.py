@@ -67,6 +67,9 @@ SIGNATURES = {
     "gpry_ns_generation_clustered": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64,
                                                C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
                                                _P(C.c_double)]),
+    "gpry_ns_generation_volumes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64,
+                                             C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                                             _P(C.c_double)]),
     "gpry_ns_knn": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _P(C.c_double)]),
     "gpry_mcmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_double, C.c_uint64,
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
@@ -407,10 +410,15 @@ class Device:
                                             C.byref(ms)), "gpry_ns_prior")
         return X, y, ms.value
 
-    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels=None):
+    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels=None,
+                      cum_p=None):
         """One generation of ``k`` slice-sampling chains above ``lstar``: ``(X_new (k, d), y_new (k,), ncalls (k,),
         device_ms)``.  ``labels`` (nsurv cluster numbers) with ``W`` of shape (n_clusters, d, d): every chain walks with
-        the matrix of its starting survivor's cluster (gpry_ns_generation_clustered)."""
+        the matrix of its starting survivor's cluster (gpry_ns_generation_clustered).  With ``cum_p`` (n_clusters
+        cumulative probabilities, the last 1.0) as well, every chain first draws its cluster from cum_p and then its
+        start among that cluster's survivors (gpry_ns_generation_volumes)."""
+        if cum_p is not None and labels is None:
+            raise ValueError("cum_p needs labels")
         lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
         X_surv = _f64(X_surv)
         n = X_surv.shape[0]
@@ -431,6 +439,14 @@ class Device:
         lab = np.ascontiguousarray(labels, dtype=np.int32)
         if lab.shape != (n,):
             raise ValueError(f"expected {n} labels, got shape {lab.shape}")
+        if cum_p is not None:
+            cp = _f64(cum_p, (W.shape[0],))
+            self._check(self._lib.gpry_ns_generation_volumes(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
+                                                             float(lstar), _ptr(W), int(seed), int(generation), int(k),
+                                                             int(num_repeats), _ptr(lab), int(W.shape[0]), _ptr(cp),
+                                                             _ptr(X_new), _ptr(y_new), _ptr(cnt), C.byref(ms)),
+                        "gpry_ns_generation_volumes")
+            return X_new, y_new, cnt, ms.value
         self._check(self._lib.gpry_ns_generation_clustered(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
                                                            float(lstar), _ptr(W), int(seed), int(generation), int(k),
                                                            int(num_repeats), _ptr(lab), int(W.shape[0]), _ptr(X_new),

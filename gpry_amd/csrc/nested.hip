@@ -21,7 +21,11 @@
 // Clusters.  gpry_ns_knn tables the k nearest neighbours of every live point (unit-cube coordinates) for the host's
 // clustering rule (nested.py: knn_clusters); gpry_ns_generation_clustered then gives every chain the whitening matrix
 // of its starting survivor's cluster.  Without labels the chain kernel is the unclustered one, bit for bit.
+// gpry_ns_generation_volumes lets every chain first draw its cluster from cumulative probabilities (the clusters' prior
+// volumes, PolyChord's choice) and then its start among that cluster's survivors; without a member list the chain
+// kernel draws its start uniformly from all survivors, as before, bit for bit.
 #include <climits>
+#include <vector>
 
 #include "ns_common.h"
 
@@ -65,11 +69,17 @@ __global__ __launch_bounds__(256) void ns_prior_kernel(NsArgs a, KernParams kp, 
 // Box-Muller from draws 0..(d-1)/2; the interval [-r, 1 - r] along v (r: draw 16) stepped out by whole widths, at most
 // 32 per side; then up to 64 shrinkage tries (draws 17..), each uniform on the interval.  A step that hits a cap keeps
 // the current point.  Outputs: the chain's last point, its y and the number of evaluations it made.
+// With a member list (volumes): chain c first draws its cluster q, the first q with u1 < cum_p[q] (u1: counter
+// (START, 1, gen, c, 0)), then its start members[moffs[q] + min(floor(u0 n_q), n_q - 1)] from the same u0 as above
+// (n_q = moffs[q + 1] - moffs[q]), and walks with W + q d d.  The host guarantees cum_p[n_clusters - 1] = 1.0 and
+// n_q >= 1 wherever cum_p rises.
 template <int DP, int KID>
 __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, AffParams ap,
                                                        const double* __restrict__ X_surv, const double* __restrict__ y_surv,
                                                        int64_t nsurv, const double* __restrict__ W,
-                                                       const int* __restrict__ labels, double lstar, unsigned gen,
+                                                       const int* __restrict__ labels, const int* __restrict__ members,
+                                                       const int* __restrict__ moffs, const double* __restrict__ cum_p,
+                                                       int n_clusters, double lstar, unsigned gen,
                                                        int num_repeats, double* __restrict__ X_new, double* __restrict__ y_new,
                                                        int64_t* __restrict__ ncalls) {
     __shared__ double r2s[MEAN_SLICE_CH];
@@ -82,9 +92,22 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, 
     const unsigned c = blockIdx.x;
     // the starting survivor
     const NsU2 us = ns_philox(a.seed, NS_PHASE_START, 0u, gen, c, 0u);
-    int64_t j = (int64_t)(us.a * (double)nsurv);
-    if (j > nsurv - 1) j = nsurv - 1;
-    const double* Wc = labels ? W + (int64_t)labels[j] * d * d : W;
+    int64_t j;
+    const double* Wc = W;
+    if (members) {
+        const double u1 = ns_philox(a.seed, NS_PHASE_START, 1u, gen, c, 0u).a;
+        int q = 0;
+        while (q < n_clusters - 1 && !(u1 < cum_p[q])) q++;
+        const int64_t nq = (int64_t)moffs[q + 1] - moffs[q];
+        int64_t jq = (int64_t)(us.a * (double)nq);
+        if (jq > nq - 1) jq = nq - 1;
+        j = members[moffs[q] + jq];
+        Wc = W + (int64_t)q * d * d;
+    } else {
+        j = (int64_t)(us.a * (double)nsurv);
+        if (j > nsurv - 1) j = nsurv - 1;
+        if (labels) Wc = W + (int64_t)labels[j] * d * d;
+    }
     for (int e = t; e < d * d; e += 256) s_W[e] = Wc[e];
     double y_cur = y_surv[j];
     if (t < d) {
@@ -223,8 +246,8 @@ __global__ __launch_bounds__(256) void ns_knn_kernel(const double* __restrict__ 
 
 static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, const double* hi, const double* X_surv,
                               const double* y_surv, int64_t nsurv, double lstar, const double* W, const int32_t* labels,
-                              int n_clusters, uint64_t seed, int64_t generation, int k, int num_repeats, double* X_new,
-                              double* y_new, int64_t* ncalls, double* device_ms) {
+                              int n_clusters, const double* cum_p, uint64_t seed, int64_t generation, int k,
+                              int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
     if (!lo || !hi || !X_surv || !y_surv || !W || !X_new || !y_new || !ncalls)
         return gpry_fail(ctx, -1, "%s: NULL argument", who);
     if (nsurv < 1 || k < 0 || num_repeats < 0 || generation < 0 || generation > 0xffffffffll)
@@ -238,15 +261,32 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
                 return gpry_fail(ctx, -1, "%s: labels[%lld] = %d outside 0 .. %d", who, (long long)i, (int)labels[i],
                                  n_clusters - 1);
     }
+    if (cum_p) {
+        if (!labels) return gpry_fail(ctx, -1, "%s: cum_p without labels", who);
+        for (int q = 0; q < n_clusters; q++)
+            if (!(cum_p[q] >= (q ? cum_p[q - 1] : 0.0)))
+                return gpry_fail(ctx, -1, "%s: cum_p[%d] = %.17g is not non-decreasing (nor >= 0)", who, q, cum_p[q]);
+        if (cum_p[n_clusters - 1] != 1.0)
+            return gpry_fail(ctx, -1, "%s: cum_p[%d] = %.17g, not 1.0", who, n_clusters - 1, cum_p[n_clusters - 1]);
+        std::vector<int64_t> cnt(n_clusters, 0);
+        for (int64_t i = 0; i < nsurv; i++) cnt[labels[i]]++;
+        for (int q = 0; q < n_clusters; q++)
+            if (cum_p[q] > (q ? cum_p[q - 1] : 0.0) && cnt[q] == 0)
+                return gpry_fail(ctx, -1, "%s: cluster %d has probability %.17g and no survivor", who, q,
+                                 cum_p[q] - (q ? cum_p[q - 1] : 0.0));
+    }
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
     const int d = ctx->d;
     const int64_t nw = labels ? n_clusters : 1;
-    // one pinned, mapped buffer: [survivors | their y | W | labels | new points | their y | counts]
+    // one pinned, mapped buffer: [survivors | their y | W | labels | new points | their y | counts]; with cum_p the
+    // labels' place holds [members | member offsets | cum_p] instead
+    const int64_t bm = round_up(sizeof(int32_t) * nsurv, 256), bo = round_up(sizeof(int32_t) * (n_clusters + 1), 256);
     const int64_t bx = round_up(sizeof(double) * nsurv * d, 256), by = round_up(sizeof(double) * nsurv, 256),
                   bw = round_up(sizeof(double) * nw * d * d, 256),
-                  bl = labels ? round_up(sizeof(int32_t) * nsurv, 256) : 0,
+                  bl = !labels ? 0 : cum_p ? bm + bo + round_up(sizeof(double) * n_clusters, 256)
+                                           : round_up(sizeof(int32_t) * nsurv, 256),
                   bn = round_up(sizeof(double) * (int64_t)k * d, 256), bny = round_up(sizeof(double) * (int64_t)k, 256),
                   bc = round_up(sizeof(int64_t) * (int64_t)k, 256);
     GPRY_TRY(ensure_pinned(ctx, bx + by + bw + bl + bn + bny + bc));
@@ -255,11 +295,30 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
     memcpy(h, X_surv, sizeof(double) * nsurv * d);
     memcpy(h + bx, y_surv, sizeof(double) * nsurv);
     memcpy(h + bx + by, W, sizeof(double) * nw * d * d);
-    if (labels) memcpy(h + bx + by + bw, labels, sizeof(int32_t) * nsurv);
+    const int* dlab = nullptr;
+    const int* dmem = nullptr;
+    const int* dmof = nullptr;
+    const double* dcp = nullptr;
+    if (cum_p) {
+        // each cluster's survivors in their order in X_surv (a counting sort, stable by index)
+        int32_t* mem = (int32_t*)(h + bx + by + bw);
+        int32_t* mof = (int32_t*)(h + bx + by + bw + bm);
+        for (int q = 0; q <= n_clusters; q++) mof[q] = 0;
+        for (int64_t i = 0; i < nsurv; i++) mof[labels[i] + 1]++;
+        for (int q = 0; q < n_clusters; q++) mof[q + 1] += mof[q];
+        std::vector<int32_t> fill(mof, mof + n_clusters);
+        for (int64_t i = 0; i < nsurv; i++) mem[fill[labels[i]]++] = (int32_t)i;
+        memcpy(h + bx + by + bw + bm + bo, cum_p, sizeof(double) * n_clusters);
+        dmem = (const int*)(hd + bx + by + bw);
+        dmof = (const int*)(hd + bx + by + bw + bm);
+        dcp = (const double*)(hd + bx + by + bw + bm + bo);
+    } else if (labels) {
+        memcpy(h + bx + by + bw, labels, sizeof(int32_t) * nsurv);
+        dlab = (const int*)(hd + bx + by + bw);
+    }
     const double* dXs_ = (const double*)hd;
     const double* dys_ = (const double*)(hd + bx);
     const double* dW = (const double*)(hd + bx + by);
-    const int* dlab = labels ? (const int*)(hd + bx + by + bw) : nullptr;
     const int64_t on = bx + by + bw + bl;
     double* dXn = (double*)(hd + on);
     double* dyn = (double*)(hd + on + bn);
@@ -268,7 +327,8 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
     GPRY_TRY(ns_begin(ctx, &tm));
     if (k > 0) {
 #define NC(DP, KID) hipLaunchKernelGGL((ns_chain_kernel<DP, KID>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, ap, \
-                                       dXs_, dys_, nsurv, dW, dlab, lstar, (unsigned)generation, num_repeats, dXn, dyn, dcn)
+                                       dXs_, dys_, nsurv, dW, dlab, dmem, dmof, dcp, (int)nw, lstar, (unsigned)generation, \
+                                       num_repeats, dXn, dyn, dcn)
 #define NC_4(KID) NC(4, KID)
 #define NC_8(KID) NC(8, KID)
 #define NC_16(KID) NC(16, KID)
@@ -336,8 +396,8 @@ int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const 
                        int64_t nsurv, double lstar, const double* W, uint64_t seed, int64_t generation, int k,
                        int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation: ctx is NULL");
-    return ns_generation_impl(ctx, "gpry_ns_generation", lo, hi, X_surv, y_surv, nsurv, lstar, W, nullptr, 1, seed,
-                              generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    return ns_generation_impl(ctx, "gpry_ns_generation", lo, hi, X_surv, y_surv, nsurv, lstar, W, nullptr, 1, nullptr,
+                              seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
 }
 
 int gpry_ns_generation_clustered(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
@@ -347,7 +407,18 @@ int gpry_ns_generation_clustered(gpry_ctx* ctx, const double* lo, const double* 
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_clustered: ctx is NULL");
     if (!labels) return gpry_fail(ctx, -1, "gpry_ns_generation_clustered: NULL argument");
     return ns_generation_impl(ctx, "gpry_ns_generation_clustered", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
-                              n_clusters, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+                              n_clusters, nullptr, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+}
+
+int gpry_ns_generation_volumes(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
+                               const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                               int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
+                               const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_volumes: ctx is NULL");
+    if (!labels || !cum_p) return gpry_fail(ctx, -1, "gpry_ns_generation_volumes: NULL argument");
+    if (nsurv > INT_MAX) return gpry_fail(ctx, -1, "gpry_ns_generation_volumes: nsurv = %lld", (long long)nsurv);
+    return ns_generation_impl(ctx, "gpry_ns_generation_volumes", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
+                              n_clusters, cum_p, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
 }
 
 int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double* X, int64_t n, int k, int32_t* nbr_out,

@@ -311,7 +311,10 @@ class NORA(GenericGPAcquisition):
     pool's y is ``gpr.predict`` bit for bit and goes to the sweep as given; ``acq.stats["sampler_info"]`` holds logZ, its
     error, the evaluations, the generations and the device time.  ``nested_clustering=True``: the sampler clusters its
     live set and gives each cluster's chains their own whitening matrix (``gpry_amd.nested.knn_clusters``); the largest
-    cluster count of the run is ``sampler_info["clusters"]``.
+    cluster count of the run is ``sampler_info["clusters"]``.  ``nested_cluster_volumes=True`` (needs
+    ``nested_clustering``): every cluster keeps its own prior volume and local evidence, and chains start in a cluster
+    drawn by volume (PolyChord's bookkeeping); ``sampler_info["cluster_logZ"]`` and ``["cluster_parent"]`` map each cluster
+    id to its local evidence and its parent id (-1: the root).
     """
 
     def __init__(self, bounds, preprocessing_X=None, verbose=1, acq_func="LogExp", sampler=None,
@@ -319,7 +322,7 @@ class NORA(GenericGPAcquisition):
                  num_repeats="5d", num_repeats_per_dim=None, precision_criterion_target=0.01,
                  nprior_per_nlive=10, max_ncalls=None, tmpdir=None, comm=None,
                  shortlist_size=None, gather_y="auto", devices=None, exact_prune=True,
-                 nested_batch=None, nested_clustering=False):
+                 nested_batch=None, nested_clustering=False, nested_cluster_volumes=False):
         super().__init__(bounds=np.asarray(bounds), preprocessing_X=preprocessing_X,
                          verbose=verbose, acq_func=acq_func)
         self.log_header = f"[ACQUISITION : {self.__class__.__name__}] "
@@ -358,6 +361,10 @@ class NORA(GenericGPAcquisition):
         self.nested_batch = nested_batch
         # a whitening matrix per cluster of the live set in sampler="nested" (gpry_amd.nested.knn_clusters)
         self.nested_clustering = bool(nested_clustering)
+        # a prior volume and a local evidence per cluster (gpry_amd.nested.run_nested(cluster_volumes=True))
+        self.nested_cluster_volumes = bool(nested_cluster_volumes)
+        if self.nested_cluster_volumes and not self.nested_clustering:
+            raise ValueError("nested_cluster_volumes=True needs nested_clustering=True")
         self._X_already_proposed = np.empty((0, self.n_d))
         self.stats = {}
 
@@ -428,11 +435,17 @@ class NORA(GenericGPAcquisition):
         if self.nested_clustering:
             nc = res.n_clusters
             self.stats["sampler_info"]["clusters"] = int(np.max(nc)) if nc is not None and len(nc) else 1
+        if self.nested_cluster_volumes:
+            self.stats["sampler_info"]["cluster_logZ"] = {q: float(v) for q, v in enumerate(res.cluster_logZ)}
+            self.stats["sampler_info"]["cluster_parent"] = {q: int(v) for q, v in enumerate(res.cluster_parent)}
         return res.X, res.y, None, res.w
 
     def _clustering_kw(self):
-        """run_nested's clustering argument: passed only when on, so that the run's calls are those of before without."""
-        return {"clustering": True} if self.nested_clustering else {}
+        """run_nested's clustering arguments: passed only when on, so that the run's calls are those of before without."""
+        kw = {"clustering": True} if self.nested_clustering else {}
+        if self.nested_cluster_volumes:
+            kw["cluster_volumes"] = True
+        return kw
 
     def _do_MC_sample_uniform(self, gpr, bounds=None, rng=None):
         """1000 d points drawn one at a time, as gp_acquisition.py:750-758 does."""

@@ -16,7 +16,7 @@ from gpry_amd.tools import generic_params_names, get_Xnumber
 # PolyChord's defaults (the Runner passes nlive = 50d)
 NESTED_DEFAULTS = {"nlive": "25d", "num_repeats": "5d", "precision_criterion": 0.001, "nprior": None, "max_ncalls": None}
 # options of the device nested sampler beyond PolyChord's settings: in nested_settings' result only when given
-NESTED_EXTRA = {"clustering": False}
+NESTED_EXTRA = {"clustering": False, "cluster_volumes": False}
 # PolyChord's names of those options -> ours, for the warning that ignores them
 NESTED_RENAMED = {"do_clustering": "clustering"}
 # Cobaya's names where they exist -> run_mcmc's arguments
@@ -49,6 +49,10 @@ def nested_settings(d, sampler_options=None):
     out["max_ncalls"] = None if opts["max_ncalls"] is None else get_Xnumber(opts["max_ncalls"], "d", d, int, "max_ncalls")
     if "clustering" in opts:
         out["clustering"] = bool(opts["clustering"])
+    if "cluster_volumes" in opts:
+        out["cluster_volumes"] = bool(opts["cluster_volumes"])
+        if out["cluster_volumes"] and not out.get("clustering"):
+            raise ValueError("sampler option cluster_volumes=True needs clustering=True")
     return out
 
 
@@ -117,7 +121,8 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
         _push_model(gpr, sampler)
         res = run_nested(gpr.device, b, seed, s["nlive"], s["num_repeats"], precision_criterion=s["precision_criterion"],
                          nprior=s["nprior"], max_ncalls=s["max_ncalls"], minus_inf_value=gpr.minus_inf_value,
-                         **({"clustering": True} if s.get("clustering") else {}))
+                         **({"clustering": True} if s.get("clustering") else {}),
+                         **({"cluster_volumes": True} if s.get("cluster_volumes") else {}))
     else:
         from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
         s = mcmc_settings(d, sampler_options)

@@ -12,7 +12,8 @@ for it (the CPU tests use a numpy one):
     -> (X_new (k, d), y_new (k,), ncalls (k,), device_ms)``
 
 With ``clustering=True`` it also calls ``dev.ns_knn(lo, hi, X, k) -> (nbr (n, k), device_ms)`` and passes
-``labels=`` (with one W per cluster) to ``ns_generation``.
+``labels=`` (with one W per cluster) to ``ns_generation``; with ``cluster_volumes=True`` as well, it passes ``cum_p=``
+(cumulative cluster probabilities) too.
 
 The algorithm, step by step:
 
@@ -25,8 +26,16 @@ The algorithm, step by step:
 * Clustering (opt-in): after the kill, the survivors' k-nearest-neighbour table (device) is cut into clusters by
   ``knn_clusters``, each cluster gets the whitening matrix of its own points, and every chain walks with the matrix of
   the cluster its start belongs to.  Starts, kills and volumes are those of the unclustered run, so a cluster receives
-  new points in proportion to its live count and logZ and the weights keep their meaning.  Not done: PolyChord's
-  per-cluster volumes and local evidences, and the choice of a cluster in proportion to its volume.
+  new points in proportion to its live count and logZ and the weights keep their meaning.
+* Per-cluster volumes (opt-in on top of clustering, after PolyChord, Handley et al. 2015): every cluster q keeps its own
+  log volume log X_q and live count n_q.  The kills are those above (the lowest of the whole live set), but a point
+  that dies in q weighs L X_q / (n_q + 1) and shrinks X_q by n_q / (n_q + 1); an emptied cluster is closed and the rest
+  of its volume dropped.  After the kill each open cluster's survivors are clustered on their own (clusters only
+  split); a split closes q and gives each child X_q n_child / n_q.  Every chain draws its cluster in proportion to X_q
+  (``chain_clusters`` restates the device's draw), its start uniformly among that cluster's survivors, and its new
+  point joins that cluster.  Z_live = sum_q X_q mean(L over q); the final live points of q get X_q / n_q each.  Every row records its
+  cluster id; the local evidence of an id sums the weights of its rows, and a mode's evidence is the sum over its
+  subtree (profiles/nested_volumes.md).
 * Stop when Z_live / Z < ``precision_criterion`` (Z_live = X mean(L_live), the PolyChord criterion) or, at the end of
   a generation, when the evaluation count has reached ``max_ncalls``.  The final live points get the volume X / n each.
 """
@@ -36,18 +45,25 @@ from time import time
 import numpy as np
 
 NestedResult = namedtuple("NestedResult", ["X", "y", "w", "logZ", "logZ_err", "ncalls", "ngen", "device_s",
-                                           "wall_s", "dead_L", "dead_logX", "n_dead", "n_clusters"],
-                          defaults=(None,))
+                                           "wall_s", "dead_L", "dead_logX", "n_dead", "n_clusters", "cluster",
+                                           "cluster_logZ", "cluster_parent"],
+                          defaults=(None, None, None, None))
 NestedResult.__doc__ = """Output of ``run_nested``.  X, y, w: rows with a finite likelihood, dead points in the order they
 died then the final live points; w sums to 1.  logZ and its error sqrt(H / nlive); ncalls: evaluations of the surrogate;
 ngen: generations; device_s / wall_s: time in the device calls / in the whole run.  dead_L / dead_logX: log-likelihood
 (-inf outside) and log prior volume after each removal, outside points included; n_dead: their count.  n_clusters: the
-cluster count of each generation (an int array) with clustering on, None without."""
+cluster count of each generation (an int array) with clustering on, None without.  With cluster_volumes on (None
+without): cluster, the id of the cluster each row of X died or stayed live in; cluster_logZ, the local evidence of each
+id (log of the summed weights of its rows, unnormalised: their logsumexp is logZ); cluster_parent, each id's parent id
+(-1 for the root).  dead_logX is then the log of the summed volume of the open clusters."""
 
 # a run stops after this many generations whatever its other criteria say (a safeguard, never met in practice)
 MAX_GENERATIONS = 100000
 # largest neighbour count the clustering rule tries (profiles/nested_clusters.md)
 DEFAULT_CLUSTER_K_MAX = 10
+# Philox4x32-10 of nested.hip: the multipliers and key increments, and the phase of a chain's start draws
+_PH_M0, _PH_M1, _PH_W0, _PH_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_PHASE_START = 1
 
 
 def default_batch(nlive):
@@ -125,6 +141,39 @@ def knn_clusters(nbr, d, k_max, min_size=None):
     return one
 
 
+def _philox_a(seed, word0, gen, chain, step):
+    """Word a of the device's ns_philox for the counters (word0, gen, chain, step), vectorised over ``chain``: a uniform
+    in [0, 1) with 53 bits."""
+    m = np.uint64(0xFFFFFFFF)
+    c1 = np.full(np.shape(chain), gen, np.uint64) & m
+    c0 = np.full_like(c1, word0) & m
+    c2 = np.asarray(chain, dtype=np.uint64) & m
+    c3 = np.full_like(c1, step) & m
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PH_M0) * c0, np.uint64(_PH_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + np.uint64(_PH_W0)) & m, (k1 + np.uint64(_PH_W1)) & m
+    return (((c0 << np.uint64(32)) | c1) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def chain_clusters(seed, generation, k, cum_p):
+    """The cluster each of the ``k`` chains of a generation draws in ``ns_generation(..., cum_p=)``
+    (gpry_ns_generation_volumes): the first q with u1 < cum_p[q], u1 from the counter (START, 1, generation, c, 0)."""
+    u1 = _philox_a(int(seed), (_PHASE_START << 24) | 1, int(generation), np.arange(int(k)), 0)
+    cum_p = np.asarray(cum_p, dtype=float)
+    return np.minimum(np.searchsorted(cum_p, u1, side="right"), len(cum_p) - 1)
+
+
+def cluster_probabilities(logX):
+    """Cumulative probabilities of choosing each cluster in proportion to its volume exp(logX), non-decreasing, the last
+    exactly 1.0."""
+    logX = np.asarray(logX, dtype=float)
+    cum = np.minimum(np.cumsum(np.exp(logX - _logsumexp(logX))), 1.0)
+    cum[-1] = 1.0
+    return cum
+
+
 def _logL(y, minus_inf_value):
     L = np.asarray(y, dtype=float).copy()
     if np.isfinite(minus_inf_value):
@@ -143,10 +192,11 @@ def _logsumexp(a):
 
 
 def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, nprior=None, max_ncalls=None,
-               batch=None, minus_inf_value=-np.inf, clustering=False, cluster_k_max=None):
+               batch=None, minus_inf_value=-np.inf, clustering=False, cluster_k_max=None, cluster_volumes=False):
     """Nested sampling run of the surrogate on ``dev``; see the module's docstring.  Returns a ``NestedResult``.
     ``clustering``: a whitening matrix per cluster of the survivors (``knn_clusters`` with neighbour tables of up to
-    ``cluster_k_max`` points, default ``DEFAULT_CLUSTER_K_MAX``)."""
+    ``cluster_k_max`` points, default ``DEFAULT_CLUSTER_K_MAX``).  ``cluster_volumes`` (needs ``clustering``): every
+    cluster keeps its own prior volume and local evidence, and chains start in a cluster drawn by volume."""
     t_start = time()
     bounds = np.asarray(bounds, dtype=float)
     lo, hi = np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
@@ -163,6 +213,11 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
     k_max = DEFAULT_CLUSTER_K_MAX if cluster_k_max is None else int(cluster_k_max)
     if clustering and not 2 <= k_max <= 32:
         raise ValueError(f"cluster_k_max = {k_max} must lie in 2 .. 32")
+    if cluster_volumes:
+        if not clustering:
+            raise ValueError("cluster_volumes=True needs clustering=True")
+        return _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls,
+                            minus_inf_value, k_max, t_start)
     n_clusters = []
     device_ms = 0.0
     # ---- prior
@@ -255,3 +310,139 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
                         dead_logX=np.concatenate(dead_logX) if dead_logX else np.empty(0),
                         n_dead=int(sum(len(a) for a in dead_y)),
                         n_clusters=np.array(n_clusters, dtype=np.int64) if clustering else None)
+
+
+def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls, minus_inf_value,
+                 k_max, t_start):
+    """run_nested(clustering=True, cluster_volumes=True): the module docstring's per-cluster bookkeeping."""
+    d = len(lo)
+    device_ms = 0.0
+    X, y, ms = dev.ns_prior(lo, hi, seed, nprior)
+    device_ms += ms
+    ncalls = nprior
+    L = _logL(y, minus_inf_value)
+    cl = np.zeros(len(L), np.int64)                 # the cluster id of every live point
+    parent, logXc = [-1], [0.0]                     # per id: parent id, log prior volume
+    open_ids = [0]
+    n_clusters = []
+    dead_X, dead_y, dead_L, dead_logw, dead_logX, dead_cl = [], [], [], [], [], []
+
+    def kill(idx):
+        """idx: positions of the removed points in ascending (y, index) order.  Every cluster's volume shrinks by
+        n_q / (n_q + 1) per removal of one of its n_q live points."""
+        cid = cl[idx]
+        logw = np.empty(len(idx))
+        touched = np.unique(cid)
+        after = np.empty((len(idx), len(touched)))  # log volume of each touched cluster after each removal
+        for col, q in enumerate(touched):
+            sel = np.flatnonzero(cid == q)
+            nb = np.count_nonzero(cl == q) - np.arange(len(sel), dtype=float)
+            seq = logXc[q] + np.cumsum(np.log(nb / (nb + 1.0)))
+            prev = np.concatenate([[logXc[q]], seq[:-1]])
+            with np.errstate(invalid="ignore"):
+                logw[sel] = L[idx[sel]] + prev - np.log(nb + 1.0)
+            seen = np.cumsum(cid == q)
+            after[:, col] = np.where(seen > 0, seq[np.maximum(seen - 1, 0)], logXc[q])
+            logXc[q] = float(seq[-1])
+        logw[~np.isfinite(L[idx])] = -np.inf
+        rest = [logXc[q] for q in open_ids if q not in touched]
+        if rest:
+            after = np.concatenate([after, np.broadcast_to(np.array(rest), (len(idx), len(rest)))], axis=1)
+        mx = np.max(after, axis=1)
+        dead_X.append(X[idx]); dead_y.append(y[idx]); dead_L.append(L[idx]); dead_cl.append(cid)
+        dead_logw.append(logw); dead_logX.append(mx + np.log(np.sum(np.exp(after - mx[:, None]), axis=1)))
+
+    def order_of(Ll):
+        return np.lexsort((np.arange(len(Ll)), Ll))
+
+    if nprior > nlive:
+        order = order_of(L)
+        kill(order[:nprior - nlive])
+        keep = np.sort(order[nprior - nlive:])
+        X, y, L, cl = X[keep], y[keep], L[keep], cl[keep]
+    gen = 0
+    while True:
+        logZ_dead = _logsumexp(np.concatenate(dead_logw)) if dead_logw else -np.inf
+        logZ_live = _logsumexp([logXc[q] + _logsumexp(L[cl == q]) - np.log(np.count_nonzero(cl == q))
+                                for q in open_ids])
+        logZ = np.logaddexp(logZ_dead, logZ_live)
+        if not np.isfinite(logZ) or logZ_live - logZ < np.log(precision_criterion):
+            break
+        if max_ncalls is not None and ncalls >= max_ncalls:
+            break
+        if gen >= MAX_GENERATIONS:
+            break
+        order = order_of(L)
+        rem, keep = order[:k_gen], np.sort(order[k_gen:])
+        lstar = float(L[rem[-1]])
+        kill(rem)
+        Xs, ys = np.ascontiguousarray(X[keep]), np.ascontiguousarray(y[keep])
+        Ls, cls = L[keep], cl[keep]
+        Us = (Xs - lo) / (hi - lo)
+        thr = lstar if not np.isfinite(minus_inf_value) else max(lstar, float(minus_inf_value))
+        # re-cluster every open cluster's survivors on their own; an emptied cluster is closed (its volume dropped),
+        # a split one is closed and its children share its volume in proportion to their live counts
+        still = []
+        for q in open_ids:
+            mem = np.flatnonzero(cls == q)
+            if len(mem) == 0:
+                continue
+            nc = 1
+            if len(mem) >= 3:
+                nbr, ms = dev.ns_knn(lo, hi, np.ascontiguousarray(Xs[mem]), min(k_max, len(mem) - 1))
+                device_ms += ms
+                lab, nc = knn_clusters(nbr, d, k_max)
+            if nc == 1:
+                still.append(q)
+                continue
+            counts = np.bincount(lab)
+            for part in range(nc):
+                parent.append(q)
+                logXc.append(logXc[q] + np.log(counts[part] / len(mem)))
+                cls[mem[lab == part]] = len(parent) - 1
+                still.append(len(parent) - 1)
+        open_ids = still
+        ids = np.array(open_ids, dtype=np.int64)
+        pos = np.empty(len(parent), np.int64)
+        pos[ids] = np.arange(len(ids))
+        labels = pos[cls].astype(np.int32)
+        cum_p = cluster_probabilities([logXc[q] for q in open_ids])
+        # every cluster walks with the matrix of its own survivors, also once kills have left it fewer than d + 1 (the
+        # ridge of cholesky_ridged keeps it positive definite): a matrix fitted to more points would span the gap to
+        # another mode, and a chain that jumps across is charged to the wrong cluster (profiles/nested_volumes.md)
+        W = np.stack([whitening(Us[labels == i]) for i in range(len(ids))])
+        n_clusters.append(len(ids))
+        Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats, labels=labels,
+                                            cum_p=cum_p)
+        device_ms += ms
+        ncalls += int(np.sum(cnt))
+        X = np.concatenate([Xs, Xn])
+        y = np.concatenate([ys, yn])
+        L = np.concatenate([Ls, _logL(yn, minus_inf_value)])
+        cl = np.concatenate([cls, ids[chain_clusters(seed, gen, k_gen, cum_p)]])
+        gen += 1
+    # ---- final live points: volume X_q / n_q each
+    nq = np.bincount(cl, minlength=len(parent)).astype(float)
+    live_logw = L + np.array(logXc)[cl] - np.log(nq[cl])
+    all_X = np.concatenate(dead_X + [X]) if dead_X else X
+    all_y = np.concatenate(dead_y + [y]) if dead_y else y
+    all_L = np.concatenate(dead_L + [L]) if dead_L else L
+    all_cl = np.concatenate(dead_cl + [cl]) if dead_cl else cl
+    all_logw = np.concatenate(dead_logw + [live_logw]) if dead_logw else live_logw
+    logZ = _logsumexp(all_logw)
+    cluster_logZ = np.array([_logsumexp(all_logw[all_cl == q]) for q in range(len(parent))])
+    fin = np.isfinite(all_L)
+    if np.isfinite(logZ):
+        p = np.exp(all_logw[fin] - logZ)
+        H = float(np.sum(p * (all_L[fin] - logZ)))
+        w = p / np.sum(p)
+    else:
+        H, w = 0.0, np.zeros(int(fin.sum()))
+    return NestedResult(X=np.ascontiguousarray(all_X[fin]), y=np.ascontiguousarray(all_y[fin]), w=w, logZ=float(logZ),
+                        logZ_err=float(np.sqrt(max(H, 0.0) / nlive)), ncalls=int(ncalls), ngen=gen,
+                        device_s=device_ms / 1e3, wall_s=time() - t_start,
+                        dead_L=np.concatenate(dead_L) if dead_L else np.empty(0),
+                        dead_logX=np.concatenate(dead_logX) if dead_logX else np.empty(0),
+                        n_dead=int(sum(len(a) for a in dead_y)), n_clusters=np.array(n_clusters, dtype=np.int64),
+                        cluster=np.ascontiguousarray(all_cl[fin]), cluster_logZ=cluster_logZ,
+                        cluster_parent=np.array(parent, dtype=np.int64))

@@ -256,6 +256,21 @@ int gpry_ns_generation_clustered(gpry_ctx* ctx, const double* lo, const double* 
                                  const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
                                  int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
                                  double* X_new, double* y_new, int64_t* ncalls, double* device_ms);
+/* gpry_ns_generation_volumes: gpry_ns_generation_clustered with the chains' clusters drawn in proportion to given
+ *   probabilities (PolyChord's choice by prior volume).  cum_p: n_clusters non-decreasing cumulative probabilities, the
+ *   last exactly 1.0.  Chain c draws its cluster q, the first q with u1 < cum_p[q] (u1: counter (1, 1, gen, c, 0), word
+ *   a), then its start among q's survivors in their order in X_surv: index min(floor(u0 n_q), n_q - 1) with the u0 of
+ *   gpry_ns_generation (counter (1, 0, gen, c, 0)), and walks with W + q d d; every step keeps its counter
+ *   (gen, c, s).  Refused (-1) before anything runs: a label outside 0 .. n_clusters - 1, a decreasing (or negative,
+ *   or NaN) cum_p, a last entry other than 1.0, a cluster with positive probability and no survivor.  Hence, bit for
+ *   bit:
+ *   - with one cluster and cum_p = {1.0}, the call equals gpry_ns_generation with that W;
+ *   - a chain c that drew cluster q equals chain c of gpry_ns_generation called with q's survivors alone (in their
+ *     order) and W + q d d: the same start from the same u0, the same step counters. */
+int gpry_ns_generation_volumes(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
+                               const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                               int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
+                               const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, double* device_ms);
 /* gpry_ns_knn: the k nearest other points of each of the n points X (n x d) in unit-cube coordinates
  *   u = (x - lo) / (hi - lo): nbr_out (n x k, row-major) holds row i's neighbours in order of (squared distance, index),
  *   i itself excluded, ties (duplicated points) broken by the index.  The squared distance is the sum over the
