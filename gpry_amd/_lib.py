@@ -413,7 +413,8 @@ class Device:
     def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels=None,
                       cum_p=None):
         """One generation of ``k`` slice-sampling chains above ``lstar``: ``(X_new (k, d), y_new (k,), ncalls (k,),
-        device_ms)``.  ``labels`` (nsurv cluster numbers) with ``W`` of shape (n_clusters, d, d): every chain walks with
+        device_ms)``.  ``W`` (d, d) is lower triangular (``nested.whitening`` / ``cholesky_ridged`` deliver one): the
+        direction is tril(W) z / |z|, entries above the diagonal are not read.  ``labels`` (nsurv cluster numbers) with ``W`` of shape (n_clusters, d, d): every chain walks with
         the matrix of its starting survivor's cluster (gpry_ns_generation_clustered).  With ``cum_p`` (n_clusters
         cumulative probabilities, the last 1.0) as well, every chain first draws its cluster from cum_p and then its
         start among that cluster's survivors (gpry_ns_generation_volumes)."""

@@ -67,8 +67,11 @@ __global__ __launch_bounds__(256) void ns_prior_kernel(NsArgs a, KernParams kp, 
 // `num_repeats` slice-sampling steps on {x in the box : y(x) > lstar}.  Step s: direction v = W z / |z| (with labels: W of
 // the start's cluster, W + labels[j] d d), z ~ N(0, I) by
 // Box-Muller from draws 0..(d-1)/2; the interval [-r, 1 - r] along v (r: draw 16) stepped out by whole widths, at most
-// 32 per side; then up to 64 shrinkage tries (draws 17..), each uniform on the interval.  A step that hits a cap keeps
-// the current point.  Outputs: the chain's last point, its y and the number of evaluations it made.
+// 32 per side (a side that reaches 32 widths stops growing and the step goes on to shrink from the interval it has); then
+// up to 64 shrinkage tries (draws 17..), each uniform on the interval, a failed try at t moving the end on t's side of
+// the current point (t < 0: the left one).  A step whose 64 tries all fail keeps the current point.  A try outside the
+// box fails without an evaluation.  W is lower triangular: the sum over k stops at the row's index, what lies above the
+// diagonal is never read.  tests/tools/sampler_walk.py restates the walk step by step.  Outputs: the chain's last point, its y and the number of evaluations it made.
 // With a member list (volumes): chain c first draws its cluster q, the first q with u1 < cum_p[q] (u1: counter
 // (START, 1, gen, c, 0)), then its start members[moffs[q] + min(floor(u0 n_q), n_q - 1)] from the same u0 as above
 // (n_q = moffs[q + 1] - moffs[q]), and walks with W + q d d.  The host guarantees cum_p[n_clusters - 1] = 1.0 and

@@ -242,7 +242,10 @@ int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t se
                   double* y_out, double* device_ms);
 /* gpry_ns_generation: one generation of batch replacement -- k chains, chain c starting from a survivor drawn uniformly
  *   from X_surv (nsurv x d, their y y_surv), `num_repeats` slice-sampling steps on {x in the box : y(x) > lstar} along
- *   directions W z / |z| (W: d x d lower Cholesky factor in unit-cube coordinates, row-major).  Outputs the chains' last
+ *   directions W z / |z| (W: d x d lower triangular in unit-cube coordinates, row-major -- a Cholesky factor; the
+ *   contract is the triangle: row t is summed over columns 0 .. t, entries above the diagonal are never read).  A step
+ *   steps out by whole widths, at most 32 per side, then makes up to 64 shrinkage tries; if all fail the chain keeps
+ *   its point; a try outside the box costs no evaluation.  num_repeats = 0 returns the drawn starts.  Outputs the chains' last
  *   points X_new (k x d), their y (y_new) and the evaluations each chain made (ncalls, k).  Replaces one
  *   PolyChord iteration's `num_repeats` slice steps (gpry/gp_acquisition.py:650-682 settings, :760-813 run). */
 int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv, const double* y_surv,

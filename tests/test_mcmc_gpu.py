@@ -13,7 +13,8 @@ from conftest import ROOT
 from test_nested_gpu import _banana_ll, _fitted, _gauss_ll, _one_point, _parity_cases, _quadrature
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
-import mcmc_numpy  # noqa: E402
+import mcmc_numpy  # noqa: E402,F401
+import sampler_walk  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -66,37 +67,13 @@ def test_every_step_follows_the_metropolis_rule(scale, T):
     gpr, bounds = dict(_parity_cases())["N=600 d=3 (nsplit 1)"]()
     _pushed(gpr)
     lo, hi = bounds[:, 0], bounds[:, 1]
-    span = hi - lo
     n, steps, seed, batch = 16, 60, 1234, 5
     Lp = _proposal(gpr, bounds, scale)
     X0 = _starts(gpr, n, 4)
-    out = gpr.device.mcmc_chains(lo, hi, X0, np.full(n, np.nan), Lp, T, gpr.minus_inf_value, seed, batch, steps, 1,
-                                 proposals=True)
-    y0 = _one_point(gpr, X0)
-    c = np.arange(n)
-    X_prev, y_prev = X0, y0
-    outside = borderline = 0
-    for s in range(steps):
-        z = mcmc_numpy.normals(seed, batch, c, s, len(lo))
-        Xp, yp = out["X_prop"][:, s], out["y_prop"][:, s]
-        np.testing.assert_allclose(Xp - X_prev, (z @ Lp.T) * span, rtol=0, atol=1e-13 * np.max(np.abs(bounds)))
-        inside = np.all((Xp >= lo) & (Xp <= hi), axis=1)
-        np.testing.assert_array_equal(np.isnan(yp), ~inside)
-        outside += int(np.sum(~inside))
-        lu = np.log(1.0 - mcmc_numpy.accept_uniform(seed, batch, c, s))
-        with np.errstate(invalid="ignore"):
-            rhs = (yp - y_prev) / T
-            expect = inside & np.isfinite(yp) & (lu < rhs)
-            close = inside & (np.abs(lu - rhs) < 1e-12 * (1 + np.abs(rhs)))
-        borderline += int(np.sum(close))
-        moved = np.any(out["X"][:, s] != X_prev, axis=1)
-        np.testing.assert_array_equal(moved[~close], expect[~close])
-        np.testing.assert_array_equal(out["X"][:, s][moved], Xp[moved])
-        np.testing.assert_array_equal(out["y"][:, s], np.where(moved, yp, y_prev))
-        X_prev, y_prev = out["X"][:, s], out["y"][:, s]
-    assert borderline < 3
-    moves = np.any(np.diff(np.concatenate([X0[:, None], out["X"]], axis=1), axis=1) != 0, axis=2)
-    np.testing.assert_array_equal(out["naccept"], moves.sum(axis=1))
+    # (the body of the check: tests/tools/sampler_walk.py, which test_sampler_walk_gpu.py runs at every instantiation)
+    counts = sampler_walk.check_metropolis_rule(gpr.device, lo, hi, X0, np.full(n, np.nan), _one_point(gpr, X0), Lp, T,
+                                                gpr.minus_inf_value, seed, batch, steps, 1)
+    outside = counts["outside"]
     if scale > 1:
         assert outside > 0, "the wide proposal never left the box"
 

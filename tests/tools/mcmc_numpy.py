@@ -53,6 +53,7 @@ class NumpyMCMCDevice:
             cnt[todo] += 1
         nrec = nsteps // thin
         Xr, yr = np.empty((n, nrec, d)), np.empty((n, nrec))
+        Xprop, yprop = np.empty((n, nsteps, d)), np.empty((n, nsteps))
         for s in range(nsteps):
             ut = u + normals(seed, batch, c, s, d) @ np.asarray(Lp).T
             xt = lo + ut * span
@@ -61,6 +62,7 @@ class NumpyMCMCDevice:
             if inside.any():
                 yt[inside] = self.loglike(xt[inside])
                 cnt[inside] += 1
+            Xprop[:, s], yprop[:, s] = xt, yt
             ua = accept_uniform(seed, batch, c, s)
             with np.errstate(invalid="ignore"):
                 acc = inside & np.isfinite(yt) & (yt > minus_inf_value) & (np.log(1.0 - ua) < (yt - y) / T)
@@ -68,4 +70,7 @@ class NumpyMCMCDevice:
             nacc += acc
             if (s + 1) % thin == 0:
                 Xr[:, (s + 1) // thin - 1], yr[:, (s + 1) // thin - 1] = x, y
-        return dict(X=Xr, y=yr, X_last=x, y_last=y, naccept=nacc, ncalls=cnt, device_ms=0.0)
+        out = dict(X=Xr, y=yr, X_last=x, y_last=y, naccept=nacc, ncalls=cnt, device_ms=0.0)
+        if proposals:
+            out.update(X_prop=Xprop, y_prop=yprop)
+        return out

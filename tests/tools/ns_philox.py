@@ -56,6 +56,7 @@ class NumpyNestedDevice:
         return X, np.asarray(self.loglike(X), dtype=float), 0.0
 
     def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats):
+        """``W``: lower triangular (the kernel sums k <= t only; what lies above the diagonal is not read)."""
         lo, hi = np.asarray(lo, dtype=float), np.asarray(hi, dtype=float)
         span = hi - lo
         n, d = X_surv.shape
@@ -86,7 +87,7 @@ class NumpyNestedDevice:
             z = np.empty((k, 2 * h))
             z[:, 0::2], z[:, 1::2] = rad * np.cos(ang), rad * np.sin(ang)
             z = z[:, :d]
-            v = z @ np.asarray(W).T / np.linalg.norm(z, axis=1)[:, None]
+            v = z @ np.tril(np.asarray(W)).T / np.linalg.norm(z, axis=1)[:, None]
             r, _ = philox(seed, PHASE_STEP, DRAW_OFFSET, generation, c, s)
             lt, rt = -r, 1.0 - r
             act = np.ones(k, bool)
