@@ -22,6 +22,12 @@ struct StageTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// post-processing of a sweep's partial sums (sweep.hip: finish_y, finish_sd, logexp_value)
+struct FinishParams {
+    double C, y_mean, y_std, clip_hi, zeta, baseline, sigma_n;
+    int want_std, want_acq;
+};
+
 struct gpry_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -145,7 +151,14 @@ struct gpry_ctx {
     unsigned long long* dkeys = nullptr; int64_t keys_cap = 0;
     unsigned int* dhist = nullptr;
     gpry_cand* dcand = nullptr; int64_t cand_cap = 0;
-    unsigned long long* dsel = nullptr;  // select state
+    unsigned long long* dsel = nullptr;  // DSEL_WORDS words: select state and the counters of the sweep
+    enum { DSEL_NAN = 0,       // count_nan_kernel (between selections)
+           DSEL_STATE = 0,     // SelState of a radix select, 4 words ...
+           DSEL_EMIT = 4,      // ... and its two counters: records emitted, largest key below the threshold
+           DSEL_SURV = 6,      // candidates whose bound is not below tau (prune_survivors)
+           DSEL_GIDX = 7,      // indices written to dgidx
+           DSEL_LIVE = 8,      // live blocks of the bound pass
+           DSEL_WORDS = 64 };
 
     // Kriging-believer session
     int64_t kb_n = 0, kb_cap = 0;
@@ -177,22 +190,21 @@ struct gpry_ctx {
     int opt_chol_stacked_dense = 0;    // 1: potrf_stacked without use of the zero structure of the appended rows (comparator)
     int opt_sweep_overlap = 0;         // 1: the cross-kernel panel of chunk c + 1 is built on the side stream underneath the contraction of chunk c (two panels)
     int opt_sweep_upload = 1;          // 1: a fresh candidate pool is uploaded chunk by chunk on stream2, chunk c + 1 underneath the kernels of chunk c
-    const double* up_X = nullptr;      // host pool of the sweep in flight whose chunks are still to be uploaded (run_sweep)
+    const double* up_X = nullptr;      // host pool of the sweep in flight whose chunks are still to be uploaded (sweep.hip: run_sweep)
     const double* up_y = nullptr;      // ... and the caller's y of a sweep with given y (gpry_sweep_logexp_given), beside them
     int up_gates = 0;                  // ... and the device gates are evaluated chunk by chunk behind each upload
     int opt_predict_gates = 0;         // 1: gpry_predict ORs the device gates (gpry_set_gates) into the caller's mask, as the sweep does
-    // pruned sweep (option "sweep_prune", api.hip): gpry_sweep_logexp with no arrays wanted leaves y and a per-candidate upper
+    // pruned sweep (option "sweep_prune", sweep.hip / sweep_topk.hip): gpry_sweep_logexp with no arrays wanted leaves y and a per-candidate upper
     // bound of the acquisition; gpry_sweep_topk contracts only the candidates whose bound can reach the shortlist
     int opt_sweep_prune = 0;
     // 1 (default): in the hybrid panel form, stage A of a pruned sweep bounds y instead of computing it (the bound pass,
-    // api.hip: run_sweep); exact y only for the candidates that are contracted
+    // sweep.hip: mean_bound_setup); exact y only for the candidates that are contracted
     int opt_sweep_mean_bound = 1;
-    int sw_pruned = 0;                 // 1: the resident sweep is pruned (acq_all holds exact values or bounds, see api.hip)
+    int sw_pruned = 0;                 // 1: the resident sweep is pruned (acq_all holds exact values or bounds, see sweep_topk.hip)
     struct PruneState {
         int have_mask = 0;
         int form = 0;                  // panel form stage A decided (panel_form codes); compact panels take the same
-        double zeta = 0.0, baseline = 0.0, sigma_n = 0.0;
-        double C = 0.0, y_mean = 0.0, y_std = 0.0, clip_hi = 0.0;   // the model's post-processing the bounds were made with
+        FinishParams fp = {};          // the model's post-processing the bounds were made with
         int64_t n_eval = 0;            // candidates evaluated exactly: the top n_eval by bound
         int64_t rounds = 0, evaluated_total = 0, completed = 0, last_K = 0;
         int64_t n_gidx = 0;            // candidates in dgidx (the last contracted set)
@@ -202,7 +214,7 @@ struct gpry_ctx {
         int ybound = 0;                // stage A bounded y (the bound pass): every contraction computes y as well
         int64_t live_blocks = 0, blocks = 0;    // blocks of 16 training rows x 32 candidates the bound pass evaluated / saw
     } prune;
-    // the prediction state the pruned sweep was made with, copied at its end (api.hip: prune_snapshot): a later contraction
+    // the prediction state the pruned sweep was made with, copied at its end (sweep.hip: prune_snapshot): a later contraction
     // round or completion evaluates THAT model, whatever gpry_set_train / set_theta / factorize / append_rows did meanwhile
     struct ModelSnap {
         double *dV = nullptr, *dalpha_ = nullptr, *dXs = nullptr, *dX = nullptr;
@@ -262,6 +274,18 @@ int dev_alloc(gpry_ctx* ctx, T** p, int64_t count);
 int dev_free(gpry_ctx* ctx, void* p);
 
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+// grow-only device buffer with one capacity (in elements): nothing to do while need <= *cap; else the stream is drained,
+// the old buffer freed and `need` elements allocated (the contents are not kept)
+template <typename T>
+int dev_grow(gpry_ctx* ctx, T** p, int64_t* cap, int64_t need) {
+    if (need <= *cap) return 0;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*p) GPRY_TRY(dev_free(ctx, *p));
+    *p = nullptr; *cap = 0;
+    GPRY_TRY(dev_alloc(ctx, p, need));
+    *cap = need;
+    return 0;
+}
 
 // the buffer of theta `tb` in a batched launch (see gpry_ctx::bn): every per-theta pointer moves by tb * bstride doubles
 // (pointer arithmetic, not integer arithmetic: the result keeps the provenance of a kernel argument, i.e. global loads

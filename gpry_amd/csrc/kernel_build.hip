@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
 // (x - c, y - c with c = the mean of the training rows per dimension: distances do not change, the norms shrink to the
 // spread of the data): the absolute error of r^2 is <= 4 eps (|x - c|^2 + |y - c|^2), i.e. up to 4 eps C (1 + 6 R^2) in an
 // entry of K* (R = the scaled radius of the training set: 1e-14 C at l = 0.3, d = 16, but 1e-10 C at l = 0.01) -- and
-// the posterior mean multiplies that by the weights alpha_.  The caller (api.hip, where the panel form is chosen) therefore takes this form
+// the posterior mean multiplies that by the weights alpha_.  The caller (sweep.hip: choose_panel_form) therefore takes this form
 // only while its estimate of that product stays a factor of four inside the 1e-6 the posterior mean is specified to, and the
 // difference form otherwise.  The exact difference form also stays for gpry_kernel_cross (K* itself is
 // compared at 1e-13), the small batches and the Kriging-believer registrations.
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
 // blocks in two pairs; per 16 training rows (A operand from LDS) 4 x d/4 MFMAs give each lane 4 x 4 pairs: rows g + 4 q
 // (g = lane >> 4), two neighbouring candidates per block pair, stored as 16-byte pieces of 256-byte row segments.
 // Ycs: Np x DP centred scaled training rows (zero rows for the padding), row-major; Xcs: DP x ldm centred scaled candidates.
-// HYB (round 6): the HYBRID form for models whose error estimates rule the expanded form out (api.hip: run_sweep).  The error
+// HYB (round 6): the HYBRID form for models whose error estimates rule the expanded form out (sweep.hip: choose_panel_form).  The error
 // of the expanded r^2 is absolute -- 4 eps (2 r^2 + 4 R^2) whatever r -- while the kernel only listens to r^2 where r is small:
 // beyond r^2 = 100 every smooth kernel here has |dk / d r^2| < 4e-9 C, so that even R^2 = 1.6e7 (all length scales at their
 // lower bound) moves such an entry by < 1e-15 C.  A pair that comes out NEARER than that has its distance taken again from the
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
 // [ubnd, uhi] -- ubnd >= ucut, so the hybrid form would take none of them again from the coordinates -- adds nothing (a
 // wave-uniform branch); any other block goes through the code of the exact pass unchanged, so that each of its terms
 // alpha_j v_j is the exact pass's to the bit.  mean_part then holds the partial sums over the live terms and sabs_part the
-// sums of |alpha_j v_j| over them; live_cnt counts the live blocks.  The caller (api.hip: run_sweep) bounds what was left out.
+// sums of |alpha_j v_j| over them; live_cnt counts the live blocks.  The caller (sweep.hip: mean_bound_setup) bounds what was left out.
 template <int DP, int KID, bool HYB, bool BND = false>
 __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
     const double* __restrict__ Xcs, int64_t ldm, int64_t mc,

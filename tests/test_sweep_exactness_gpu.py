@@ -228,7 +228,7 @@ def test_pruned_sweep_with_one_row_tile(dev, kid, N):
 
 
 def test_completion_after_a_model_of_fewer_dimensions():
-    """Regression: the gathered rows of a compact evaluation (api.hip: prune_eval, dXg) were sized in rows of the model that
+    """Regression: the gathered rows of a compact evaluation (sweep.hip: prune_eval, dXg) were sized in rows of the model that
     first needed them.  A completion at d = 3 that gathered ~38000 rows, then one at d = 8 of ~19000 rows, wrote past the
     buffer.  Own context, so that the d = 3 completion is the first one made on it."""
     dev = _lib.Device(0)

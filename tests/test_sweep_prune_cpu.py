@@ -1,7 +1,7 @@
 """NORA.multi_add over a device whose shortlist comes from a pruned sweep (option "sweep_prune"): the records are exact, but
 the bound may be any value >= the full sweep's -- the largest acquisition bound of a candidate that was never contracted.
 The extension loop of multi_add must still arrive at the reference's proposals.  The double below restates the library's
-answer rule in numpy (api.hip: prune_topk; its contracted set only grows x 8, without the survivor round) with a
+answer rule in numpy (sweep_topk.hip: prune_topk; its contracted set only grows x 8, without the survivor round) with a
 deliberately loose bound: the acquisition at the largest sigma of the pool."""
 import numpy as np
 import pytest

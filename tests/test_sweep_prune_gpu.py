@@ -1,4 +1,4 @@
-"""The pruned sweep (option "sweep_prune", api.hip: prune_topk) against the full sweep on the same model and pool: the
+"""The pruned sweep (option "sweep_prune", sweep_topk.hip: prune_topk) against the full sweep on the same model and pool: the
 shortlist records (idx, acq, y, sigma) are equal bit for bit, the pruned bound is >= the full one, and every array fetched
 after a pruned shortlist is the full sweep's.  NORA.multi_add gives the same proposals with exact_prune on and off."""
 import numpy as np
