@@ -70,6 +70,9 @@ SIGNATURES = {
     "gpry_ns_generation_volumes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64,
                                              C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
                                              _P(C.c_double)]),
+    "gpry_ns_generation_phantoms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, _vp, C.c_uint64,
+                                              C.c_int64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
+                                              _vp, _vp, _P(C.c_double)]),
     "gpry_ns_knn": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _P(C.c_double)]),
     "gpry_mcmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_double, C.c_uint64,
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
@@ -454,6 +457,45 @@ class Device:
                                                            _ptr(y_new), _ptr(cnt), C.byref(ms)),
                     "gpry_ns_generation_clustered")
         return X_new, y_new, cnt, ms.value
+
+    def ns_generation_phantoms(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, thin,
+                               labels=None, cum_p=None):
+        """``ns_generation`` that also keeps the chains' interior states: ``(X_new (k, d), y_new (k,), ncalls (k,), X_ph
+        (k, n_ph, d), y_ph (k, n_ph), device_ms)``, n_ph = (num_repeats - 1) // thin.  Slot i of chain c is its state
+        after step (i + 1) thin; the last state is X_new and is not among them.  X_new, y_new and ncalls are those of
+        ``ns_generation`` with the same arguments, bit for bit (gpry_ns_generation_phantoms)."""
+        if cum_p is not None and labels is None:
+            raise ValueError("cum_p needs labels")
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X_surv = _f64(X_surv)
+        n = X_surv.shape[0]
+        if X_surv.ndim != 2 or X_surv.shape[1] != self.d:
+            raise ValueError(f"expected survivors of shape (n, {self.d}), got {X_surv.shape}")
+        y_surv = _f64(y_surv, (n,))
+        k, num_repeats, thin = int(k), int(num_repeats), int(thin)
+        n_ph = max(num_repeats - 1, 0) // max(thin, 1)          # (thin < 1 is refused by the library)
+        lab = cp = None
+        nc = 1
+        if labels is None:
+            W = _f64(W, (self.d, self.d))
+        else:
+            W = _f64(W)
+            if W.ndim != 3 or W.shape[1:] != (self.d, self.d):
+                raise ValueError(f"expected W of shape (n_clusters, {self.d}, {self.d}), got {W.shape}")
+            nc = int(W.shape[0])
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (n,):
+                raise ValueError(f"expected {n} labels, got shape {lab.shape}")
+            if cum_p is not None:
+                cp = _f64(cum_p, (nc,))
+        X_new, y_new, cnt, ms = np.empty((k, self.d)), np.empty(k), np.zeros(k, np.int64), C.c_double(0.0)
+        X_ph, y_ph = np.empty((k, n_ph, self.d)), np.empty((k, n_ph))
+        self._check(self._lib.gpry_ns_generation_phantoms(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
+                                                          float(lstar), _ptr(W), int(seed), int(generation), k,
+                                                          num_repeats, _ptr(lab), nc, _ptr(cp), _ptr(X_new), _ptr(y_new),
+                                                          _ptr(cnt), thin, _ptr(X_ph), _ptr(y_ph), C.byref(ms)),
+                    "gpry_ns_generation_phantoms")
+        return X_new, y_new, cnt, X_ph, y_ph, ms.value
 
     def ns_knn(self, lo, hi, X, k):
         """The ``k`` nearest other points of every row of ``X`` in unit-cube coordinates, in order of (squared distance,

@@ -236,6 +236,8 @@ struct gpry_ctx {
     int64_t mc_cap = 0;
     char* dknn = nullptr;              // gpry_ns_knn: transposed unit-cube points and the neighbour table (bytes)
     int64_t knn_cap = 0;
+    char* dph = nullptr;               // gpry_ns_generation_phantoms: the chains' recorded states and their y (bytes)
+    int64_t ph_cap = 0;
 
     // host pinned staging
     void* hpin = nullptr; void* hpin_dev = nullptr; int64_t hpin_cap = 0;   // host / device view of the same buffer

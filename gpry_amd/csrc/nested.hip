@@ -24,6 +24,10 @@
 // gpry_ns_generation_volumes lets every chain first draw its cluster from cumulative probabilities (the clusters' prior
 // volumes, PolyChord's choice) and then its start among that cluster's survivors; without a member list the chain
 // kernel draws its start uniformly from all survivors, as before, bit for bit.
+//
+// Phantoms.  gpry_ns_generation_phantoms also keeps the chains' interior states: the state after every thin-th step but
+// the last goes to X_ph / y_ph (PolyChord's phantom points).  The recording is a template flag of the chain kernel: no
+// draw, evaluation or barrier is added, and without it the kernel is the instantiation of before.
 #include <climits>
 #include <vector>
 
@@ -39,6 +43,7 @@
 #define NS_KNN_MAX_K 32
 #define NS_KNN_MAX_N 65536
 #define NS_KNN_LDS_N 7680           // rows of up to this many points keep their distances in LDS (60 KiB + 3.3 KiB static)
+#define NS_PHANTOM_MAX_BYTES (1ll << 30)    // X_ph and y_ph of one generation together (gpry_hip.h)
 
 // Prior draws: point i (one workgroup) is lo + u * (hi - lo), u from the counter (PRIOR, draw j, 0, i, 0) for
 // coordinates 2j and 2j + 1, clamped to hi.
@@ -76,7 +81,11 @@ __global__ __launch_bounds__(256) void ns_prior_kernel(NsArgs a, KernParams kp, 
 // (START, 1, gen, c, 0)), then its start members[moffs[q] + min(floor(u0 n_q), n_q - 1)] from the same u0 as above
 // (n_q = moffs[q + 1] - moffs[q]), and walks with W + q d d.  The host guarantees cum_p[n_clusters - 1] = 1.0 and
 // n_q >= 1 wherever cum_p rises.
-template <int DP, int KID>
+// PH (phantoms): after step s with (s + 1) % thin == 0 and s + 1 < num_repeats the chain's state (s_x, y_cur) goes to slot
+// (s + 1) / thin - 1 of its n_ph = (num_repeats - 1) / thin rows of X_ph / y_ph.  Thread t stores the s_x[t] it wrote itself
+// and every thread holds y_cur, so the stores need no barrier of their own; a chain that did not move stores the same
+// state again (a repeated sample).  Without PH the three arguments are not read.
+template <int DP, int KID, bool PH>
 __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, AffParams ap,
                                                        const double* __restrict__ X_surv, const double* __restrict__ y_surv,
                                                        int64_t nsurv, const double* __restrict__ W,
@@ -84,7 +93,8 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, 
                                                        const int* __restrict__ moffs, const double* __restrict__ cum_p,
                                                        int n_clusters, double lstar, unsigned gen,
                                                        int num_repeats, double* __restrict__ X_new, double* __restrict__ y_new,
-                                                       int64_t* __restrict__ ncalls) {
+                                                       int64_t* __restrict__ ncalls, int thin, int n_ph,
+                                                       double* __restrict__ X_ph, double* __restrict__ y_ph) {
     __shared__ double r2s[MEAN_SLICE_CH];
     __shared__ double red[256];
     __shared__ double s_W[GPRY_MAX_DIM * GPRY_MAX_DIM];
@@ -170,6 +180,11 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, 
             }
             if (tt < 0.0) lt = tt; else rt = tt;
         }
+        if (PH && (s + 1) % thin == 0 && s + 1 < num_repeats) {
+            const int64_t r = (int64_t)c * n_ph + (s + 1) / thin - 1;
+            if (t < d) X_ph[r * d + t] = s_x[t];
+            if (t == 0) y_ph[r] = y_cur;
+        }
         __syncthreads();
     }
     if (t < d) X_new[(int64_t)c * d + t] = s_x[t];
@@ -250,9 +265,13 @@ __global__ __launch_bounds__(256) void ns_knn_kernel(const double* __restrict__ 
 static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, const double* hi, const double* X_surv,
                               const double* y_surv, int64_t nsurv, double lstar, const double* W, const int32_t* labels,
                               int n_clusters, const double* cum_p, uint64_t seed, int64_t generation, int k,
-                              int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
+                              int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms,
+                              int thin = 1, double* X_ph = nullptr, double* y_ph = nullptr) {
     if (!lo || !hi || !X_surv || !y_surv || !W || !X_new || !y_new || !ncalls)
         return gpry_fail(ctx, -1, "%s: NULL argument", who);
+    if (thin < 1) return gpry_fail(ctx, -1, "%s: thin = %d", who, thin);
+    if ((X_ph == nullptr) != (y_ph == nullptr))
+        return gpry_fail(ctx, -1, "%s: X_ph and y_ph are both NULL or both given", who);
     if (nsurv < 1 || k < 0 || num_repeats < 0 || generation < 0 || generation > 0xffffffffll)
         return gpry_fail(ctx, -1, "%s: nsurv = %lld, k = %d, num_repeats = %d, generation = %lld", who,
                          (long long)nsurv, k, num_repeats, (long long)generation);
@@ -283,6 +302,13 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
     GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
     const int d = ctx->d;
     const int64_t nw = labels ? n_clusters : 1;
+    // phantoms: n_ph recorded states per chain, [X_ph | y_ph] in a device buffer of the context
+    const int n_ph = X_ph && num_repeats > 0 ? (num_repeats - 1) / thin : 0;
+    const int64_t pxb = sizeof(double) * (int64_t)k * n_ph * d, pyb = sizeof(double) * (int64_t)k * n_ph;
+    if (pxb + pyb > NS_PHANTOM_MAX_BYTES)
+        return gpry_fail(ctx, -1, "%s: %d chains x %d phantoms x %d coordinates need %lld bytes, the limit is %lld", who, k,
+                         n_ph, d, (long long)(pxb + pyb), (long long)NS_PHANTOM_MAX_BYTES);
+    const bool rec = k > 0 && n_ph > 0;
     // one pinned, mapped buffer: [survivors | their y | W | labels | new points | their y | counts]; with cum_p the
     // labels' place holds [members | member offsets | cum_p] instead
     const int64_t bm = round_up(sizeof(int32_t) * nsurv, 256), bo = round_up(sizeof(int32_t) * (n_clusters + 1), 256);
@@ -328,15 +354,34 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
     int64_t* dcn = (int64_t*)(hd + on + bn + bny);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
+    const int64_t pxo = round_up(pxb, 256);
+    if (rec && pxo + pyb > ctx->ph_cap) {
+        if (ctx->dph) HIP_TRY(ctx, hipFree(ctx->dph));
+        ctx->dph = nullptr; ctx->ph_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->dph, (size_t)(pxo + pyb)));
+        ctx->ph_cap = pxo + pyb;
+    }
+    double* dXp = rec ? (double*)ctx->dph : nullptr;
+    double* dyp = rec ? (double*)(ctx->dph + pxo) : nullptr;
     if (k > 0) {
-#define NC(DP, KID) hipLaunchKernelGGL((ns_chain_kernel<DP, KID>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, ap, \
-                                       dXs_, dys_, nsurv, dW, dlab, dmem, dmof, dcp, (int)nw, lstar, (unsigned)generation, \
-                                       num_repeats, dXn, dyn, dcn)
-#define NC_4(KID) NC(4, KID)
-#define NC_8(KID) NC(8, KID)
-#define NC_16(KID) NC(16, KID)
-#define NC_32(KID) NC(32, KID)
-        if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NC_4) }
+#define NC(DP, KID, PH) hipLaunchKernelGGL((ns_chain_kernel<DP, KID, PH>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, \
+                                           ap, dXs_, dys_, nsurv, dW, dlab, dmem, dmof, dcp, (int)nw, lstar, \
+                                           (unsigned)generation, num_repeats, dXn, dyn, dcn, thin, n_ph, dXp, dyp)
+#define NC_4(KID) NC(4, KID, false)
+#define NC_8(KID) NC(8, KID, false)
+#define NC_16(KID) NC(16, KID, false)
+#define NC_32(KID) NC(32, KID, false)
+#define NP_4(KID) NC(4, KID, true)
+#define NP_8(KID) NC(8, KID, true)
+#define NP_16(KID) NC(16, KID, true)
+#define NP_32(KID) NC(32, KID, true)
+        if (rec) {
+            if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NP_4) }
+            else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NP_8) }
+            else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NP_16) }
+            else { DISPATCH_KID(ctx->kernel_id, NP_32) }
+        }
+        else if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NC_4) }
         else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NC_8) }
         else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NC_16) }
         else { DISPATCH_KID(ctx->kernel_id, NC_32) }
@@ -344,7 +389,16 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
 #undef NC_8
 #undef NC_16
 #undef NC_32
+#undef NP_4
+#undef NP_8
+#undef NP_16
+#undef NP_32
 #undef NC
+    }
+    if (rec) {
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(X_ph, dXp, (size_t)pxb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(y_ph, dyp, (size_t)pyb, hipMemcpyDeviceToHost, ctx->stream));
     }
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
     memcpy(X_new, h + on, sizeof(double) * (int64_t)k * d);
@@ -422,6 +476,19 @@ int gpry_ns_generation_volumes(gpry_ctx* ctx, const double* lo, const double* hi
     if (nsurv > INT_MAX) return gpry_fail(ctx, -1, "gpry_ns_generation_volumes: nsurv = %lld", (long long)nsurv);
     return ns_generation_impl(ctx, "gpry_ns_generation_volumes", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
                               n_clusters, cum_p, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+}
+
+int gpry_ns_generation_phantoms(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
+                                const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                                int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
+                                const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, int thin, double* X_ph,
+                                double* y_ph, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_phantoms: ctx is NULL");
+    if (cum_p && nsurv > INT_MAX)
+        return gpry_fail(ctx, -1, "gpry_ns_generation_phantoms: nsurv = %lld", (long long)nsurv);
+    return ns_generation_impl(ctx, "gpry_ns_generation_phantoms", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
+                              labels ? n_clusters : 1, cum_p, seed, generation, k, num_repeats, X_new, y_new, ncalls,
+                              device_ms, thin, X_ph, y_ph);
 }
 
 int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double* X, int64_t n, int k, int32_t* nbr_out,

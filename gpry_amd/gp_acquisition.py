@@ -314,7 +314,12 @@ class NORA(GenericGPAcquisition):
     cluster count of the run is ``sampler_info["clusters"]``.  ``nested_cluster_volumes=True`` (needs
     ``nested_clustering``): every cluster keeps its own prior volume and local evidence, and chains start in a cluster
     drawn by volume (PolyChord's bookkeeping); ``sampler_info["cluster_logZ"]`` and ``["cluster_parent"]`` map each cluster
-    id to its local evidence and its parent id (-1: the root).
+    id to its local evidence and its parent id (-1: the root).  ``nested_phantoms`` (None / 0: off; an int t >= 1): the
+    sampler also keeps every t-th interior state of its chains as a weighted phantom row
+    (``gpry_amd.nested.run_nested(phantom_thin=t)``): the pool grows by about num_repeats / t rows per new live point
+    at no further evaluation, its y goes to the sweep as before and the weights are the merged ones;
+    ``sampler_info["phantom_rows"]``, ``["phantom_thin"]`` and ``["logZ_merged"]`` report it and ``["rows"]`` counts all
+    rows.  Not together with ``nested_cluster_volumes`` (ValueError).
     """
 
     def __init__(self, bounds, preprocessing_X=None, verbose=1, acq_func="LogExp", sampler=None,
@@ -322,7 +327,7 @@ class NORA(GenericGPAcquisition):
                  num_repeats="5d", num_repeats_per_dim=None, precision_criterion_target=0.01,
                  nprior_per_nlive=10, max_ncalls=None, tmpdir=None, comm=None,
                  shortlist_size=None, gather_y="auto", devices=None, exact_prune=True,
-                 nested_batch=None, nested_clustering=False, nested_cluster_volumes=False):
+                 nested_batch=None, nested_clustering=False, nested_cluster_volumes=False, nested_phantoms=None):
         super().__init__(bounds=np.asarray(bounds), preprocessing_X=preprocessing_X,
                          verbose=verbose, acq_func=acq_func)
         self.log_header = f"[ACQUISITION : {self.__class__.__name__}] "
@@ -365,6 +370,14 @@ class NORA(GenericGPAcquisition):
         self.nested_cluster_volumes = bool(nested_cluster_volumes)
         if self.nested_cluster_volumes and not self.nested_clustering:
             raise ValueError("nested_cluster_volumes=True needs nested_clustering=True")
+        # every nested_phantoms-th interior state of the sampler's chains joins the pool (None: off)
+        if nested_phantoms is not None and (isinstance(nested_phantoms, bool) or int(nested_phantoms) != nested_phantoms
+                                            or int(nested_phantoms) < 0):
+            raise ValueError(f"nested_phantoms = {nested_phantoms!r} must be None, 0 or a thinning factor >= 1")
+        self.nested_phantoms = int(nested_phantoms) if nested_phantoms else None
+        if self.nested_phantoms and self.nested_cluster_volumes:
+            raise ValueError("nested_phantoms with nested_cluster_volumes=True: phantoms have no per-cluster birth "
+                             "volumes")
         self._X_already_proposed = np.empty((0, self.n_d))
         self.stats = {}
 
@@ -438,13 +451,19 @@ class NORA(GenericGPAcquisition):
         if self.nested_cluster_volumes:
             self.stats["sampler_info"]["cluster_logZ"] = {q: float(v) for q, v in enumerate(res.cluster_logZ)}
             self.stats["sampler_info"]["cluster_parent"] = {q: int(v) for q, v in enumerate(res.cluster_parent)}
+        if self.nested_phantoms:
+            self.stats["sampler_info"].update(phantom_rows=int(res.n_phantom), phantom_thin=self.nested_phantoms,
+                                              logZ_merged=float(res.logZ_merged))
         return res.X, res.y, None, res.w
 
     def _clustering_kw(self):
-        """run_nested's clustering arguments: passed only when on, so that the run's calls are those of before without."""
+        """run_nested's clustering and phantom arguments: passed only when on, so that the run's calls are those of
+        before without."""
         kw = {"clustering": True} if self.nested_clustering else {}
         if self.nested_cluster_volumes:
             kw["cluster_volumes"] = True
+        if self.nested_phantoms:
+            kw["phantom_thin"] = self.nested_phantoms
         return kw
 
     def _do_MC_sample_uniform(self, gpr, bounds=None, rng=None):

@@ -16,7 +16,7 @@ from gpry_amd.tools import generic_params_names, get_Xnumber
 # PolyChord's defaults (the Runner passes nlive = 50d)
 NESTED_DEFAULTS = {"nlive": "25d", "num_repeats": "5d", "precision_criterion": 0.001, "nprior": None, "max_ncalls": None}
 # options of the device nested sampler beyond PolyChord's settings: in nested_settings' result only when given
-NESTED_EXTRA = {"clustering": False, "cluster_volumes": False}
+NESTED_EXTRA = {"clustering": False, "cluster_volumes": False, "phantom_thin": None}
 # PolyChord's names of those options -> ours, for the warning that ignores them
 NESTED_RENAMED = {"do_clustering": "clustering"}
 # Cobaya's names where they exist -> run_mcmc's arguments
@@ -53,6 +53,13 @@ def nested_settings(d, sampler_options=None):
         out["cluster_volumes"] = bool(opts["cluster_volumes"])
         if out["cluster_volumes"] and not out.get("clustering"):
             raise ValueError("sampler option cluster_volumes=True needs clustering=True")
+    if opts.get("phantom_thin") is not None:
+        t = opts["phantom_thin"]
+        if isinstance(t, bool) or int(t) != t or int(t) < 1:
+            raise ValueError(f"sampler option phantom_thin = {t!r} must be an int >= 1")
+        if out.get("cluster_volumes"):
+            raise ValueError("sampler option phantom_thin is not available with cluster_volumes=True")
+        out["phantom_thin"] = int(t)
     return out
 
 
@@ -102,7 +109,8 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
 
     bounds: default ``gpr.trust_bounds``, else ``gpr.bounds`` (gpry/mc.py:381-382).  sampler: ``"nested"`` (options
     nlive, num_repeats, precision_criterion, nprior, max_ncalls; PolyChord's defaults 25d, 5d, 0.001, nlive; and
-    clustering, default False: a whitening matrix per cluster of the live set) or
+    clustering, default False: a whitening matrix per cluster of the live set; phantom_thin, default None: an int t
+    keeps every t-th interior state of the chains as a weighted phantom row, see ``run_nested``) or
     ``"mcmc"`` (options Rminus1_stop, temperature, covmat, max_samples -> max_ncalls, and run_mcmc's nchains,
     learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature).  Unknown options are warned
     about and ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.  The
@@ -122,7 +130,8 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
         res = run_nested(gpr.device, b, seed, s["nlive"], s["num_repeats"], precision_criterion=s["precision_criterion"],
                          nprior=s["nprior"], max_ncalls=s["max_ncalls"], minus_inf_value=gpr.minus_inf_value,
                          **({"clustering": True} if s.get("clustering") else {}),
-                         **({"cluster_volumes": True} if s.get("cluster_volumes") else {}))
+                         **({"cluster_volumes": True} if s.get("cluster_volumes") else {}),
+                         **({"phantom_thin": s["phantom_thin"]} if s.get("phantom_thin") else {}))
     else:
         from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
         s = mcmc_settings(d, sampler_options)

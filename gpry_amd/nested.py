@@ -13,7 +13,10 @@ for it (the CPU tests use a numpy one):
 
 With ``clustering=True`` it also calls ``dev.ns_knn(lo, hi, X, k) -> (nbr (n, k), device_ms)`` and passes
 ``labels=`` (with one W per cluster) to ``ns_generation``; with ``cluster_volumes=True`` as well, it passes ``cum_p=``
-(cumulative cluster probabilities) too.
+(cumulative cluster probabilities) too.  With ``phantom_thin`` it calls, in place of ``ns_generation``,
+
+``dev.ns_generation_phantoms(lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, thin, labels=None)
+    -> (X_new, y_new, ncalls, X_ph (k, n_ph, d), y_ph (k, n_ph), device_ms)``
 
 The algorithm, step by step:
 
@@ -36,6 +39,13 @@ The algorithm, step by step:
   point joins that cluster.  Z_live = sum_q X_q mean(L over q); the final live points of q get X_q / n_q each.  Every row records its
   cluster id; the local evidence of an id sums the weights of its rows, and a mode's evidence is the sum over its
   subtree (profiles/nested_volumes.md).
+* Phantoms (opt-in, ``phantom_thin``; after PolyChord's ``boost_posterior``): every thin-th interior state of a chain is
+  kept as well.  A chain starts from a live point, which is uniform in {L > L*}, and a slice-sampling step leaves that
+  distribution invariant, so every state is a (correlated) sample of the contour it was born in.  The run itself does
+  not see them: kills, thresholds, stopping, logZ, its error and the real rows are those of the run without.  They are
+  appended to the rows and all rows are weighted by ``merged_weights``, which treats the points like the threads of a
+  dynamic nested-sampling run (Higson et al. 2019): the live count becomes a function of the likelihood level.  Not
+  available together with ``cluster_volumes``: per-cluster birth volumes are not kept.
 * Stop when Z_live / Z < ``precision_criterion`` (Z_live = X mean(L_live), the PolyChord criterion) or, at the end of
   a generation, when the evaluation count has reached ``max_ncalls``.  The final live points get the volume X / n each.
 """
@@ -46,8 +56,8 @@ import numpy as np
 
 NestedResult = namedtuple("NestedResult", ["X", "y", "w", "logZ", "logZ_err", "ncalls", "ngen", "device_s",
                                            "wall_s", "dead_L", "dead_logX", "n_dead", "n_clusters", "cluster",
-                                           "cluster_logZ", "cluster_parent"],
-                          defaults=(None, None, None, None))
+                                           "cluster_logZ", "cluster_parent", "phantom", "logZ_merged", "n_phantom"],
+                          defaults=(None, None, None, None, None, None, None))
 NestedResult.__doc__ = """Output of ``run_nested``.  X, y, w: rows with a finite likelihood, dead points in the order they
 died then the final live points; w sums to 1.  logZ and its error sqrt(H / nlive); ncalls: evaluations of the surrogate;
 ngen: generations; device_s / wall_s: time in the device calls / in the whole run.  dead_L / dead_logX: log-likelihood
@@ -55,7 +65,10 @@ ngen: generations; device_s / wall_s: time in the device calls / in the whole ru
 cluster count of each generation (an int array) with clustering on, None without.  With cluster_volumes on (None
 without): cluster, the id of the cluster each row of X died or stayed live in; cluster_logZ, the local evidence of each
 id (log of the summed weights of its rows, unnormalised: their logsumexp is logZ); cluster_parent, each id's parent id
-(-1 for the root).  dead_logX is then the log of the summed volume of the open clusters."""
+(-1 for the root).  dead_logX is then the log of the summed volume of the open clusters.  With phantom_thin (None
+without): phantom, True for the rows that are phantoms (they follow the real rows, in (generation, chain, slot) order);
+logZ_merged, the evidence of the merged point set (``merged_weights``); n_phantom, the count of phantom rows.  w then
+comes from ``merged_weights`` and covers all rows; logZ and logZ_err remain those of the run."""
 
 # a run stops after this many generations whatever its other criteria say (a safeguard, never met in practice)
 MAX_GENERATIONS = 100000
@@ -191,12 +204,63 @@ def _logsumexp(a):
     return m + np.log(np.sum(np.exp(a - m)))
 
 
+def merged_weights(L, born, thr, L_end=None):
+    """Log weights of a point set in which every point is uniform in the contour it was born in: ``(logw (n,), logZ)``.
+
+    ``L`` (n,): log-likelihoods, -inf outside.  ``born`` (n,): the generation a point was born in, -1 for a prior point.
+    ``thr`` (G,): the threshold of each generation, non-decreasing; a point of generation g lies in {L > thr[g]} (or at
+    thr[g], where a plateau lets a chain stay on its start).  ``L_end``: points above it form the final set (default:
+    thr[-1], or -inf without generations).
+
+    All points, outside ones included, are ordered by (L, born, row index).  The point at position r (from 0) has the
+    live count n_r = B_r - r, where B_r = #prior + sum of m_g over the generations counted as born by then: those with
+    thr[g] < L_r and, among those with thr[g] == L_r, the ones with g <= born_r (m_g: the points born in g).  Ties in L
+    are thus broken by generation, and a generation whose threshold equals L_r is counted once the order has reached its
+    own points; every point sorted up to r then belongs to a counted generation, so n_r >= 1 also on a plateau of tied
+    values (a count is still clamped to 1, which only an outside start that never moved can need).  Points with
+    L <= L_end die in that order: log X_r = sum_{j <= r} log(n_j / (n_j + 1)), log w_r = L_r + log X_{r-1} -
+    log(n_r + 1).  The n_final points above L_end get X_end / n_final each.  Outside points weigh 0.  With one
+    generation's worth of new live points per threshold and no ties this is the run's own weighting."""
+    L = np.asarray(L, dtype=float)
+    born = np.asarray(born, dtype=np.int64)
+    thr = np.asarray(thr, dtype=float)
+    n, G = len(L), len(thr)
+    if born.shape != L.shape or (n and (born.min() < -1 or born.max() >= G)):
+        raise ValueError("born must hold one generation in -1 .. len(thr) - 1 per point")
+    if np.any(thr[1:] < thr[:-1]):
+        raise ValueError("thr must be non-decreasing")
+    if L_end is None:
+        L_end = thr[-1] if G else -np.inf
+    order = np.lexsort((np.arange(n), born, L))
+    Ls, bs = L[order], born[order]
+    cum_m = np.concatenate([[0], np.cumsum(np.bincount(born[born >= 0], minlength=G))])
+    below, upto = np.searchsorted(thr, Ls, side="left"), np.searchsorted(thr, Ls, side="right")
+    B = int(np.count_nonzero(born < 0)) + cum_m[np.maximum(below, np.minimum(upto, bs + 1))]
+    cnt = np.maximum(B - np.arange(n), 1).astype(float)
+    nd = int(np.searchsorted(Ls, L_end, side="right"))          # the first nd die in order
+    logX = np.cumsum(np.log(cnt[:nd] / (cnt[:nd] + 1.0)))
+    logX_prev = np.concatenate([[0.0], logX[:-1]])
+    logw_s = np.empty(n)
+    with np.errstate(invalid="ignore"):
+        logw_s[:nd] = Ls[:nd] + logX_prev - np.log(cnt[:nd] + 1.0)
+        if n > nd:
+            logw_s[nd:] = Ls[nd:] + (logX[-1] if nd else 0.0) - np.log(n - nd)
+    logw_s[~np.isfinite(Ls)] = -np.inf
+    logw = np.empty(n)
+    logw[order] = logw_s
+    return logw, float(_logsumexp(logw))
+
+
 def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, nprior=None, max_ncalls=None,
-               batch=None, minus_inf_value=-np.inf, clustering=False, cluster_k_max=None, cluster_volumes=False):
+               batch=None, minus_inf_value=-np.inf, clustering=False, cluster_k_max=None, cluster_volumes=False,
+               phantom_thin=None):
     """Nested sampling run of the surrogate on ``dev``; see the module's docstring.  Returns a ``NestedResult``.
     ``clustering``: a whitening matrix per cluster of the survivors (``knn_clusters`` with neighbour tables of up to
     ``cluster_k_max`` points, default ``DEFAULT_CLUSTER_K_MAX``).  ``cluster_volumes`` (needs ``clustering``): every
-    cluster keeps its own prior volume and local evidence, and chains start in a cluster drawn by volume."""
+    cluster keeps its own prior volume and local evidence, and chains start in a cluster drawn by volume.
+    ``phantom_thin`` (None: off; an int >= 1): keep every thin-th interior state of the chains as a weighted phantom row
+    (``dev.ns_generation_phantoms``); the run is the one without, the rows grow and ``w`` comes from ``merged_weights``.
+    Not together with ``cluster_volumes`` (ValueError): the phantoms' per-cluster birth volumes are not kept."""
     t_start = time()
     bounds = np.asarray(bounds, dtype=float)
     lo, hi = np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
@@ -213,6 +277,12 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
     k_max = DEFAULT_CLUSTER_K_MAX if cluster_k_max is None else int(cluster_k_max)
     if clustering and not 2 <= k_max <= 32:
         raise ValueError(f"cluster_k_max = {k_max} must lie in 2 .. 32")
+    if phantom_thin is not None:
+        if isinstance(phantom_thin, bool) or int(phantom_thin) != phantom_thin or int(phantom_thin) < 1:
+            raise ValueError(f"phantom_thin = {phantom_thin!r} must be an int >= 1 (or None)")
+        phantom_thin = int(phantom_thin)
+        if cluster_volumes:
+            raise ValueError("phantom_thin with cluster_volumes=True: phantoms have no per-cluster birth volumes")
     if cluster_volumes:
         if not clustering:
             raise ValueError("cluster_volumes=True needs clustering=True")
@@ -227,6 +297,10 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
     L = _logL(y, minus_inf_value)
     dead_X, dead_y, dead_L, dead_logw, dead_logX = [], [], [], [], []
     logX = 0.0
+    # phantoms: the generation every live / dead point was born in (-1: prior), each generation's threshold and phantoms
+    ph = phantom_thin is not None
+    born = np.full(nprior, -1, np.int64)
+    dead_born, thrs, ph_X, ph_y = [], [], [], []
 
     def kill(idx, Xl, yl, Ll, logX):
         """idx: positions of the removed points in ascending order; returns the new log volume."""
@@ -249,7 +323,8 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
         order = order_of(L)
         logX = kill(order[:nprior - nlive], X, y, L, logX)
         keep = np.sort(order[nprior - nlive:])
-        X, y, L = X[keep], y[keep], L[keep]
+        dead_born.append(born[order[:nprior - nlive]])
+        X, y, L, born = X[keep], y[keep], L[keep], born[keep]
     gen = 0
     while True:
         logZ_dead = _logsumexp(np.concatenate(dead_logw)) if dead_logw else -np.inf
@@ -269,9 +344,17 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
         Us = (Xs - lo) / (hi - lo)
         # an outside point is never accepted: with a finite minus_inf_value the threshold is at least that value
         thr = lstar if not np.isfinite(minus_inf_value) else max(lstar, float(minus_inf_value))
+        if ph:
+            dead_born.append(born[rem])
+            born = np.concatenate([born[keep], np.full(k_gen, gen, np.int64)])
+            thrs.append(thr)
         if not clustering:
             W = whitening(Us)
-            Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats)
+            if ph:
+                Xn, yn, cnt, Xp, yp, ms = dev.ns_generation_phantoms(lo, hi, Xs, ys, thr, W, seed, gen, k_gen,
+                                                                     num_repeats, phantom_thin)
+            else:
+                Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats)
         else:
             if len(Xs) >= 3:
                 nbr, ms = dev.ns_knn(lo, hi, Xs, min(k_max, len(Xs) - 1))
@@ -281,7 +364,14 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
                 labels, nc = np.zeros(len(Xs), np.int32), 1
             W = np.stack([whitening(Us[labels == q]) for q in range(nc)])
             n_clusters.append(nc)
-            Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats, labels=labels)
+            if ph:
+                Xn, yn, cnt, Xp, yp, ms = dev.ns_generation_phantoms(lo, hi, Xs, ys, thr, W, seed, gen, k_gen,
+                                                                     num_repeats, phantom_thin, labels=labels)
+            else:
+                Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats, labels=labels)
+        if ph:
+            ph_X.append(np.asarray(Xp, dtype=float).reshape(-1, len(lo)))
+            ph_y.append(np.asarray(yp, dtype=float).reshape(-1))
         device_ms += ms
         ncalls += int(np.sum(cnt))
         X = np.concatenate([Xs, Xn])
@@ -303,13 +393,38 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
         w = p / np.sum(p)
     else:
         H, w = 0.0, np.zeros(int(fin.sum()))
-    return NestedResult(X=np.ascontiguousarray(all_X[fin]), y=np.ascontiguousarray(all_y[fin]), w=w, logZ=float(logZ),
+    rows_X, rows_y, extra = all_X[fin], all_y[fin], {}
+    if ph:
+        # the real rows, then the phantoms in (generation, chain, slot) order; all of them weighted as one merged run
+        d = len(lo)
+        Xp = np.concatenate(ph_X) if ph_X else np.empty((0, d))
+        yp = np.concatenate(ph_y) if ph_y else np.empty(0)
+        per_gen = len(ph_y[0]) if ph_y else 0
+        Lp = _logL(yp, minus_inf_value)
+        m_L = np.concatenate([all_L, Lp])
+        m_born = np.concatenate(dead_born + [born, np.repeat(np.arange(gen, dtype=np.int64), per_gen)])
+        n_dead_all = len(all_L) - len(L)
+        L_end = float(all_L[n_dead_all - 1]) if n_dead_all else -np.inf
+        logw_m, logZ_m = merged_weights(m_L, m_born, np.array(thrs, dtype=float), L_end=L_end)
+        fin_m = np.isfinite(m_L)
+        if np.isfinite(logZ_m):
+            w = np.exp(logw_m[fin_m] - logZ_m)
+            w = w / np.sum(w)
+        else:
+            w = np.zeros(int(fin_m.sum()))
+        fin_p = fin_m[len(all_L):]
+        rows_X = np.concatenate([rows_X, Xp[fin_p]])
+        rows_y = np.concatenate([rows_y, yp[fin_p]])
+        flag = np.zeros(len(rows_y), bool)
+        flag[int(fin.sum()):] = True
+        extra = dict(phantom=flag, logZ_merged=logZ_m, n_phantom=int(fin_p.sum()))
+    return NestedResult(X=np.ascontiguousarray(rows_X), y=np.ascontiguousarray(rows_y), w=w, logZ=float(logZ),
                         logZ_err=float(np.sqrt(max(H, 0.0) / nlive)), ncalls=int(ncalls), ngen=gen,
                         device_s=device_ms / 1e3, wall_s=time() - t_start,
                         dead_L=np.concatenate(dead_L) if dead_L else np.empty(0),
                         dead_logX=np.concatenate(dead_logX) if dead_logX else np.empty(0),
                         n_dead=int(sum(len(a) for a in dead_y)),
-                        n_clusters=np.array(n_clusters, dtype=np.int64) if clustering else None)
+                        n_clusters=np.array(n_clusters, dtype=np.int64) if clustering else None, **extra)
 
 
 def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls, minus_inf_value,

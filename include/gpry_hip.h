@@ -274,6 +274,26 @@ int gpry_ns_generation_volumes(gpry_ctx* ctx, const double* lo, const double* hi
                                const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
                                int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
                                const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, double* device_ms);
+/* gpry_ns_generation_phantoms: a generation that also keeps the chains' interior states (PolyChord's phantom points).
+ *   The arguments of gpry_ns_generation_volumes with labels / cum_p nullable -- both NULL: the chains of
+ *   gpry_ns_generation (n_clusters is then not read, W is d x d); labels alone: those of gpry_ns_generation_clustered;
+ *   both: those of gpry_ns_generation_volumes -- and thin >= 1, X_ph, y_ph.  n_ph = (num_repeats - 1) / thin (0 for
+ *   num_repeats = 0).  After step s (from 0) with (s + 1) % thin == 0 and s + 1 < num_repeats chain c's state and its y go
+ *   to X_ph[(c n_ph + i) d ..] and y_ph[c n_ph + i], i = (s + 1) / thin - 1 (X_ph: k x n_ph x d, y_ph: k x n_ph,
+ *   row-major); the last state is X_new as before and is not a phantom.  A chain whose step kept its point records that
+ *   point again.  No draw, evaluation or counter is added or moved.  Hence, bit for bit:
+ *   - X_new, y_new and ncalls equal those of the matching entry point above with the same arguments;
+ *   - slot i of chain c equals X_new / y_new of chain c of that entry point called with num_repeats = (i + 1) thin;
+ *   - every y_ph is gpry_predict of its row alone, and exceeds lstar unless the chain never moved.
+ *   X_ph and y_ph both NULL: nothing is recorded (thin is still checked).  Refused (-1) before anything runs: thin < 1;
+ *   exactly one of X_ph / y_ph NULL; X_ph and y_ph together above 2^30 bytes (8 k n_ph (d + 1)); and what the entry
+ *   points above refuse.  The states are written to a device buffer of the context, which grows on demand, and copied
+ *   out at the end; device_ms includes that copy. */
+int gpry_ns_generation_phantoms(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
+                                const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                                int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
+                                const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, int thin, double* X_ph,
+                                double* y_ph, double* device_ms);
 /* gpry_ns_knn: the k nearest other points of each of the n points X (n x d) in unit-cube coordinates
  *   u = (x - lo) / (hi - lo): nbr_out (n x k, row-major) holds row i's neighbours in order of (squared distance, index),
  *   i itself excluded, ties (duplicated points) broken by the index.  The squared distance is the sum over the
