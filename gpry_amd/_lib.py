@@ -413,14 +413,10 @@ class Device:
                                             C.byref(ms)), "gpry_ns_prior")
         return X, y, ms.value
 
-    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels=None,
-                      cum_p=None):
-        """One generation of ``k`` slice-sampling chains above ``lstar``: ``(X_new (k, d), y_new (k,), ncalls (k,),
-        device_ms)``.  ``W`` (d, d) is lower triangular (``nested.whitening`` / ``cholesky_ridged`` deliver one): the
-        direction is tril(W) z / |z|, entries above the diagonal are not read.  ``labels`` (nsurv cluster numbers) with ``W`` of shape (n_clusters, d, d): every chain walks with
-        the matrix of its starting survivor's cluster (gpry_ns_generation_clustered).  With ``cum_p`` (n_clusters
-        cumulative probabilities, the last 1.0) as well, every chain first draws its cluster from cum_p and then its
-        start among that cluster's survivors (gpry_ns_generation_volumes)."""
+    def _ns_generate(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels, cum_p, thin=None):
+        """One generation call: checks the arguments, picks the entry point from (labels, cum_p, thin) -- plain,
+        _clustered, _volumes; _phantoms whenever ``thin`` is given -- and returns ``(X_new, y_new, ncalls, X_ph, y_ph,
+        device_ms)``, X_ph and y_ph None without ``thin``."""
         if cum_p is not None and labels is None:
             raise ValueError("cum_p needs labels")
         lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
@@ -429,51 +425,7 @@ class Device:
         if X_surv.ndim != 2 or X_surv.shape[1] != self.d:
             raise ValueError(f"expected survivors of shape (n, {self.d}), got {X_surv.shape}")
         y_surv = _f64(y_surv, (n,))
-        X_new, y_new, cnt, ms = np.empty((int(k), self.d)), np.empty(int(k)), np.zeros(int(k), np.int64), C.c_double(0.0)
-        if labels is None:
-            W = _f64(W, (self.d, self.d))
-            self._check(self._lib.gpry_ns_generation(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
-                                                     float(lstar), _ptr(W), int(seed), int(generation), int(k),
-                                                     int(num_repeats), _ptr(X_new), _ptr(y_new), _ptr(cnt),
-                                                     C.byref(ms)), "gpry_ns_generation")
-            return X_new, y_new, cnt, ms.value
-        W = _f64(W)
-        if W.ndim != 3 or W.shape[1:] != (self.d, self.d):
-            raise ValueError(f"expected W of shape (n_clusters, {self.d}, {self.d}), got {W.shape}")
-        lab = np.ascontiguousarray(labels, dtype=np.int32)
-        if lab.shape != (n,):
-            raise ValueError(f"expected {n} labels, got shape {lab.shape}")
-        if cum_p is not None:
-            cp = _f64(cum_p, (W.shape[0],))
-            self._check(self._lib.gpry_ns_generation_volumes(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
-                                                             float(lstar), _ptr(W), int(seed), int(generation), int(k),
-                                                             int(num_repeats), _ptr(lab), int(W.shape[0]), _ptr(cp),
-                                                             _ptr(X_new), _ptr(y_new), _ptr(cnt), C.byref(ms)),
-                        "gpry_ns_generation_volumes")
-            return X_new, y_new, cnt, ms.value
-        self._check(self._lib.gpry_ns_generation_clustered(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
-                                                           float(lstar), _ptr(W), int(seed), int(generation), int(k),
-                                                           int(num_repeats), _ptr(lab), int(W.shape[0]), _ptr(X_new),
-                                                           _ptr(y_new), _ptr(cnt), C.byref(ms)),
-                    "gpry_ns_generation_clustered")
-        return X_new, y_new, cnt, ms.value
-
-    def ns_generation_phantoms(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, thin,
-                               labels=None, cum_p=None):
-        """``ns_generation`` that also keeps the chains' interior states: ``(X_new (k, d), y_new (k,), ncalls (k,), X_ph
-        (k, n_ph, d), y_ph (k, n_ph), device_ms)``, n_ph = (num_repeats - 1) // thin.  Slot i of chain c is its state
-        after step (i + 1) thin; the last state is X_new and is not among them.  X_new, y_new and ncalls are those of
-        ``ns_generation`` with the same arguments, bit for bit (gpry_ns_generation_phantoms)."""
-        if cum_p is not None and labels is None:
-            raise ValueError("cum_p needs labels")
-        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
-        X_surv = _f64(X_surv)
-        n = X_surv.shape[0]
-        if X_surv.ndim != 2 or X_surv.shape[1] != self.d:
-            raise ValueError(f"expected survivors of shape (n, {self.d}), got {X_surv.shape}")
-        y_surv = _f64(y_surv, (n,))
-        k, num_repeats, thin = int(k), int(num_repeats), int(thin)
-        n_ph = max(num_repeats - 1, 0) // max(thin, 1)          # (thin < 1 is refused by the library)
+        k, num_repeats = int(k), int(num_repeats)
         lab = cp = None
         nc = 1
         if labels is None:
@@ -489,13 +441,45 @@ class Device:
             if cum_p is not None:
                 cp = _f64(cum_p, (nc,))
         X_new, y_new, cnt, ms = np.empty((k, self.d)), np.empty(k), np.zeros(k, np.int64), C.c_double(0.0)
-        X_ph, y_ph = np.empty((k, n_ph, self.d)), np.empty((k, n_ph))
-        self._check(self._lib.gpry_ns_generation_phantoms(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n,
-                                                          float(lstar), _ptr(W), int(seed), int(generation), k,
-                                                          num_repeats, _ptr(lab), nc, _ptr(cp), _ptr(X_new), _ptr(y_new),
-                                                          _ptr(cnt), thin, _ptr(X_ph), _ptr(y_ph), C.byref(ms)),
-                    "gpry_ns_generation_phantoms")
+        X_ph = y_ph = None
+        out = [_ptr(X_new), _ptr(y_new), _ptr(cnt)]
+        if thin is not None:
+            thin = int(thin)
+            n_ph = max(num_repeats - 1, 0) // max(thin, 1)          # (thin < 1 is refused by the library)
+            X_ph, y_ph = np.empty((k, n_ph, self.d)), np.empty((k, n_ph))
+            name, own = "gpry_ns_generation_phantoms", [_ptr(lab), nc, _ptr(cp)]
+            out += [thin, _ptr(X_ph), _ptr(y_ph)]
+        elif lab is None:
+            name, own = "gpry_ns_generation", []
+        elif cp is None:
+            name, own = "gpry_ns_generation_clustered", [_ptr(lab), nc]
+        else:
+            name, own = "gpry_ns_generation_volumes", [_ptr(lab), nc, _ptr(cp)]
+        # (every entry point: the common arguments, its own, the outputs)
+        self._check(getattr(self._lib, name)(self._h, _ptr(lo), _ptr(hi), _ptr(X_surv), _ptr(y_surv), n, float(lstar),
+                                             _ptr(W), int(seed), int(generation), k, num_repeats, *own, *out,
+                                             C.byref(ms)), name)
         return X_new, y_new, cnt, X_ph, y_ph, ms.value
+
+    def ns_generation(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels=None,
+                      cum_p=None):
+        """One generation of ``k`` slice-sampling chains above ``lstar``: ``(X_new (k, d), y_new (k,), ncalls (k,),
+        device_ms)``.  ``W`` (d, d) is lower triangular (``nested.whitening`` / ``cholesky_ridged`` deliver one): the
+        direction is tril(W) z / |z|, entries above the diagonal are not read.  ``labels`` (nsurv cluster numbers) with
+        ``W`` of shape (n_clusters, d, d): every chain walks with the matrix of its starting survivor's cluster
+        (gpry_ns_generation_clustered).  With ``cum_p`` (n_clusters cumulative probabilities, the last 1.0) as well,
+        every chain first draws its cluster from cum_p and then its start among that cluster's survivors
+        (gpry_ns_generation_volumes)."""
+        out = self._ns_generate(lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels, cum_p)
+        return out[:3] + out[5:]
+
+    def ns_generation_phantoms(self, lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, thin,
+                               labels=None, cum_p=None):
+        """``ns_generation`` that also keeps the chains' interior states: ``(X_new (k, d), y_new (k,), ncalls (k,), X_ph
+        (k, n_ph, d), y_ph (k, n_ph), device_ms)``, n_ph = (num_repeats - 1) // thin.  Slot i of chain c is its state
+        after step (i + 1) thin; the last state is X_new and is not among them.  X_new, y_new and ncalls are those of
+        ``ns_generation`` with the same arguments, bit for bit (gpry_ns_generation_phantoms)."""
+        return self._ns_generate(lo, hi, X_surv, y_surv, lstar, W, seed, generation, k, num_repeats, labels, cum_p, thin)
 
     def ns_knn(self, lo, hi, X, k):
         """The ``k`` nearest other points of every row of ``X`` in unit-cube coordinates, in order of (squared distance,

@@ -232,11 +232,11 @@ struct gpry_ctx {
     int64_t xg_cap = 0;                // doubles
     int64_t* dgidx = nullptr;          // their pool indices
     int64_t gidx_cap = 0;
-    char* dmc = nullptr;               // gpry_mcmc_chains: start states, proposal factor and outputs (bytes)
+    uint8_t* dmc = nullptr;            // gpry_mcmc_chains: start states, proposal factor and outputs (bytes)
     int64_t mc_cap = 0;
-    char* dknn = nullptr;              // gpry_ns_knn: transposed unit-cube points and the neighbour table (bytes)
+    uint8_t* dknn = nullptr;           // gpry_ns_knn: transposed unit-cube points and the neighbour table (bytes)
     int64_t knn_cap = 0;
-    char* dph = nullptr;               // gpry_ns_generation_phantoms: the chains' recorded states and their y (bytes)
+    uint8_t* dph = nullptr;            // gpry_ns_generation_phantoms: the chains' recorded states and their y (bytes)
     int64_t ph_cap = 0;
 
     // host pinned staging

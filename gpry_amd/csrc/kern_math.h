@@ -163,7 +163,17 @@ static AffParams make_ap(gpry_ctx* ctx, bool use_affine) {
         case GPRY_MATERN32: { CALL(GPRY_MATERN32); break; } \
         default: { CALL(GPRY_MATERN52); break; }        \
     }
-
+// the samplers' instantiations: CALL(DP, KID) with DP the smallest of 4 / 8 / 16 / 32 that holds d
+#define DISPATCH_DP_(d, CALL, KID)                                          \
+    if ((d) <= 4) { CALL(4, KID); } else if ((d) <= 8) { CALL(8, KID); }    \
+    else if ((d) <= 16) { CALL(16, KID); } else { CALL(32, KID); }
+#define DISPATCH_DP_KID(d, kid, CALL)                                       \
+    switch (kid) {                                                          \
+        case GPRY_RBF: { DISPATCH_DP_(d, CALL, GPRY_RBF) break; }           \
+        case GPRY_MATERN12: { DISPATCH_DP_(d, CALL, GPRY_MATERN12) break; } \
+        case GPRY_MATERN32: { DISPATCH_DP_(d, CALL, GPRY_MATERN32) break; } \
+        default: { DISPATCH_DP_(d, CALL, GPRY_MATERN52) break; }            \
+    }
 
 // ------------------------------------------------------------------------------------
 // One slice of the posterior mean of ONE point: sum over the training rows [row_lo, row_lo + rows_per_split) of

@@ -7,7 +7,7 @@
 // Likelihood.  ns_eval of ns_common.h: gpr.predict(x[None]) bit for bit, gates included (-inf where they reject).
 //
 // Randomness.  ns_philox with phase 3: step s of chain c in call `batch` takes the counters (3, draw j, batch, c, s);
-// draws 0..15 give z ~ N(0, I) by Box-Muller (coordinates 2j and 2j + 1 from draw j, as ns_chain_kernel does), draw 16
+// draws 0..15 give z ~ N(0, I) by Box-Muller (ns_box_muller of ns_common.h, which ns_chain_kernel calls too), draw 16
 // gives the acceptance uniform ua.  No value depends on how many chains share a launch or on the workgroup schedule.
 //
 // Chains.  One 256-thread workgroup per chain, `nsteps` Metropolis steps inside the kernel.  Coordinates are the unit
@@ -54,12 +54,7 @@ __global__ __launch_bounds__(256) void mcmc_chain_kernel(NsArgs a, KernParams kp
         n_eval++;
     }
     for (int s = 0; s < nsteps; s++) {
-        if (t < (d + 1) / 2) {
-            const NsU2 u = ns_philox(a.seed, MC_PHASE, (unsigned)t, batch, c, (unsigned)s);
-            const double rad = sqrt(-2.0 * log(1.0 - u.a)), ang = 6.283185307179586 * u.b;
-            s_z[2 * t] = rad * cos(ang);
-            if (2 * t + 1 < d) s_z[2 * t + 1] = rad * sin(ang);
-        }
+        if (t < (d + 1) / 2) ns_box_muller(s_z, t, d, ns_philox(a.seed, MC_PHASE, (unsigned)t, batch, c, (unsigned)s));
         __syncthreads();
         if (t < d) {
             double v = 0.0;
@@ -102,15 +97,6 @@ __global__ __launch_bounds__(256) void mcmc_chain_kernel(NsArgs a, KernParams kp
     if (t == 0) { y_last[c] = y_cur; naccept[c] = n_acc; ncalls[c] = n_eval; }
 }
 
-static int ensure_mc(gpry_ctx* ctx, int64_t bytes) {
-    if (bytes <= ctx->mc_cap) return 0;
-    if (ctx->dmc) HIP_TRY(ctx, hipFree(ctx->dmc));
-    ctx->dmc = nullptr; ctx->mc_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->dmc, (size_t)bytes));
-    ctx->mc_cap = bytes;
-    return 0;
-}
-
 extern "C" {
 
 int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0,
@@ -136,8 +122,8 @@ int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const do
     // one buffer: [X0 | y0 | Lp | records X | records y | last X | last y | accepted | evaluations | proposals X | their y]
     const int64_t sz[11] = {8 * n * d, 8 * n, 8 * (int64_t)d * d, 8 * n * nrec * d, 8 * n * nrec, 8 * n * d, 8 * n, 8 * n,
                             8 * n, 8 * hook * n * nsteps * d, 8 * hook * n * nsteps};
-    int64_t off[12] = {0};
-    for (int i = 0; i < 11; i++) off[i + 1] = off[i] + round_up(sz[i], 256);
+    int64_t off[12];
+    ns_layout(sz, off);
     const bool mapped = ctx->opt_mcmc_mapped != 0;
     char *h = nullptr, *b = nullptr;
     if (mapped) {
@@ -151,8 +137,8 @@ int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const do
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
     if (!mapped) {
-        GPRY_TRY(ensure_mc(ctx, off[11]));
-        b = ctx->dmc;
+        GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[11]));
+        b = (char*)ctx->dmc;
         HIP_TRY(ctx, hipMemcpyAsync(b + off[0], X0, sz[0], hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(b + off[1], y0, sz[1], hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(b + off[2], Lp, sz[2], hipMemcpyHostToDevice, ctx->stream));
@@ -171,18 +157,7 @@ int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const do
 #define MC(DP, KID) hipLaunchKernelGGL((mcmc_chain_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, \
                                        ap, dX0, dy0, dL, T, minus_inf_value, (unsigned)batch, nsteps, thin, dXr, dyr, dXl, \
                                        dyl, dna, dnc, dXp, dyp)
-#define MC_4(KID) MC(4, KID)
-#define MC_8(KID) MC(8, KID)
-#define MC_16(KID) MC(16, KID)
-#define MC_32(KID) MC(32, KID)
-    if (d <= 4) { DISPATCH_KID(ctx->kernel_id, MC_4) }
-    else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, MC_8) }
-    else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, MC_16) }
-    else { DISPATCH_KID(ctx->kernel_id, MC_32) }
-#undef MC_4
-#undef MC_8
-#undef MC_16
-#undef MC_32
+    DISPATCH_DP_KID(d, ctx->kernel_id, MC)
 #undef MC
     if (!mapped) {
         HIP_TRY(ctx, hipGetLastError());

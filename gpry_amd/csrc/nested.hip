@@ -28,6 +28,10 @@
 // Phantoms.  gpry_ns_generation_phantoms also keeps the chains' interior states: the state after every thin-th step but
 // the last goes to X_ph / y_ph (PolyChord's phantom points).  The recording is a template flag of the chain kernel: no
 // draw, evaluation or barrier is added, and without it the kernel is the instantiation of before.
+//
+// Host side.  The four gpry_ns_generation* entry points fill in an NsGenRequest by name; ns_generation_impl checks it
+// (ns_check), lays out one pinned buffer (ns_layout of ns_common.h over the NS_* regions), fills it (ns_members: the
+// clusters' member lists), launches (ns_launch_chains) and copies back.
 #include <climits>
 #include <vector>
 
@@ -70,13 +74,14 @@ __global__ __launch_bounds__(256) void ns_prior_kernel(NsArgs a, KernParams kp, 
 
 // One generation: chain c starts from a survivor drawn uniformly (counter (START, 0, gen, c, 0)) and makes
 // `num_repeats` slice-sampling steps on {x in the box : y(x) > lstar}.  Step s: direction v = W z / |z| (with labels: W of
-// the start's cluster, W + labels[j] d d), z ~ N(0, I) by
-// Box-Muller from draws 0..(d-1)/2; the interval [-r, 1 - r] along v (r: draw 16) stepped out by whole widths, at most
-// 32 per side (a side that reaches 32 widths stops growing and the step goes on to shrink from the interval it has); then
-// up to 64 shrinkage tries (draws 17..), each uniform on the interval, a failed try at t moving the end on t's side of
-// the current point (t < 0: the left one).  A step whose 64 tries all fail keeps the current point.  A try outside the
-// box fails without an evaluation.  W is lower triangular: the sum over k stops at the row's index, what lies above the
-// diagonal is never read.  tests/tools/sampler_walk.py restates the walk step by step.  Outputs: the chain's last point, its y and the number of evaluations it made.
+// the start's cluster, W + labels[j] d d), z ~ N(0, I) from draws 0..(d-1)/2 (ns_box_muller); the interval [-r, 1 - r]
+// along v (r: draw 16) stepped out by whole widths, at most 32 per side (a side that reaches 32 widths stops growing and
+// the step goes on to shrink from the interval it has); then up to 64 shrinkage tries (draws 17..), each uniform on the
+// interval, a failed try at t moving the end on t's side of the current point (t < 0: the left one).  A step whose 64
+// tries all fail keeps the current point.  A try outside the box fails without an evaluation.  W is lower
+// triangular: the sum over k stops at the row's index, what lies above the diagonal is never read.
+// tests/tools/sampler_walk.py restates the walk step by step.  Outputs: the chain's last point, its y and the number of
+// evaluations it made.
 // With a member list (volumes): chain c first draws its cluster q, the first q with u1 < cum_p[q] (u1: counter
 // (START, 1, gen, c, 0)), then its start members[moffs[q] + min(floor(u0 n_q), n_q - 1)] from the same u0 as above
 // (n_q = moffs[q + 1] - moffs[q]), and walks with W + q d d.  The host guarantees cum_p[n_clusters - 1] = 1.0 and
@@ -148,12 +153,7 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(NsArgs a, KernParams kp, 
     };
     for (int s = 0; s < num_repeats; s++) {
         // direction
-        if (t < (d + 1) / 2) {
-            const NsU2 u = ns_philox(a.seed, NS_PHASE_STEP, (unsigned)t, gen, c, (unsigned)s);
-            const double rad = sqrt(-2.0 * log(1.0 - u.a)), ang = 6.283185307179586 * u.b;
-            s_z[2 * t] = rad * cos(ang);
-            if (2 * t + 1 < d) s_z[2 * t + 1] = rad * sin(ang);
-        }
+        if (t < (d + 1) / 2) ns_box_muller(s_z, t, d, ns_philox(a.seed, NS_PHASE_STEP, (unsigned)t, gen, c, (unsigned)s));
         __syncthreads();
         double nz = 0.0;
         for (int k = 0; k < d; k++) nz += s_z[k] * s_z[k];
@@ -262,19 +262,40 @@ __global__ __launch_bounds__(256) void ns_knn_kernel(const double* __restrict__ 
     }
 }
 
-static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, const double* hi, const double* X_surv,
-                              const double* y_surv, int64_t nsurv, double lstar, const double* W, const int32_t* labels,
-                              int n_clusters, const double* cum_p, uint64_t seed, int64_t generation, int k,
-                              int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms,
-                              int thin = 1, double* X_ph = nullptr, double* y_ph = nullptr) {
-    if (!lo || !hi || !X_surv || !y_surv || !W || !X_new || !y_new || !ncalls)
+// ---- one generation -------------------------------------------------------------------------------------------------
+// What a generation is asked to do: the four gpry_ns_generation* entry points fill it in by name.
+struct NsGenRequest {
+    const char* who = nullptr;          // the entry point's name, for the messages
+    bool need_labels = false, need_cum_p = false;      // the entry point requires them (the others take NULL for none)
+    const double *lo = nullptr, *hi = nullptr, *X_surv = nullptr, *y_surv = nullptr, *W = nullptr;
+    int64_t nsurv = 0, generation = 0; double lstar = 0.0; uint64_t seed = 0; int k = 0, num_repeats = 0;
+    // clusters (labels NULL: none, one W); with cum_p the chains draw their cluster first
+    const int32_t* labels = nullptr; int n_clusters = 1; const double* cum_p = nullptr;
+    // phantoms (X_ph NULL: none)
+    int thin = 1; double *X_ph = nullptr, *y_ph = nullptr;
+    // outputs
+    double *X_new = nullptr, *y_new = nullptr, *device_ms = nullptr; int64_t* ncalls = nullptr;
+};
+
+// The regions of a generation's pinned, mapped buffer, in this order.  NS_LAB is used with labels alone; with cum_p the
+// kernel reads the member lists NS_MEM / NS_MOF and NS_CP instead; a region that is not used has no bytes.
+enum { NS_XS, NS_YS, NS_W, NS_LAB, NS_MEM, NS_MOF, NS_CP, NS_XN, NS_YN, NS_CNT, NS_REGIONS };
+
+static int ns_check(gpry_ctx* ctx, const NsGenRequest& rq) {
+    const char* who = rq.who;
+    const int32_t* labels = rq.labels; const double* cum_p = rq.cum_p;
+    const int64_t nsurv = rq.nsurv; const int n_clusters = rq.n_clusters;
+    if (!ctx) return gpry_fail(nullptr, -1, "%s: ctx is NULL", who);
+    if ((rq.need_labels && !labels) || (rq.need_cum_p && !cum_p)) return gpry_fail(ctx, -1, "%s: NULL argument", who);
+    if (cum_p && nsurv > INT_MAX) return gpry_fail(ctx, -1, "%s: nsurv = %lld", who, (long long)nsurv);  // (int32 lists)
+    if (!rq.lo || !rq.hi || !rq.X_surv || !rq.y_surv || !rq.W || !rq.X_new || !rq.y_new || !rq.ncalls)
         return gpry_fail(ctx, -1, "%s: NULL argument", who);
-    if (thin < 1) return gpry_fail(ctx, -1, "%s: thin = %d", who, thin);
-    if ((X_ph == nullptr) != (y_ph == nullptr))
+    if (rq.thin < 1) return gpry_fail(ctx, -1, "%s: thin = %d", who, rq.thin);
+    if ((rq.X_ph == nullptr) != (rq.y_ph == nullptr))
         return gpry_fail(ctx, -1, "%s: X_ph and y_ph are both NULL or both given", who);
-    if (nsurv < 1 || k < 0 || num_repeats < 0 || generation < 0 || generation > 0xffffffffll)
+    if (nsurv < 1 || rq.k < 0 || rq.num_repeats < 0 || rq.generation < 0 || rq.generation > 0xffffffffll)
         return gpry_fail(ctx, -1, "%s: nsurv = %lld, k = %d, num_repeats = %d, generation = %lld", who,
-                         (long long)nsurv, k, num_repeats, (long long)generation);
+                         (long long)nsurv, rq.k, rq.num_repeats, (long long)rq.generation);
     if (labels) {
         if (n_clusters < 1 || n_clusters > nsurv)
             return gpry_fail(ctx, -1, "%s: n_clusters = %d for %lld survivors", who, n_clusters, (long long)nsurv);
@@ -297,114 +318,104 @@ static int ns_generation_impl(gpry_ctx* ctx, const char* who, const double* lo, 
                 return gpry_fail(ctx, -1, "%s: cluster %d has probability %.17g and no survivor", who, q,
                                  cum_p[q] - (q ? cum_p[q - 1] : 0.0));
     }
+    return 0;
+}
+
+// each cluster's survivors in their order in X_surv (a counting sort, stable by index): those of cluster q are
+// mem[mof[q] .. mof[q + 1])
+static void ns_members(const int32_t* labels, int64_t nsurv, int n_clusters, int32_t* mem, int32_t* mof) {
+    for (int q = 0; q <= n_clusters; q++) mof[q] = 0;
+    for (int64_t i = 0; i < nsurv; i++) mof[labels[i] + 1]++;
+    for (int q = 0; q < n_clusters; q++) mof[q + 1] += mof[q];
+    std::vector<int32_t> fill(mof, mof + n_clusters);
+    for (int64_t i = 0; i < nsurv; i++) mem[fill[labels[i]]++] = (int32_t)i;
+}
+
+// the chain kernel of the context's (DP, KID), recording (PH) iff there is a phantom buffer, on the regions at `hd`
+static void ns_launch_chains(gpry_ctx* ctx, const NsGenRequest& rq, const NsArgs& a, const KernParams& kp,
+                             const AffParams& ap, char* hd, const int64_t* off, int nw, int n_ph, double* dXp, double* dyp) {
+    const bool lists = rq.cum_p != nullptr;
+    const int* dlab = rq.labels && !lists ? (const int*)(hd + off[NS_LAB]) : nullptr;
+    const int* dmem = lists ? (const int*)(hd + off[NS_MEM]) : nullptr;
+    const int* dmof = lists ? (const int*)(hd + off[NS_MOF]) : nullptr;
+    const double* dcp = lists ? (const double*)(hd + off[NS_CP]) : nullptr;
+#define NS_CHAIN(DP, KID, PH)                                                                                          \
+    hipLaunchKernelGGL((ns_chain_kernel<DP, KID, PH>), dim3((unsigned)rq.k), dim3(256), 0, ctx->stream, a, kp, ap,      \
+                       (const double*)(hd + off[NS_XS]), (const double*)(hd + off[NS_YS]), rq.nsurv,                   \
+                       (const double*)(hd + off[NS_W]), dlab, dmem, dmof, dcp, nw, rq.lstar, (unsigned)rq.generation,   \
+                       rq.num_repeats, (double*)(hd + off[NS_XN]), (double*)(hd + off[NS_YN]),                         \
+                       (int64_t*)(hd + off[NS_CNT]), rq.thin, n_ph, dXp, dyp)
+#define NS_CHAIN_PLAIN(DP, KID) NS_CHAIN(DP, KID, false)
+#define NS_CHAIN_PH(DP, KID) NS_CHAIN(DP, KID, true)
+    if (dXp) { DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_CHAIN_PH) }
+    else { DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_CHAIN_PLAIN) }
+#undef NS_CHAIN_PH
+#undef NS_CHAIN_PLAIN
+#undef NS_CHAIN
+}
+
+static int ns_generation_impl(gpry_ctx* ctx, const NsGenRequest& rq) {
+    GPRY_TRY(ns_check(ctx, rq));
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
-    GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
-    const int d = ctx->d;
-    const int64_t nw = labels ? n_clusters : 1;
+    GPRY_TRY(ns_args(ctx, "nested sampler", rq.lo, rq.hi, rq.seed, &a, &kp, &ap));
+    const int64_t d = ctx->d, n = rq.nsurv, k = rq.k, nc = rq.n_clusters, nw = rq.labels ? nc : 1;
+    const bool lists = rq.cum_p != nullptr;
     // phantoms: n_ph recorded states per chain, [X_ph | y_ph] in a device buffer of the context
-    const int n_ph = X_ph && num_repeats > 0 ? (num_repeats - 1) / thin : 0;
-    const int64_t pxb = sizeof(double) * (int64_t)k * n_ph * d, pyb = sizeof(double) * (int64_t)k * n_ph;
-    if (pxb + pyb > NS_PHANTOM_MAX_BYTES)
-        return gpry_fail(ctx, -1, "%s: %d chains x %d phantoms x %d coordinates need %lld bytes, the limit is %lld", who, k,
-                         n_ph, d, (long long)(pxb + pyb), (long long)NS_PHANTOM_MAX_BYTES);
+    const int n_ph = rq.X_ph && rq.num_repeats > 0 ? (rq.num_repeats - 1) / rq.thin : 0;
+    const int64_t psz[2] = {8 * k * n_ph * d, 8 * k * n_ph};
+    int64_t poff[3];
+    ns_layout(psz, poff);
+    if (psz[0] + psz[1] > NS_PHANTOM_MAX_BYTES)
+        return gpry_fail(ctx, -1, "%s: %d chains x %d phantoms x %d coordinates need %lld bytes, the limit is %lld", rq.who,
+                         rq.k, n_ph, (int)d, (long long)(psz[0] + psz[1]), (long long)NS_PHANTOM_MAX_BYTES);
     const bool rec = k > 0 && n_ph > 0;
-    // one pinned, mapped buffer: [survivors | their y | W | labels | new points | their y | counts]; with cum_p the
-    // labels' place holds [members | member offsets | cum_p] instead
-    const int64_t bm = round_up(sizeof(int32_t) * nsurv, 256), bo = round_up(sizeof(int32_t) * (n_clusters + 1), 256);
-    const int64_t bx = round_up(sizeof(double) * nsurv * d, 256), by = round_up(sizeof(double) * nsurv, 256),
-                  bw = round_up(sizeof(double) * nw * d * d, 256),
-                  bl = !labels ? 0 : cum_p ? bm + bo + round_up(sizeof(double) * n_clusters, 256)
-                                           : round_up(sizeof(int32_t) * nsurv, 256),
-                  bn = round_up(sizeof(double) * (int64_t)k * d, 256), bny = round_up(sizeof(double) * (int64_t)k, 256),
-                  bc = round_up(sizeof(int64_t) * (int64_t)k, 256);
-    GPRY_TRY(ensure_pinned(ctx, bx + by + bw + bl + bn + bny + bc));
+    // ---- lay out and fill the buffer
+    int64_t sz[NS_REGIONS] = {0}, off[NS_REGIONS + 1];
+    sz[NS_XS] = 8 * n * d; sz[NS_YS] = 8 * n; sz[NS_W] = 8 * nw * d * d;
+    if (lists) { sz[NS_MEM] = 4 * n; sz[NS_MOF] = 4 * (nc + 1); sz[NS_CP] = 8 * nc; }
+    else if (rq.labels) sz[NS_LAB] = 4 * n;
+    sz[NS_XN] = 8 * k * d; sz[NS_YN] = 8 * k; sz[NS_CNT] = 8 * k;
+    ns_layout(sz, off);
+    GPRY_TRY(ensure_pinned(ctx, off[NS_REGIONS]));
     char* h = (char*)ctx->hpin;
-    char* hd = (char*)ctx->hpin_dev;
-    memcpy(h, X_surv, sizeof(double) * nsurv * d);
-    memcpy(h + bx, y_surv, sizeof(double) * nsurv);
-    memcpy(h + bx + by, W, sizeof(double) * nw * d * d);
-    const int* dlab = nullptr;
-    const int* dmem = nullptr;
-    const int* dmof = nullptr;
-    const double* dcp = nullptr;
-    if (cum_p) {
-        // each cluster's survivors in their order in X_surv (a counting sort, stable by index)
-        int32_t* mem = (int32_t*)(h + bx + by + bw);
-        int32_t* mof = (int32_t*)(h + bx + by + bw + bm);
-        for (int q = 0; q <= n_clusters; q++) mof[q] = 0;
-        for (int64_t i = 0; i < nsurv; i++) mof[labels[i] + 1]++;
-        for (int q = 0; q < n_clusters; q++) mof[q + 1] += mof[q];
-        std::vector<int32_t> fill(mof, mof + n_clusters);
-        for (int64_t i = 0; i < nsurv; i++) mem[fill[labels[i]]++] = (int32_t)i;
-        memcpy(h + bx + by + bw + bm + bo, cum_p, sizeof(double) * n_clusters);
-        dmem = (const int*)(hd + bx + by + bw);
-        dmof = (const int*)(hd + bx + by + bw + bm);
-        dcp = (const double*)(hd + bx + by + bw + bm + bo);
-    } else if (labels) {
-        memcpy(h + bx + by + bw, labels, sizeof(int32_t) * nsurv);
-        dlab = (const int*)(hd + bx + by + bw);
-    }
-    const double* dXs_ = (const double*)hd;
-    const double* dys_ = (const double*)(hd + bx);
-    const double* dW = (const double*)(hd + bx + by);
-    const int64_t on = bx + by + bw + bl;
-    double* dXn = (double*)(hd + on);
-    double* dyn = (double*)(hd + on + bn);
-    int64_t* dcn = (int64_t*)(hd + on + bn + bny);
+    memcpy(h + off[NS_XS], rq.X_surv, sz[NS_XS]);
+    memcpy(h + off[NS_YS], rq.y_surv, sz[NS_YS]);
+    memcpy(h + off[NS_W], rq.W, sz[NS_W]);
+    if (lists) {
+        ns_members(rq.labels, n, (int)nc, (int32_t*)(h + off[NS_MEM]), (int32_t*)(h + off[NS_MOF]));
+        memcpy(h + off[NS_CP], rq.cum_p, sz[NS_CP]);
+    } else if (rq.labels) memcpy(h + off[NS_LAB], rq.labels, sz[NS_LAB]);
+    // ---- launch
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    const int64_t pxo = round_up(pxb, 256);
-    if (rec && pxo + pyb > ctx->ph_cap) {
-        if (ctx->dph) HIP_TRY(ctx, hipFree(ctx->dph));
-        ctx->dph = nullptr; ctx->ph_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->dph, (size_t)(pxo + pyb)));
-        ctx->ph_cap = pxo + pyb;
-    }
+    if (rec) GPRY_TRY(dev_grow(ctx, &ctx->dph, &ctx->ph_cap, poff[2]));
     double* dXp = rec ? (double*)ctx->dph : nullptr;
-    double* dyp = rec ? (double*)(ctx->dph + pxo) : nullptr;
-    if (k > 0) {
-#define NC(DP, KID, PH) hipLaunchKernelGGL((ns_chain_kernel<DP, KID, PH>), dim3((unsigned)k), dim3(256), 0, ctx->stream, a, kp, \
-                                           ap, dXs_, dys_, nsurv, dW, dlab, dmem, dmof, dcp, (int)nw, lstar, \
-                                           (unsigned)generation, num_repeats, dXn, dyn, dcn, thin, n_ph, dXp, dyp)
-#define NC_4(KID) NC(4, KID, false)
-#define NC_8(KID) NC(8, KID, false)
-#define NC_16(KID) NC(16, KID, false)
-#define NC_32(KID) NC(32, KID, false)
-#define NP_4(KID) NC(4, KID, true)
-#define NP_8(KID) NC(8, KID, true)
-#define NP_16(KID) NC(16, KID, true)
-#define NP_32(KID) NC(32, KID, true)
-        if (rec) {
-            if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NP_4) }
-            else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NP_8) }
-            else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NP_16) }
-            else { DISPATCH_KID(ctx->kernel_id, NP_32) }
-        }
-        else if (d <= 4) { DISPATCH_KID(ctx->kernel_id, NC_4) }
-        else if (d <= 8) { DISPATCH_KID(ctx->kernel_id, NC_8) }
-        else if (d <= 16) { DISPATCH_KID(ctx->kernel_id, NC_16) }
-        else { DISPATCH_KID(ctx->kernel_id, NC_32) }
-#undef NC_4
-#undef NC_8
-#undef NC_16
-#undef NC_32
-#undef NP_4
-#undef NP_8
-#undef NP_16
-#undef NP_32
-#undef NC
-    }
+    double* dyp = rec ? (double*)(ctx->dph + poff[1]) : nullptr;
+    if (k > 0) ns_launch_chains(ctx, rq, a, kp, ap, (char*)ctx->hpin_dev, off, (int)nw, n_ph, dXp, dyp);
+    // ---- copy back
     if (rec) {
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(X_ph, dXp, (size_t)pxb, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(y_ph, dyp, (size_t)pyb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(rq.X_ph, dXp, (size_t)psz[0], hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(rq.y_ph, dyp, (size_t)psz[1], hipMemcpyDeviceToHost, ctx->stream));
     }
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    memcpy(X_new, h + on, sizeof(double) * (int64_t)k * d);
-    memcpy(y_new, h + on + bn, sizeof(double) * (int64_t)k);
-    memcpy(ncalls, h + on + bn + bny, sizeof(int64_t) * (int64_t)k);
+    GPRY_TRY(ns_end(ctx, &tm, rq.device_ms));
+    memcpy(rq.X_new, h + off[NS_XN], sz[NS_XN]);
+    memcpy(rq.y_new, h + off[NS_YN], sz[NS_YN]);
+    memcpy(rq.ncalls, h + off[NS_CNT], sz[NS_CNT]);
     return 0;
+}
+
+// the part of a request that every generation entry point takes
+static NsGenRequest ns_request(const char* who, const double* lo, const double* hi, const double* X_surv,
+                               const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
+                               int64_t generation, int k, int num_repeats, double* X_new, double* y_new, int64_t* ncalls,
+                               double* device_ms) {
+    NsGenRequest rq;
+    rq.who = who; rq.lo = lo; rq.hi = hi; rq.X_surv = X_surv; rq.y_surv = y_surv; rq.nsurv = nsurv; rq.lstar = lstar;
+    rq.W = W; rq.seed = seed; rq.generation = generation; rq.k = k; rq.num_repeats = num_repeats;
+    rq.X_new = X_new; rq.y_new = y_new; rq.ncalls = ncalls; rq.device_ms = device_ms;
+    return rq;
 }
 
 extern "C" {
@@ -419,32 +430,22 @@ int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t se
     GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
+    const int64_t sz[2] = {8 * n * ctx->d, 8 * n};      // [X | y] in the pinned, mapped buffer
+    int64_t off[3];
+    ns_layout(sz, off);
     if (n > 0) {
-        const int64_t xb = round_up(sizeof(double) * n * ctx->d, 256);
-        GPRY_TRY(ensure_pinned(ctx, xb + (int64_t)sizeof(double) * n));
-        char* hd = (char*)ctx->hpin_dev;
-        double* dX = (double*)hd;
-        double* dy = (double*)(hd + xb);
-#define NP(DP, KID) hipLaunchKernelGGL((ns_prior_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX, dy)
-#define NP_4(KID) NP(4, KID)
-#define NP_8(KID) NP(8, KID)
-#define NP_16(KID) NP(16, KID)
-#define NP_32(KID) NP(32, KID)
-        if (ctx->d <= 4) { DISPATCH_KID(ctx->kernel_id, NP_4) }
-        else if (ctx->d <= 8) { DISPATCH_KID(ctx->kernel_id, NP_8) }
-        else if (ctx->d <= 16) { DISPATCH_KID(ctx->kernel_id, NP_16) }
-        else { DISPATCH_KID(ctx->kernel_id, NP_32) }
-#undef NP_4
-#undef NP_8
-#undef NP_16
-#undef NP_32
-#undef NP
+        GPRY_TRY(ensure_pinned(ctx, off[2]));
+        double* dX = (double*)((char*)ctx->hpin_dev + off[0]);
+        double* dy = (double*)((char*)ctx->hpin_dev + off[1]);
+#define NS_PRIOR(DP, KID) \
+    hipLaunchKernelGGL((ns_prior_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX, dy)
+        DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_PRIOR)
+#undef NS_PRIOR
     }
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
     if (n > 0) {
-        const int64_t xb = round_up(sizeof(double) * n * ctx->d, 256);
-        memcpy(X_out, ctx->hpin, sizeof(double) * n * ctx->d);
-        memcpy(y_out, (char*)ctx->hpin + xb, sizeof(double) * n);
+        memcpy(X_out, (char*)ctx->hpin + off[0], sz[0]);
+        memcpy(y_out, (char*)ctx->hpin + off[1], sz[1]);
     }
     return 0;
 }
@@ -452,30 +453,28 @@ int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t se
 int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv, const double* y_surv,
                        int64_t nsurv, double lstar, const double* W, uint64_t seed, int64_t generation, int k,
                        int num_repeats, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation: ctx is NULL");
-    return ns_generation_impl(ctx, "gpry_ns_generation", lo, hi, X_surv, y_surv, nsurv, lstar, W, nullptr, 1, nullptr,
-                              seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    return ns_generation_impl(ctx, ns_request("gpry_ns_generation", lo, hi, X_surv, y_surv, nsurv, lstar, W, seed,
+                                              generation, k, num_repeats, X_new, y_new, ncalls, device_ms));
 }
 
 int gpry_ns_generation_clustered(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
                                  const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
                                  int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
                                  double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_clustered: ctx is NULL");
-    if (!labels) return gpry_fail(ctx, -1, "gpry_ns_generation_clustered: NULL argument");
-    return ns_generation_impl(ctx, "gpry_ns_generation_clustered", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
-                              n_clusters, nullptr, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    NsGenRequest rq = ns_request("gpry_ns_generation_clustered", lo, hi, X_surv, y_surv, nsurv, lstar, W, seed,
+                                 generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    rq.labels = labels; rq.n_clusters = n_clusters; rq.need_labels = true;
+    return ns_generation_impl(ctx, rq);
 }
 
 int gpry_ns_generation_volumes(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
                                const double* y_surv, int64_t nsurv, double lstar, const double* W, uint64_t seed,
                                int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
                                const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, double* device_ms) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_volumes: ctx is NULL");
-    if (!labels || !cum_p) return gpry_fail(ctx, -1, "gpry_ns_generation_volumes: NULL argument");
-    if (nsurv > INT_MAX) return gpry_fail(ctx, -1, "gpry_ns_generation_volumes: nsurv = %lld", (long long)nsurv);
-    return ns_generation_impl(ctx, "gpry_ns_generation_volumes", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
-                              n_clusters, cum_p, seed, generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    NsGenRequest rq = ns_request("gpry_ns_generation_volumes", lo, hi, X_surv, y_surv, nsurv, lstar, W, seed,
+                                 generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    rq.labels = labels; rq.n_clusters = n_clusters; rq.cum_p = cum_p; rq.need_labels = rq.need_cum_p = true;
+    return ns_generation_impl(ctx, rq);
 }
 
 int gpry_ns_generation_phantoms(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv,
@@ -483,12 +482,11 @@ int gpry_ns_generation_phantoms(gpry_ctx* ctx, const double* lo, const double* h
                                 int64_t generation, int k, int num_repeats, const int32_t* labels, int n_clusters,
                                 const double* cum_p, double* X_new, double* y_new, int64_t* ncalls, int thin, double* X_ph,
                                 double* y_ph, double* device_ms) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_ns_generation_phantoms: ctx is NULL");
-    if (cum_p && nsurv > INT_MAX)
-        return gpry_fail(ctx, -1, "gpry_ns_generation_phantoms: nsurv = %lld", (long long)nsurv);
-    return ns_generation_impl(ctx, "gpry_ns_generation_phantoms", lo, hi, X_surv, y_surv, nsurv, lstar, W, labels,
-                              labels ? n_clusters : 1, cum_p, seed, generation, k, num_repeats, X_new, y_new, ncalls,
-                              device_ms, thin, X_ph, y_ph);
+    NsGenRequest rq = ns_request("gpry_ns_generation_phantoms", lo, hi, X_surv, y_surv, nsurv, lstar, W, seed,
+                                 generation, k, num_repeats, X_new, y_new, ncalls, device_ms);
+    rq.labels = labels; rq.n_clusters = labels ? n_clusters : 1; rq.cum_p = cum_p;
+    rq.thin = thin; rq.X_ph = X_ph; rq.y_ph = y_ph;
+    return ns_generation_impl(ctx, rq);
 }
 
 int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double* X, int64_t n, int k, int32_t* nbr_out,
@@ -515,12 +513,7 @@ int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double*
     }
     const int64_t bu = round_up(sizeof(double) * n * d, 256), bx = round_up(sizeof(double) * n * d, 256),
                   bn = round_up(sizeof(int32_t) * n * k, 256);
-    if (bu + bx + bn > ctx->knn_cap) {
-        if (ctx->dknn) HIP_TRY(ctx, hipFree(ctx->dknn));
-        ctx->dknn = nullptr; ctx->knn_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->dknn, (size_t)(bu + bx + bn)));
-        ctx->knn_cap = bu + bx + bn;
-    }
+    GPRY_TRY(dev_grow(ctx, &ctx->dknn, &ctx->knn_cap, bu + bx + bn));
     double* dUT = (double*)ctx->dknn;
     double* dX = (double*)(ctx->dknn + bu);
     int* dnbr = (int*)(ctx->dknn + bu + bx);

@@ -64,7 +64,27 @@ __device__ double ns_eval(const double* x, const NsArgs& a, const KernParams& kp
     return y;
 }
 
+// What the two chain kernels (ns_chain_kernel, mcmc_chain_kernel) share beyond the above: the helper below and no more.
+// The kernels differ on purpose in where products are fenced with ns_rn: the nested chain's W z sum and its
+// lo + u * span may fuse into FMAs, the Metropolis chain's Lp z and lo + ns_rn(u * span) may not, and merging either
+// pair changes bits.  The inside-the-box test over s_ut / s_xt is the same loop in both and stays written out in each:
+// as a function of any form it compiles to other registers or other branches than the loop in place.
+// Box-Muller: thread t < (d + 1) / 2 turns draw t of a step (u) into coordinates 2t and 2t + 1 of z ~ N(0, I) in LDS.  The
+// draw stays with the caller (with it in here the chain kernel compiles to other code); the caller's barrier follows.
+__device__ __forceinline__ void ns_box_muller(double* s_z, int t, int d, NsU2 u) {
+    const double rad = sqrt(-2.0 * log(1.0 - u.a)), ang = 6.283185307179586 * u.b;
+    s_z[2 * t] = rad * cos(ang);
+    if (2 * t + 1 < d) s_z[2 * t + 1] = rad * sin(ang);
+}
+
 // ---- host side -----------------------------------------------------------------------------------
+// byte offsets of N regions of sz[i] bytes laid end to end, each on a 256-byte boundary: off[i], and off[N] for the whole
+template <int N>
+static void ns_layout(const int64_t (&sz)[N], int64_t (&off)[N + 1]) {
+    off[0] = 0;
+    for (int i = 0; i < N; i++) off[i + 1] = off[i] + round_up(sz[i], 256);
+}
+
 static int ns_args(gpry_ctx* ctx, const char* who, const double* lo, const double* hi, unsigned long long seed, NsArgs* a, KernParams* kp,
                    AffParams* ap) {
     if (ctx->d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "%s: d = %d > %d", who, ctx->d, GPRY_MAX_DIM);

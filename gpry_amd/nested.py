@@ -49,7 +49,7 @@ The algorithm, step by step:
 * Stop when Z_live / Z < ``precision_criterion`` (Z_live = X mean(L_live), the PolyChord criterion) or, at the end of
   a generation, when the evaluation count has reached ``max_ncalls``.  The final live points get the volume X / n each.
 """
-from collections import namedtuple
+from collections import defaultdict, namedtuple
 from time import time
 
 import numpy as np
@@ -251,6 +251,105 @@ def merged_weights(L, born, thr, L_end=None):
     return logw, float(_logsumexp(logw))
 
 
+def _prior_phase(dev, lo, hi, seed, nprior, minus_inf_value):
+    """The start of a run: ``nprior`` uniform points, ``(X, y, L, device_ms)``."""
+    X, y, ms = dev.ns_prior(lo, hi, seed, nprior)
+    return X, y, _logL(y, minus_inf_value), ms
+
+
+def _split(L, k, minus_inf_value):
+    """The kill of the ``k`` lowest of a live set ordered by (L, index): ``(rem, keep, thr)``, the positions of the
+    removed points in that order, those of the survivors in ascending order, and the threshold L* for the new points."""
+    order = np.lexsort((np.arange(len(L)), L))
+    rem, keep = order[:k], np.sort(order[k:])
+    lstar = float(L[rem[-1]])
+    # an outside point is never accepted: with a finite minus_inf_value the threshold is at least that value
+    return rem, keep, lstar if not np.isfinite(minus_inf_value) else max(lstar, float(minus_inf_value))
+
+
+def _goes_on(dead, logZ_live, precision_criterion, ncalls, max_ncalls, gen):
+    """The stopping rule, asked before every generation: False once Z_live / Z < precision_criterion (or Z is not finite),
+    the evaluations have reached ``max_ncalls``, or after MAX_GENERATIONS."""
+    logZ = np.logaddexp(_logsumexp(np.concatenate(dead["logw"])) if dead["logw"] else -np.inf, logZ_live)
+    if not np.isfinite(logZ) or logZ_live - logZ < np.log(precision_criterion):
+        return False
+    return not (max_ncalls is not None and ncalls >= max_ncalls) and gen < MAX_GENERATIONS
+
+
+def _bury(dead, **columns):
+    """Appends one kill's arrays (X, y, L, logw, logX, ...) to the lists of the dead points."""
+    for name, a in columns.items():
+        dead[name].append(a)
+
+
+def _clusters_of(dev, lo, hi, Xs, k_max):
+    """``(labels, n_clusters, device_ms)`` of the points Xs: the device's neighbour table cut by ``knn_clusters``; fewer
+    than 3 points are one cluster."""
+    if len(Xs) < 3:
+        return np.zeros(len(Xs), np.int32), 1, 0.0
+    nbr, ms = dev.ns_knn(lo, hi, Xs, min(k_max, len(Xs) - 1))
+    return knn_clusters(nbr, Xs.shape[1], k_max) + (ms,)
+
+
+def _generation(dev, thin, *args, **kw):
+    """The run loops' one way to the device: ``dev.ns_generation(*args, **kw)``, or with ``thin`` (phantoms)
+    ``dev.ns_generation_phantoms(*args, thin, **kw)``: ``(X_new, y_new, ncalls, X_ph, y_ph, device_ms)``, X_ph and y_ph
+    None without ``thin``."""
+    if thin is not None:
+        return dev.ns_generation_phantoms(*args, thin, **kw)
+    Xn, yn, cnt, ms = dev.ns_generation(*args, **kw)
+    return Xn, yn, cnt, None, None, ms
+
+
+def _finish(dead, X, y, L, live_logw, nlive, ncalls, gen, device_ms, n_clusters):
+    """The end of a run: the dead points in the order they died, then the final live ones with the log weights
+    ``live_logw``; logZ, the information H and w from all of them.  Returns the fields of ``NestedResult`` that every
+    run has (rows: the points with a finite likelihood) and, for all points, L and the log weights."""
+    all_X, all_y, all_L, all_logw = (np.concatenate(dead[name] + [live])
+                                     for name, live in (("X", X), ("y", y), ("L", L), ("logw", live_logw)))
+    logZ = _logsumexp(all_logw)
+    fin = np.isfinite(all_L)
+    if np.isfinite(logZ):
+        p = np.exp(all_logw[fin] - logZ)
+        H = float(np.sum(p * (all_L[fin] - logZ)))
+        w = p / np.sum(p)
+    else:
+        H, w = 0.0, np.zeros(int(fin.sum()))
+    res = dict(X=np.ascontiguousarray(all_X[fin]), y=np.ascontiguousarray(all_y[fin]), w=w, logZ=float(logZ),
+               logZ_err=float(np.sqrt(max(H, 0.0) / nlive)), ncalls=int(ncalls), ngen=gen, device_s=device_ms / 1e3,
+               dead_L=np.concatenate(dead["L"]) if dead["L"] else np.empty(0),
+               dead_logX=np.concatenate(dead["logX"]) if dead["logX"] else np.empty(0),
+               n_dead=int(sum(len(a) for a in dead["y"])),
+               n_clusters=None if n_clusters is None else np.array(n_clusters, dtype=np.int64))
+    return res, all_L, all_logw
+
+
+def _with_phantoms(res, all_L, n_live, born, thrs, ph_X, ph_y, d, minus_inf_value):
+    """The fields of a run with phantoms from those without (``res``): the real rows, then the phantoms in (generation,
+    chain, slot) order, all of them weighted as one merged run.  ``all_L``, ``born``: of all real points, the last
+    ``n_live`` of them live; ``thrs``: each generation's threshold; ``ph_X`` / ``ph_y``: each generation's phantoms."""
+    Xp = np.concatenate(ph_X) if ph_X else np.empty((0, d))
+    yp = np.concatenate(ph_y) if ph_y else np.empty(0)
+    per_gen = len(ph_y[0]) if ph_y else 0
+    m_L = np.concatenate([all_L, _logL(yp, minus_inf_value)])
+    m_born = np.concatenate([born, np.repeat(np.arange(len(thrs), dtype=np.int64), per_gen)])
+    n_dead_all = len(all_L) - n_live
+    L_end = float(all_L[n_dead_all - 1]) if n_dead_all else -np.inf
+    logw_m, logZ_m = merged_weights(m_L, m_born, np.array(thrs, dtype=float), L_end=L_end)
+    fin_m = np.isfinite(m_L)
+    if np.isfinite(logZ_m):
+        w = np.exp(logw_m[fin_m] - logZ_m)
+        w = w / np.sum(w)
+    else:
+        w = np.zeros(int(fin_m.sum()))
+    fin_p = fin_m[len(all_L):]
+    flag = np.zeros(len(res["y"]) + int(fin_p.sum()), bool)
+    flag[len(res["y"]):] = True
+    return dict(res, X=np.ascontiguousarray(np.concatenate([res["X"], Xp[fin_p]])),
+                y=np.ascontiguousarray(np.concatenate([res["y"], yp[fin_p]])), w=w, phantom=flag, logZ_merged=logZ_m,
+                n_phantom=int(fin_p.sum()))
+
+
 def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, nprior=None, max_ncalls=None,
                batch=None, minus_inf_value=-np.inf, clustering=False, cluster_k_max=None, cluster_volumes=False,
                phantom_thin=None):
@@ -286,90 +385,56 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
     if cluster_volumes:
         if not clustering:
             raise ValueError("cluster_volumes=True needs clustering=True")
-        return _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls,
-                            minus_inf_value, k_max, t_start)
-    n_clusters = []
-    device_ms = 0.0
-    # ---- prior
-    X, y, ms = dev.ns_prior(lo, hi, seed, nprior)
-    device_ms += ms
-    ncalls = nprior
-    L = _logL(y, minus_inf_value)
-    dead_X, dead_y, dead_L, dead_logw, dead_logX = [], [], [], [], []
-    logX = 0.0
-    # phantoms: the generation every live / dead point was born in (-1: prior), each generation's threshold and phantoms
-    ph = phantom_thin is not None
-    born = np.full(nprior, -1, np.int64)
-    dead_born, thrs, ph_X, ph_y = [], [], [], []
+        res = _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls,
+                           minus_inf_value, k_max)
+    else:
+        res = _run_one_volume(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls,
+                              minus_inf_value, k_max if clustering else None, phantom_thin)
+    return NestedResult(wall_s=time() - t_start, **res)
 
-    def kill(idx, Xl, yl, Ll, logX):
+
+def _run_one_volume(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls,
+                    minus_inf_value, k_max, phantom_thin):
+    """The run with one prior volume for the whole live set: plain, with a whitening matrix per cluster (``k_max`` not
+    None) and / or with phantoms (``phantom_thin`` not None).  Returns the fields of the ``NestedResult``."""
+    X, y, L, device_ms = _prior_phase(dev, lo, hi, seed, nprior, minus_inf_value)
+    ncalls, logX, n_clusters, dead = nprior, 0.0, [], defaultdict(list)
+    # for the phantoms' weights: the generation every point was born in (-1: prior), each generation's threshold, phantoms
+    born, thrs, ph_X, ph_y = np.full(nprior, -1, np.int64), [], [], []
+
+    def kill(idx):
         """idx: positions of the removed points in ascending order; returns the new log volume."""
-        n = len(Ll)
-        nb = n - np.arange(len(idx), dtype=float)                 # live count before each removal
+        nb = len(L) - np.arange(len(idx), dtype=float)             # live count before each removal
         logX_seq = logX + np.cumsum(np.log(nb / (nb + 1.0)))
         logX_prev = np.concatenate([[logX], logX_seq[:-1]])
         # w_i = L_i (X_{i-1} - X_i) = L_i X_{i-1} / (n + 1)
         with np.errstate(invalid="ignore"):
-            logw = Ll[idx] + logX_prev - np.log(nb + 1.0)
-        logw[~np.isfinite(Ll[idx])] = -np.inf
-        dead_X.append(Xl[idx]); dead_y.append(yl[idx]); dead_L.append(Ll[idx])
-        dead_logw.append(logw); dead_logX.append(logX_seq)
+            logw = L[idx] + logX_prev - np.log(nb + 1.0)
+        logw[~np.isfinite(L[idx])] = -np.inf
+        _bury(dead, X=X[idx], y=y[idx], L=L[idx], logw=logw, logX=logX_seq, born=born[idx])
         return float(logX_seq[-1]) if len(idx) else logX
 
-    def order_of(Ll):
-        return np.lexsort((np.arange(len(Ll)), Ll))
-
     if nprior > nlive:
-        order = order_of(L)
-        logX = kill(order[:nprior - nlive], X, y, L, logX)
-        keep = np.sort(order[nprior - nlive:])
-        dead_born.append(born[order[:nprior - nlive]])
+        rem, keep, _ = _split(L, nprior - nlive, minus_inf_value)
+        logX = kill(rem)
         X, y, L, born = X[keep], y[keep], L[keep], born[keep]
     gen = 0
-    while True:
-        logZ_dead = _logsumexp(np.concatenate(dead_logw)) if dead_logw else -np.inf
-        logZ_live = logX + _logsumexp(L) - np.log(len(L))
-        logZ = np.logaddexp(logZ_dead, logZ_live)
-        if not np.isfinite(logZ) or logZ_live - logZ < np.log(precision_criterion):
-            break
-        if max_ncalls is not None and ncalls >= max_ncalls:
-            break
-        if gen >= MAX_GENERATIONS:
-            break
-        order = order_of(L)
-        rem, keep = order[:k_gen], np.sort(order[k_gen:])
-        lstar = float(L[rem[-1]])
-        logX = kill(rem, X, y, L, logX)
+    while _goes_on(dead, logX + _logsumexp(L) - np.log(len(L)), precision_criterion, ncalls, max_ncalls, gen):
+        rem, keep, thr = _split(L, k_gen, minus_inf_value)
+        logX = kill(rem)
         Xs, ys = np.ascontiguousarray(X[keep]), np.ascontiguousarray(y[keep])
         Us = (Xs - lo) / (hi - lo)
-        # an outside point is never accepted: with a finite minus_inf_value the threshold is at least that value
-        thr = lstar if not np.isfinite(minus_inf_value) else max(lstar, float(minus_inf_value))
-        if ph:
-            dead_born.append(born[rem])
-            born = np.concatenate([born[keep], np.full(k_gen, gen, np.int64)])
-            thrs.append(thr)
-        if not clustering:
-            W = whitening(Us)
-            if ph:
-                Xn, yn, cnt, Xp, yp, ms = dev.ns_generation_phantoms(lo, hi, Xs, ys, thr, W, seed, gen, k_gen,
-                                                                     num_repeats, phantom_thin)
-            else:
-                Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats)
+        thrs.append(thr)
+        if k_max is None:
+            W, kw = whitening(Us), {}
         else:
-            if len(Xs) >= 3:
-                nbr, ms = dev.ns_knn(lo, hi, Xs, min(k_max, len(Xs) - 1))
-                device_ms += ms
-                labels, nc = knn_clusters(nbr, Xs.shape[1], k_max)
-            else:
-                labels, nc = np.zeros(len(Xs), np.int32), 1
-            W = np.stack([whitening(Us[labels == q]) for q in range(nc)])
+            labels, nc, ms = _clusters_of(dev, lo, hi, Xs, k_max)
+            device_ms += ms
+            W, kw = np.stack([whitening(Us[labels == q]) for q in range(nc)]), {"labels": labels}
             n_clusters.append(nc)
-            if ph:
-                Xn, yn, cnt, Xp, yp, ms = dev.ns_generation_phantoms(lo, hi, Xs, ys, thr, W, seed, gen, k_gen,
-                                                                     num_repeats, phantom_thin, labels=labels)
-            else:
-                Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats, labels=labels)
-        if ph:
+        Xn, yn, cnt, Xp, yp, ms = _generation(dev, phantom_thin, lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats,
+                                              **kw)
+        if phantom_thin is not None:
             ph_X.append(np.asarray(Xp, dtype=float).reshape(-1, len(lo)))
             ph_y.append(np.asarray(yp, dtype=float).reshape(-1))
         device_ms += ms
@@ -377,70 +442,27 @@ def run_nested(dev, bounds, seed, nlive, num_repeats, precision_criterion=0.01, 
         X = np.concatenate([Xs, Xn])
         y = np.concatenate([ys, yn])
         L = np.concatenate([L[keep], _logL(yn, minus_inf_value)])
+        born = np.concatenate([born[keep], np.full(k_gen, gen, np.int64)])
         gen += 1
-    # ---- final live points: volume X / n each
-    n = len(L)
-    live_logw = L + logX - np.log(n)
-    all_X = np.concatenate(dead_X + [X]) if dead_X else X
-    all_y = np.concatenate(dead_y + [y]) if dead_y else y
-    all_L = np.concatenate(dead_L + [L]) if dead_L else L
-    all_logw = np.concatenate(dead_logw + [live_logw]) if dead_logw else live_logw
-    logZ = _logsumexp(all_logw)
-    fin = np.isfinite(all_L)
-    if np.isfinite(logZ):
-        p = np.exp(all_logw[fin] - logZ)
-        H = float(np.sum(p * (all_L[fin] - logZ)))
-        w = p / np.sum(p)
-    else:
-        H, w = 0.0, np.zeros(int(fin.sum()))
-    rows_X, rows_y, extra = all_X[fin], all_y[fin], {}
-    if ph:
-        # the real rows, then the phantoms in (generation, chain, slot) order; all of them weighted as one merged run
-        d = len(lo)
-        Xp = np.concatenate(ph_X) if ph_X else np.empty((0, d))
-        yp = np.concatenate(ph_y) if ph_y else np.empty(0)
-        per_gen = len(ph_y[0]) if ph_y else 0
-        Lp = _logL(yp, minus_inf_value)
-        m_L = np.concatenate([all_L, Lp])
-        m_born = np.concatenate(dead_born + [born, np.repeat(np.arange(gen, dtype=np.int64), per_gen)])
-        n_dead_all = len(all_L) - len(L)
-        L_end = float(all_L[n_dead_all - 1]) if n_dead_all else -np.inf
-        logw_m, logZ_m = merged_weights(m_L, m_born, np.array(thrs, dtype=float), L_end=L_end)
-        fin_m = np.isfinite(m_L)
-        if np.isfinite(logZ_m):
-            w = np.exp(logw_m[fin_m] - logZ_m)
-            w = w / np.sum(w)
-        else:
-            w = np.zeros(int(fin_m.sum()))
-        fin_p = fin_m[len(all_L):]
-        rows_X = np.concatenate([rows_X, Xp[fin_p]])
-        rows_y = np.concatenate([rows_y, yp[fin_p]])
-        flag = np.zeros(len(rows_y), bool)
-        flag[int(fin.sum()):] = True
-        extra = dict(phantom=flag, logZ_merged=logZ_m, n_phantom=int(fin_p.sum()))
-    return NestedResult(X=np.ascontiguousarray(rows_X), y=np.ascontiguousarray(rows_y), w=w, logZ=float(logZ),
-                        logZ_err=float(np.sqrt(max(H, 0.0) / nlive)), ncalls=int(ncalls), ngen=gen,
-                        device_s=device_ms / 1e3, wall_s=time() - t_start,
-                        dead_L=np.concatenate(dead_L) if dead_L else np.empty(0),
-                        dead_logX=np.concatenate(dead_logX) if dead_logX else np.empty(0),
-                        n_dead=int(sum(len(a) for a in dead_y)),
-                        n_clusters=np.array(n_clusters, dtype=np.int64) if clustering else None, **extra)
+    # the final live points: volume X / n each
+    res, all_L, _ = _finish(dead, X, y, L, L + logX - np.log(len(L)), nlive, ncalls, gen, device_ms,
+                            None if k_max is None else n_clusters)
+    if phantom_thin is None:
+        return res
+    return _with_phantoms(res, all_L, len(L), np.concatenate(dead["born"] + [born]), thrs, ph_X, ph_y, len(lo),
+                          minus_inf_value)
 
 
 def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision_criterion, max_ncalls, minus_inf_value,
-                 k_max, t_start):
-    """run_nested(clustering=True, cluster_volumes=True): the module docstring's per-cluster bookkeeping."""
+                 k_max):
+    """run_nested(clustering=True, cluster_volumes=True): the module docstring's per-cluster bookkeeping.  Returns the
+    fields of the ``NestedResult``."""
     d = len(lo)
-    device_ms = 0.0
-    X, y, ms = dev.ns_prior(lo, hi, seed, nprior)
-    device_ms += ms
-    ncalls = nprior
-    L = _logL(y, minus_inf_value)
+    X, y, L, device_ms = _prior_phase(dev, lo, hi, seed, nprior, minus_inf_value)
+    ncalls, n_clusters, dead = nprior, [], defaultdict(list)
     cl = np.zeros(len(L), np.int64)                 # the cluster id of every live point
     parent, logXc = [-1], [0.0]                     # per id: parent id, log prior volume
     open_ids = [0]
-    n_clusters = []
-    dead_X, dead_y, dead_L, dead_logw, dead_logX, dead_cl = [], [], [], [], [], []
 
     def kill(idx):
         """idx: positions of the removed points in ascending (y, index) order.  Every cluster's volume shrinks by
@@ -464,37 +486,23 @@ def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision
         if rest:
             after = np.concatenate([after, np.broadcast_to(np.array(rest), (len(idx), len(rest)))], axis=1)
         mx = np.max(after, axis=1)
-        dead_X.append(X[idx]); dead_y.append(y[idx]); dead_L.append(L[idx]); dead_cl.append(cid)
-        dead_logw.append(logw); dead_logX.append(mx + np.log(np.sum(np.exp(after - mx[:, None]), axis=1)))
+        _bury(dead, X=X[idx], y=y[idx], L=L[idx], logw=logw, cl=cid,
+              logX=mx + np.log(np.sum(np.exp(after - mx[:, None]), axis=1)))
 
-    def order_of(Ll):
-        return np.lexsort((np.arange(len(Ll)), Ll))
+    def logZ_live():
+        return _logsumexp([logXc[q] + _logsumexp(L[cl == q]) - np.log(np.count_nonzero(cl == q)) for q in open_ids])
 
     if nprior > nlive:
-        order = order_of(L)
-        kill(order[:nprior - nlive])
-        keep = np.sort(order[nprior - nlive:])
+        rem, keep, _ = _split(L, nprior - nlive, minus_inf_value)
+        kill(rem)
         X, y, L, cl = X[keep], y[keep], L[keep], cl[keep]
     gen = 0
-    while True:
-        logZ_dead = _logsumexp(np.concatenate(dead_logw)) if dead_logw else -np.inf
-        logZ_live = _logsumexp([logXc[q] + _logsumexp(L[cl == q]) - np.log(np.count_nonzero(cl == q))
-                                for q in open_ids])
-        logZ = np.logaddexp(logZ_dead, logZ_live)
-        if not np.isfinite(logZ) or logZ_live - logZ < np.log(precision_criterion):
-            break
-        if max_ncalls is not None and ncalls >= max_ncalls:
-            break
-        if gen >= MAX_GENERATIONS:
-            break
-        order = order_of(L)
-        rem, keep = order[:k_gen], np.sort(order[k_gen:])
-        lstar = float(L[rem[-1]])
+    while _goes_on(dead, logZ_live(), precision_criterion, ncalls, max_ncalls, gen):
+        rem, keep, thr = _split(L, k_gen, minus_inf_value)
         kill(rem)
         Xs, ys = np.ascontiguousarray(X[keep]), np.ascontiguousarray(y[keep])
         Ls, cls = L[keep], cl[keep]
         Us = (Xs - lo) / (hi - lo)
-        thr = lstar if not np.isfinite(minus_inf_value) else max(lstar, float(minus_inf_value))
         # re-cluster every open cluster's survivors on their own; an emptied cluster is closed (its volume dropped),
         # a split one is closed and its children share its volume in proportion to their live counts
         still = []
@@ -502,11 +510,8 @@ def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision
             mem = np.flatnonzero(cls == q)
             if len(mem) == 0:
                 continue
-            nc = 1
-            if len(mem) >= 3:
-                nbr, ms = dev.ns_knn(lo, hi, np.ascontiguousarray(Xs[mem]), min(k_max, len(mem) - 1))
-                device_ms += ms
-                lab, nc = knn_clusters(nbr, d, k_max)
+            lab, nc, ms = _clusters_of(dev, lo, hi, np.ascontiguousarray(Xs[mem]), k_max)
+            device_ms += ms
             if nc == 1:
                 still.append(q)
                 continue
@@ -527,8 +532,8 @@ def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision
         # another mode, and a chain that jumps across is charged to the wrong cluster (profiles/nested_volumes.md)
         W = np.stack([whitening(Us[labels == i]) for i in range(len(ids))])
         n_clusters.append(len(ids))
-        Xn, yn, cnt, ms = dev.ns_generation(lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats, labels=labels,
-                                            cum_p=cum_p)
+        Xn, yn, cnt, _, _, ms = _generation(dev, None, lo, hi, Xs, ys, thr, W, seed, gen, k_gen, num_repeats,
+                                            labels=labels, cum_p=cum_p)
         device_ms += ms
         ncalls += int(np.sum(cnt))
         X = np.concatenate([Xs, Xn])
@@ -536,28 +541,11 @@ def _run_volumes(dev, lo, hi, seed, nlive, nprior, k_gen, num_repeats, precision
         L = np.concatenate([Ls, _logL(yn, minus_inf_value)])
         cl = np.concatenate([cls, ids[chain_clusters(seed, gen, k_gen, cum_p)]])
         gen += 1
-    # ---- final live points: volume X_q / n_q each
+    # the final live points: volume X_q / n_q each
     nq = np.bincount(cl, minlength=len(parent)).astype(float)
-    live_logw = L + np.array(logXc)[cl] - np.log(nq[cl])
-    all_X = np.concatenate(dead_X + [X]) if dead_X else X
-    all_y = np.concatenate(dead_y + [y]) if dead_y else y
-    all_L = np.concatenate(dead_L + [L]) if dead_L else L
-    all_cl = np.concatenate(dead_cl + [cl]) if dead_cl else cl
-    all_logw = np.concatenate(dead_logw + [live_logw]) if dead_logw else live_logw
-    logZ = _logsumexp(all_logw)
-    cluster_logZ = np.array([_logsumexp(all_logw[all_cl == q]) for q in range(len(parent))])
-    fin = np.isfinite(all_L)
-    if np.isfinite(logZ):
-        p = np.exp(all_logw[fin] - logZ)
-        H = float(np.sum(p * (all_L[fin] - logZ)))
-        w = p / np.sum(p)
-    else:
-        H, w = 0.0, np.zeros(int(fin.sum()))
-    return NestedResult(X=np.ascontiguousarray(all_X[fin]), y=np.ascontiguousarray(all_y[fin]), w=w, logZ=float(logZ),
-                        logZ_err=float(np.sqrt(max(H, 0.0) / nlive)), ncalls=int(ncalls), ngen=gen,
-                        device_s=device_ms / 1e3, wall_s=time() - t_start,
-                        dead_L=np.concatenate(dead_L) if dead_L else np.empty(0),
-                        dead_logX=np.concatenate(dead_logX) if dead_logX else np.empty(0),
-                        n_dead=int(sum(len(a) for a in dead_y)), n_clusters=np.array(n_clusters, dtype=np.int64),
-                        cluster=np.ascontiguousarray(all_cl[fin]), cluster_logZ=cluster_logZ,
-                        cluster_parent=np.array(parent, dtype=np.int64))
+    res, all_L, all_logw = _finish(dead, X, y, L, L + np.array(logXc)[cl] - np.log(nq[cl]), nlive, ncalls, gen, device_ms,
+                                   n_clusters)
+    all_cl = np.concatenate(dead["cl"] + [cl])
+    return dict(res, cluster=np.ascontiguousarray(all_cl[np.isfinite(all_L)]),
+                cluster_logZ=np.array([_logsumexp(all_logw[all_cl == q]) for q in range(len(parent))]),
+                cluster_parent=np.array(parent, dtype=np.int64))
