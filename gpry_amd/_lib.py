@@ -76,6 +76,8 @@ SIGNATURES = {
     "gpry_ns_knn": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _P(C.c_double)]),
     "gpry_mcmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_double, C.c_uint64,
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_hmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, C.c_double, C.c_double,
+                                  C.c_uint64, C.c_int64, C.c_int, C.c_int] + [_vp] * 12),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -518,6 +520,37 @@ class Device:
                                                _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]), _ptr(out["y_last"]),
                                                _ptr(out["naccept"]), _ptr(out["ncalls"]), _ptr(out.get("X_prop")),
                                                _ptr(out.get("y_prop")), C.byref(ms)), "gpry_mcmc_chains")
+        out["device_ms"] = ms.value
+        return out
+
+    # -- Hamiltonian Monte Carlo of the mean (gpry_amd/hmc.py drives this one) ---------------
+    def hmc_chains(self, lo, hi, X0, y0, Lp, eps, nleap, T, minus_inf_value, seed, batch, nsteps, thin, hooks=False):
+        """``nsteps`` leapfrog trajectories (``nleap`` steps of size ``eps``, jittered, mass-matrix inverse Lp Lp^T in
+        unit-cube coordinates) of ``len(X0)`` chains from the states (X0, y0) (y0 NaN: evaluated first): the dict of
+        ``mcmc_chains`` plus ``ngrad``, the gradient evaluations per chain (``ncalls``: evaluations of the mean); with
+        ``hooks`` also ``X_prop`` (nchains, nsteps, d), ``y_prop`` and ``dH_prop`` (nchains, nsteps; NaN: the trajectory
+        was cut short and not evaluated) and ``G0`` (nchains, d), the gradient at the start states (gpry_hmc_chains)."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X0 = _f64(X0)
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise ValueError(f"expected start states of shape (nchains, {self.d}), got {X0.shape}")
+        n, d = X0.shape
+        y0, Lp = _f64(y0, (n,)), _f64(Lp, (d, d))
+        nsteps, thin = int(nsteps), int(thin)
+        nrec = nsteps // thin if thin > 0 else 0
+        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
+                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64))
+        if hooks:
+            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)), dH_prop=np.empty((n, nsteps)),
+                       G0=np.empty((n, d)))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_hmc_chains(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(Lp), float(eps),
+                                              int(nleap), float(T), float(minus_inf_value), int(seed), int(batch), nsteps,
+                                              thin, _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]),
+                                              _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
+                                              _ptr(out["ngrad"]), _ptr(out.get("X_prop")), _ptr(out.get("y_prop")),
+                                              _ptr(out.get("dH_prop")), _ptr(out.get("G0")), C.byref(ms)),
+                    "gpry_hmc_chains")
         out["device_ms"] = ms.value
         return out
 

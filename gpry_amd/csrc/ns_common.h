@@ -1,7 +1,8 @@
-// What the two device samplers of the surrogate's mean share: nested.hip (nested sampling) and mcmc.hip (Metropolis).
-// ns_eval is gpry_predict(x[None]) bit for bit (see nested.hip for the argument); ns_philox is the counter-based
-// generator both draw from, restated in numpy by tests/tools/ns_philox.py.  Phases of the counter's word 0: 0-2 belong
-// to the nested sampler (nested.hip), 3 to the Metropolis chains (mcmc.hip).
+// What the device samplers of the surrogate's mean share: nested.hip (nested sampling), mcmc.hip (Metropolis) and
+// hmc.hip (Hamiltonian Monte Carlo).  ns_eval is gpry_predict(x[None]) bit for bit (see nested.hip for the argument);
+// ns_philox is the counter-based generator all draw from, restated in numpy by tests/tools/ns_philox.py.  Phases of the
+// counter's word 0: 0-2 belong to the nested sampler (nested.hip), 3 to the Metropolis chains (mcmc.hip), 4 to the
+// Hamiltonian chains (hmc.hip).
 #pragma once
 #include "kern_math.h"
 

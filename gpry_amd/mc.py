@@ -1,10 +1,11 @@
 """The Monte Carlo sample of the surrogate that a run ends with (gpry/mc.py), made on the device.
 
-``mc_sample_from_gp(gpr, sampler="nested" | "mcmc")`` runs one of the two device samplers of the surrogate's mean:
-the nested sampler of ``gpry_amd/nested.py`` in place of PolyChord / UltraNest (gpry/mc.py:328-456), or the Metropolis
-chains of ``gpry_amd/mcmc.py`` in place of Cobaya's MCMC (gpry/mc.py:173-327).  Both evaluate ``gpr.predict(x[None])``
-bit for bit, the classifier and trust region included.  ``mc_sample_from_gp_ns`` keeps the reference's signature, so
-that ``gpry_amd.integration.patch_gpry_mc`` can put it under an unmodified ``Runner.generate_mc_sample``.
+``mc_sample_from_gp(gpr, sampler="nested" | "mcmc" | "hmc")`` runs one of the device samplers of the surrogate's mean:
+the nested sampler of ``gpry_amd/nested.py`` in place of PolyChord / UltraNest (gpry/mc.py:328-456), or, in place of
+Cobaya's MCMC (gpry/mc.py:173-327), the Metropolis chains of ``gpry_amd/mcmc.py`` or the Hamiltonian chains of
+``gpry_amd/hmc.py``.  All evaluate ``gpr.predict(x[None])`` bit for bit, the classifier and trust region included.
+``mc_sample_from_gp_ns`` keeps the reference's signature, so that ``gpry_amd.integration.patch_gpry_mc`` can put it
+under an unmodified ``Runner.generate_mc_sample``.
 """
 import os
 import warnings
@@ -63,14 +64,29 @@ def nested_settings(d, sampler_options=None):
     return out
 
 
-def mcmc_settings(d, sampler_options=None):
-    """run_mcmc's keyword arguments from Cobaya-style options (``Rminus1_cl_stop`` and other unknown keys: a warning)."""
+# run_hmc's arguments: those of run_mcmc (counted in trajectories) and its own two
+HMC_KEYS = {**MCMC_KEYS, "eps": "eps", "accept_target": "accept_target"}
+
+
+def _chain_settings(d, sampler_options, keys, sampler):
+    """Keyword arguments of a chain sampler's run loop from Cobaya-style options; Xnumber strings such as ``"50d"``
+    are multiples of d.  Unknown keys: a warning, and they are dropped (``_known``)."""
     out = {}
-    for k, v in _known(sampler_options, MCMC_KEYS, "mcmc").items():
+    for k, v in _known(sampler_options, keys, sampler).items():
         if k in ("max_samples", "max_ncalls", "nchains", "learn_every", "batch_steps", "thin") and v is not None:
             v = get_Xnumber(v, "d", d, int, k)
-        out[MCMC_KEYS[k]] = v
+        out[keys[k]] = v
     return out
+
+
+def mcmc_settings(d, sampler_options=None):
+    """run_mcmc's keyword arguments from Cobaya-style options (``Rminus1_cl_stop`` and other unknown keys: a warning)."""
+    return _chain_settings(d, sampler_options, MCMC_KEYS, "mcmc")
+
+
+def hmc_settings(d, sampler_options=None):
+    """run_hmc's keyword arguments from Cobaya-style options (unknown keys: a warning, and they are dropped)."""
+    return _chain_settings(d, sampler_options, HMC_KEYS, "hmc")
 
 
 def _bounds(gpr, bounds):
@@ -112,11 +128,12 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     clustering, default False: a whitening matrix per cluster of the live set; phantom_thin, default None: an int t
     keeps every t-th interior state of the chains as a weighted phantom row, see ``run_nested``) or
     ``"mcmc"`` (options Rminus1_stop, temperature, covmat, max_samples -> max_ncalls, and run_mcmc's nchains,
-    learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature).  Unknown options are warned
-    about and ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.  The
+    learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature) or ``"hmc"`` (run_hmc's
+    arguments: those of "mcmc", counted in trajectories, and eps, accept_target).  Unknown options are warned about and
+    ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.  The
     run's details are kept in ``mc_sample_from_gp.last_result``."""
-    if not isinstance(sampler, str) or sampler.lower() not in ("nested", "mcmc"):
-        raise ValueError(f"sampler must be 'nested' or 'mcmc', got {sampler!r}")
+    if not isinstance(sampler, str) or sampler.lower() not in ("nested", "mcmc", "hmc"):
+        raise ValueError(f"sampler must be 'nested', 'mcmc' or 'hmc', got {sampler!r}")
     sampler = sampler.lower()
     b = _bounds(gpr, bounds)
     d = len(b)
@@ -132,6 +149,13 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
                          **({"clustering": True} if s.get("clustering") else {}),
                          **({"cluster_volumes": True} if s.get("cluster_volumes") else {}),
                          **({"phantom_thin": s["phantom_thin"]} if s.get("phantom_thin") else {}))
+    elif sampler == "hmc":
+        from gpry_amd.hmc import DEFAULT_NCHAINS, run_hmc
+        s = hmc_settings(d, sampler_options)
+        nchains = s.pop("nchains", DEFAULT_NCHAINS)
+        _push_model(gpr, sampler)
+        res = run_hmc(gpr.device, b, seed, nchains, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value, **s)
+        gpr.n_eval += res.ngrad
     else:
         from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
         s = mcmc_settings(d, sampler_options)

@@ -140,6 +140,30 @@ def _weighted_cov(X, y, T=1.0):
     return (X - m).T @ ((X - m) * w[:, None])
 
 
+def _starts(X0, y0, lo, hi, T, minus_inf_value, nchains, seed):
+    """The start rule: the usable training points (finite y above ``minus_inf_value``, inside the box) and ``nchains`` of
+    them drawn with replacement with probability ∝ exp((y - y_max) / T) from an rng seeded with ``seed``: ``(Xt, yt, Xs,
+    ys)``, ys all NaN (the device evaluates the starts)."""
+    ok = np.isfinite(y0) & (y0 > minus_inf_value) & np.all((X0 >= lo) & (X0 <= hi), axis=1)
+    if not ok.any():
+        raise ValueError("no training point with a finite y inside the bounds to start a chain from")
+    Xt, yt = X0[ok], y0[ok]
+    rng = np.random.default_rng(seed)
+    p = np.exp((yt - np.max(yt)) / T)
+    Xs = np.ascontiguousarray(Xt[rng.choice(len(yt), size=nchains, p=p / p.sum())])
+    return Xt, yt, Xs, np.full(nchains, np.nan)
+
+
+def _temperature_weights(y, T, reset_temperature):
+    """Normalised weights of a sample of exp(y / T): ∝ exp(y - y / T) with ``reset_temperature`` and T != 1, else equal."""
+    if T != 1.0 and reset_temperature and len(y):
+        logw = y - y / T
+        w = np.exp(logw - np.max(logw))
+    else:
+        w = np.ones(len(y))
+    return w / w.sum() if len(w) else w
+
+
 def run_mcmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, learn_every=DEFAULT_LEARN_EVERY,
              learn_batches=DEFAULT_LEARN_BATCHES, batch_steps=DEFAULT_BATCH_STEPS, thin=None, Rminus1_stop=0.01,
              max_ncalls=None, max_batches=DEFAULT_MAX_BATCHES, skip=0.33, reset_temperature=True,
@@ -168,15 +192,7 @@ def run_mcmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, l
     X0, y0 = np.atleast_2d(np.asarray(X0, dtype=float)), np.asarray(y0, dtype=float).ravel()
     if X0.shape != (len(y0), d):
         raise ValueError(f"X0 {X0.shape} and y0 {y0.shape} do not form a training set of dimension {d}")
-    ok = np.isfinite(y0) & (y0 > minus_inf_value) & np.all((X0 >= lo) & (X0 <= hi), axis=1)
-    if not ok.any():
-        raise ValueError("no training point with a finite y inside the bounds to start a chain from")
-    Xt, yt = X0[ok], y0[ok]
-    # ---- starts
-    rng = np.random.default_rng(seed)
-    p = np.exp((yt - np.max(yt)) / T)
-    Xs = np.ascontiguousarray(Xt[rng.choice(len(yt), size=nchains, p=p / p.sum())])
-    ys = np.full(nchains, np.nan)
+    Xt, yt, Xs, ys = _starts(X0, y0, lo, hi, T, minus_inf_value, nchains, seed)
     # ---- first proposal, unit-cube coordinates
     C_u = (np.asarray(covmat, dtype=float) if covmat is not None else _weighted_cov(Xt, yt)) / np.outer(span, span)
     scale = PROPOSAL_SCALE / np.sqrt(d)
@@ -218,12 +234,7 @@ def run_mcmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, l
     X, y = X.reshape(-1, d), y.ravel()
     fin = np.isfinite(y) & (y > minus_inf_value)
     X, y = np.ascontiguousarray(X[fin]), np.ascontiguousarray(y[fin])
-    if T != 1.0 and reset_temperature and len(y):
-        logw = y - y / T
-        w = np.exp(logw - np.max(logw))
-    else:
-        w = np.ones(len(y))
-    w = w / w.sum() if len(w) else w
+    w = _temperature_weights(y, T, reset_temperature)
     return MCMCResult(X=X, y=y, w=w, Rminus1=np.array(Rm), acceptance=nacc / max(nprop, 1), ncalls=ncalls,
                       batches=nbatch, covmat=C_u * np.outer(span, span), converged=converged,
                       device_s=device_ms / 1e3, wall_s=time() - t_start)

@@ -323,6 +323,38 @@ int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const do
                      int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
                      int64_t* naccept, int64_t* ncalls, double* X_prop, double* y_prop, double* device_ms);
 
+/* ---- Hamiltonian Monte Carlo of the posterior mean (hmc.hip; adaptation, R - 1 and weights in gpry_amd/hmc.py) ----------
+ * A second sampler for the same three uses as gpry_mcmc_chains (gpry/mc.py:173-327, gpry/convergence.py:430-476,
+ * gpry/proposal.py:359-443), driven by the x-gradient of the mean, which is evaluated inside the kernel (one pass over
+ * the training rows per gradient, as for the mean).  gpry_hmc_chains: `nchains` chains, one workgroup each, make `nsteps`
+ * leapfrog trajectories from the states X0 (nchains x d) / y0 (nchains; NaN: the start is evaluated first and counted in
+ * ncalls).  Unit-cube coordinates u = (x - lo) / (hi - lo), target exp(y / T).  Lp: d x d lower triangular, row-major, the
+ * factor of the inverse mass matrix in unit-cube coordinates, no scale folded in.  Trajectory s of chain c draws from
+ * the counters (4, j, batch, c, s): j = 0..15 for the momentum p = z ~ N(0, I) by Box-Muller, 16 for the acceptance
+ * uniform ua, 17 for the step-size jitter u, eps_s = eps (0.8 + 0.4 u); a chain's bits do not depend on nchains.  The
+ * trajectory: a half kick p += (eps_s / 2) Lp^T g(u) / T, then nleap times a drift u += eps_s Lp p followed by a kick (a
+ * full one, the last a half one).  g is the gradient of the unclipped, ungated mean with respect to u: what
+ * gpr.predict(x[None], return_mean_grad=True) returns (y_std included; that gradient is taken in the model's
+ * transformed coordinates) times (hi - lo) / x_span, x_span the span of the model's x-affine map, 1 without one -- for a
+ * model without an x-affine map the raw-coordinate gradient times (hi - lo).  A drift that leaves [0, 1]^d, or a gradient
+ * that is not finite, rejects the trajectory at once and nothing further is evaluated; otherwise the end point's y' is
+ * gpry_predict of it, bit for bit (clip and gates included), and the trajectory is accepted iff y' is finite,
+ * y' > minus_inf_value and log(1 - ua) < (y' - y) / T - (|p'|^2 - |p|^2) / 2.  The gradient at the current state is kept
+ * from one trajectory to the next inside a call, and evaluated once at the start of every call: two calls of k
+ * trajectories with batch and batch + 1 draw other numbers than one call of 2 k, and count one gradient more.
+ * Outputs: as gpry_mcmc_chains (X_rec, y_rec every thin-th trajectory, X_last, y_last, naccept, ncalls: evaluations of
+ * the mean), and ngrad, the gradient evaluations per chain.  Test hooks, each nullable (X_prop and y_prop together), no
+ * memory is set aside for one unless asked: X_prop (nchains x nsteps x d) / y_prop (nchains x nsteps), the last point of
+ * every trajectory and its y, NaN where it was not evaluated; dH_prop (nchains x nsteps), the right-hand side of the
+ * acceptance test, NaN likewise; G0 (nchains x d), g at the start states as the kernel computed it.  Refused (-1, with
+ * gpry_last_error): d > 32; lo >= hi; T <= 0; eps <= 0; nleap outside 1 .. 1024.  Stops the resident predict kernel
+ * first.  device_ms (nullable): device time of the call, copies included. */
+int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0, int64_t nchains,
+                    const double* Lp, double eps, int nleap, double T, double minus_inf_value, uint64_t seed,
+                    int64_t batch, int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
+                    int64_t* naccept, int64_t* ncalls, int64_t* ngrad, double* X_prop, double* y_prop, double* dH_prop,
+                    double* G0, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
