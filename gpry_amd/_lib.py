@@ -78,6 +78,9 @@ SIGNATURES = {
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_hmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, C.c_double, C.c_double,
                                   C.c_uint64, C.c_int64, C.c_int, C.c_int] + [_vp] * 12),
+    "gpry_hmc_chains_reflect": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, C.c_double,
+                                          C.c_double, C.c_uint64, C.c_int64, C.c_int, C.c_int] + [_vp] * 11
+                                + [C.c_int, C.c_int, _vp, _vp]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -524,12 +527,16 @@ class Device:
         return out
 
     # -- Hamiltonian Monte Carlo of the mean (gpry_amd/hmc.py drives this one) ---------------
-    def hmc_chains(self, lo, hi, X0, y0, Lp, eps, nleap, T, minus_inf_value, seed, batch, nsteps, thin, hooks=False):
+    def hmc_chains(self, lo, hi, X0, y0, Lp, eps, nleap, T, minus_inf_value, seed, batch, nsteps, thin, hooks=False,
+                   reflect=False, max_reflect=64):
         """``nsteps`` leapfrog trajectories (``nleap`` steps of size ``eps``, jittered, mass-matrix inverse Lp Lp^T in
         unit-cube coordinates) of ``len(X0)`` chains from the states (X0, y0) (y0 NaN: evaluated first): the dict of
         ``mcmc_chains`` plus ``ngrad``, the gradient evaluations per chain (``ncalls``: evaluations of the mean); with
         ``hooks`` also ``X_prop`` (nchains, nsteps, d), ``y_prop`` and ``dH_prop`` (nchains, nsteps; NaN: the trajectory
-        was cut short and not evaluated) and ``G0`` (nchains, d), the gradient at the start states (gpry_hmc_chains)."""
+        was cut short and not evaluated) and ``G0`` (nchains, d), the gradient at the start states (gpry_hmc_chains).
+        ``reflect``: the drifts reflect at the walls of the box, at most ``max_reflect`` (1 .. 1024) times each, instead of
+        rejecting the trajectory that leaves it, and the dict gains ``nreflect``, the reflections per chain
+        (gpry_hmc_chains_reflect)."""
         lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
         X0 = _f64(X0)
         if X0.ndim != 2 or X0.shape[1] != self.d:
@@ -544,13 +551,16 @@ class Device:
             out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)), dH_prop=np.empty((n, nsteps)),
                        G0=np.empty((n, d)))
         ms = C.c_double(0.0)
-        self._check(self._lib.gpry_hmc_chains(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(Lp), float(eps),
-                                              int(nleap), float(T), float(minus_inf_value), int(seed), int(batch), nsteps,
-                                              thin, _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]),
-                                              _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
-                                              _ptr(out["ngrad"]), _ptr(out.get("X_prop")), _ptr(out.get("y_prop")),
-                                              _ptr(out.get("dH_prop")), _ptr(out.get("G0")), C.byref(ms)),
-                    "gpry_hmc_chains")
+        name, own = "gpry_hmc_chains", []
+        if reflect:
+            out["nreflect"] = np.zeros(n, np.int64)
+            name, own = "gpry_hmc_chains_reflect", [1, int(max_reflect), _ptr(out["nreflect"])]
+        self._check(getattr(self._lib, name)(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(Lp), float(eps),
+                                             int(nleap), float(T), float(minus_inf_value), int(seed), int(batch), nsteps,
+                                             thin, _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]),
+                                             _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
+                                             _ptr(out["ngrad"]), _ptr(out.get("X_prop")), _ptr(out.get("y_prop")),
+                                             _ptr(out.get("dH_prop")), _ptr(out.get("G0")), *own, C.byref(ms)), name)
         out["device_ms"] = ms.value
         return out
 

@@ -1,6 +1,6 @@
-// Hamiltonian Monte Carlo of the surrogate's posterior mean on the device: the kernel behind gpry_hmc_chains.  The
-// adaptation of the mass matrix, of the step size and of the trajectory length, the convergence test (R - 1 over split
-// chains), the burn-in and the temperature weights are host-side, in gpry_amd/hmc.py; together they stand in for the
+// Hamiltonian Monte Carlo of the surrogate's posterior mean on the device: the kernel behind gpry_hmc_chains and
+// gpry_hmc_chains_reflect.  The adaptation of the mass matrix, of the step size and of the trajectory length, the
+// convergence test (R - 1 over split chains), the burn-in and the temperature weights are host-side, in gpry_amd/hmc.py; together they stand in for the
 // Cobaya MCMC runs of gpry/mc.py:173-327 (the surrogate's final sample), gpry/convergence.py:430-476 (GaussianKL's MC
 // fallback) and gpry/proposal.py:359-443 (SmallChainProposer), as the Metropolis chains of mcmc.hip do.
 //
@@ -24,6 +24,20 @@
 // y' > minus_inf_value and log(1 - ua) < (y' - y) / T - (|p'|^2 - |p|^2) / 2.  The gradient at the current state is
 // kept between trajectories: a trajectory costs nleap gradients and one mean.  Every product that feeds a sum goes
 // through ns_rn, so that no FMA fuses them (-ffp-contract=fast) and the host can restate the trajectory.
+//
+// Reflection (RF, gpry_hmc_chains_reflect with reflect set).  The drift becomes a billiard flow of duration tau = eps_s
+// inside [0, 1]^d.  Repeat: the velocity v = Lp p (the sum of the plain drift, in its order); the hit time of every
+// coordinate's wall, t_k = ((v_k > 0 ? 1 : 0) - u_k) / v_k (+inf for v_k = 0), and j, the lowest index with the smallest;
+// without a hit before tau, u += rn(tau v) and the drift is done -- a drift that never hits is the plain drift bit for bit.
+// Otherwise u_t += rn(t_j v_t) (t != j), u_j is set on its wall exactly, p is reflected about the wall's normal in the
+// whitened coordinates, r = row j of Lp: p_k -= rn((rn(2 a) / b) r_k), a = sum rn(r_k p_k) (= v_j), b = sum rn(r_k r_k),
+// k <= j, and tau -= t_j.  u is clamped to [0, 1] after every move and x to [lo, hi] after the drift, which acts at
+// rounding level only, so the box test below never fires on an overshoot.  A drift that would need more than max_reflect
+// reflections rejects the trajectory unevaluated, as a box exit does without RF.  (In q = Lp^-1 u the flow is free motion
+// with specular reflection at the planes r . q = const: volume-preserving and time-reversible, and a reflection keeps
+// |p|^2; so leapfrog with this drift followed by a momentum flip is still an involution, and the set of states whose
+// trajectory stays within the cap in every drift is invariant under it, the reversed trajectory meeting the same walls.)
+// No draw is added, and the kicks, the gradient, the acceptance rule and the records are those of the plain kernel.
 #include "ns_common.h"
 #include "mean_grad.h"
 
@@ -41,7 +55,12 @@ __device__ __forceinline__ double hmc_norm2(const double* p, int d) {
 // Outputs, per chain c: as mcmc_chain_kernel's, and ngrad, the gradient evaluations.  Test hooks (each nullable):
 // X_prop / y_prop, the last point of every trajectory (where it ended, or where it was cut short) and its y, NaN where it
 // was not evaluated; dH_prop, the right-hand side of the acceptance test (NaN likewise); G0, g at the start state.
-template <int DP, int KID>
+// RF: rf.max_reflect, and rf.nreflect (nullable), the reflections of the chain; without RF the argument is empty, so
+// that the plain kernels keep the code they had before there was a flag.
+template <bool RF> struct HmcRf { int max_reflect; int64_t* nreflect; };
+template <> struct HmcRf<false> {};
+
+template <int DP, int KID, bool RF>
 __global__ __launch_bounds__(256) void hmc_chain_kernel(NsArgs a, KernParams kp, AffParams ap,
                                                         const double* __restrict__ X0, const double* __restrict__ y0,
                                                         const double* __restrict__ Lp, double eps, int nleap, double T,
@@ -51,7 +70,7 @@ __global__ __launch_bounds__(256) void hmc_chain_kernel(NsArgs a, KernParams kp,
                                                         int64_t* __restrict__ naccept, int64_t* __restrict__ ncalls,
                                                         int64_t* __restrict__ ngrad, double* __restrict__ X_prop,
                                                         double* __restrict__ y_prop, double* __restrict__ dH_prop,
-                                                        double* __restrict__ G0) {
+                                                        double* __restrict__ G0, HmcRf<RF> rf) {
     __shared__ double r2s[MEAN_SLICE_CH];
     __shared__ double red[256];
     __shared__ double s_L[GPRY_MAX_DIM * GPRY_MAX_DIM];
@@ -87,7 +106,7 @@ __global__ __launch_bounds__(256) void hmc_chain_kernel(NsArgs a, KernParams kp,
         if (t < d) g[t] = g[t] * s_gs[t];
         __syncthreads();
     };
-    int64_t n_eval = 0, n_acc = 0, n_grad = 0;
+    int64_t n_eval = 0, n_acc = 0, n_grad = 0, n_refl = 0;
     double y_cur = y0[c];
     if (y_cur != y_cur) {                       // NaN: the start's y is evaluated here
         y_cur = ns_eval<DP, KID>(s_x, a, kp, ap, r2s, red, &s_y);
@@ -118,7 +137,49 @@ __global__ __launch_bounds__(256) void hmc_chain_kernel(NsArgs a, KernParams kp,
             if (l == nleap) break;
             // drift: u += eps_s Lp p
             double un = 0.0, xn = 0.0;
-            if (t < d) {
+            if constexpr (RF) {
+                // the billiard flow of duration eps_s: j, tj, tau and nr are the same in every thread
+                __shared__ double s_v[GPRY_MAX_DIM], s_th[GPRY_MAX_DIM];        // velocity and hit times
+                double tau = eps_s;
+                for (int nr = 0;; nr++) {
+                    double v = 0.0;
+                    if (t < d) {
+                        for (int k = 0; k <= t; k++) v = v + ns_rn(s_L[t * d + k] * s_p[k]);
+                        s_v[t] = v;
+                        s_th[t] = v != 0.0 ? ((v > 0.0 ? 1.0 : 0.0) - s_ut[t]) / v : INFINITY;
+                    }
+                    __syncthreads();
+                    int j = -1;
+                    double tj = INFINITY;
+                    for (int k = 0; k < d; k++)
+                        if (s_th[k] < tj) { tj = s_th[k]; j = k; }
+                    if (!(tj < tau)) {              // no wall within what is left: the plain move ends the drift
+                        if (t < d) un = s_ut[t] + ns_rn(tau * v);
+                        break;
+                    }
+                    if (nr == rf.max_reflect) {        // the cap: the trajectory ends where it is
+                        alive = false;
+                        if (t < d) un = s_ut[t];
+                        break;
+                    }
+                    if (t < d) un = t == j ? (s_v[j] > 0.0 ? 1.0 : 0.0) : s_ut[t] + ns_rn(tj * v);
+                    if (t < d) s_ut[t] = un < 0.0 ? 0.0 : (un > 1.0 ? 1.0 : un);
+                    if (t <= j) {                   // p -= (2 a / b) r, r = row j of Lp, a = r . p = v_j
+                        const double* r = s_L + j * d;
+                        double b = 0.0;
+                        for (int k = 0; k <= j; k++) b = b + ns_rn(r[k] * r[k]);
+                        s_p[t] = s_p[t] - ns_rn((ns_rn(2.0 * s_v[j]) / b) * r[t]);
+                    }
+                    tau = tau - tj;
+                    n_refl++;
+                    __syncthreads();                // (s_p, s_ut written; s_v, s_th read)
+                }
+                if (t < d) {
+                    un = un < 0.0 ? 0.0 : (un > 1.0 ? 1.0 : un);
+                    xn = a.lo[t] + ns_rn(un * (a.hi[t] - a.lo[t]));
+                    xn = xn < a.lo[t] ? a.lo[t] : (xn > a.hi[t] ? a.hi[t] : xn);
+                }
+            } else if (t < d) {
                 double v = 0.0;
                 for (int k = 0; k <= t; k++) v = v + ns_rn(s_L[t * d + k] * s_p[k]);
                 un = s_ut[t] + ns_rn(eps_s * v);
@@ -163,15 +224,18 @@ __global__ __launch_bounds__(256) void hmc_chain_kernel(NsArgs a, KernParams kp,
     }
     if (t < d) X_last[(int64_t)c * d + t] = s_x[t];
     if (t == 0) { y_last[c] = y_cur; naccept[c] = n_acc; ncalls[c] = n_eval; ngrad[c] = n_grad; }
+    if constexpr (RF)
+        if (rf.nreflect && t == 0) rf.nreflect[c] = n_refl;
 }
 
 extern "C" {
 
-int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0, int64_t nchains,
-                    const double* Lp, double eps, int nleap, double T, double minus_inf_value, uint64_t seed,
-                    int64_t batch, int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
-                    int64_t* naccept, int64_t* ncalls, int64_t* ngrad, double* X_prop, double* y_prop, double* dH_prop,
-                    double* G0, double* device_ms) {
+int gpry_hmc_chains_reflect(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0,
+                            int64_t nchains, const double* Lp, double eps, int nleap, double T, double minus_inf_value,
+                            uint64_t seed, int64_t batch, int nsteps, int thin, double* X_rec, double* y_rec,
+                            double* X_last, double* y_last, int64_t* naccept, int64_t* ncalls, int64_t* ngrad,
+                            double* X_prop, double* y_prop, double* dH_prop, double* G0, int reflect, int max_reflect,
+                            int64_t* nreflect, double* device_ms) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_hmc_chains: ctx is NULL");
     if (!lo || !hi || !X0 || !y0 || !Lp || !X_last || !y_last || !naccept || !ncalls || !ngrad)
         return gpry_fail(ctx, -1, "gpry_hmc_chains: NULL argument");
@@ -183,6 +247,8 @@ int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const dou
     if (!(T > 0.0) || !isfinite(T)) return gpry_fail(ctx, -1, "gpry_hmc_chains: temperature T = %g", T);
     if (!(eps > 0.0) || !isfinite(eps)) return gpry_fail(ctx, -1, "gpry_hmc_chains: step size eps = %g", eps);
     if (nleap < 1 || nleap > 1024) return gpry_fail(ctx, -1, "gpry_hmc_chains: nleap = %d is outside 1 .. 1024", nleap);
+    if (reflect && (max_reflect < 1 || max_reflect > 1024))
+        return gpry_fail(ctx, -1, "gpry_hmc_chains: max_reflect = %d is outside 1 .. 1024", max_reflect);
     const int nrec = nsteps / thin;
     if (nrec > 0 && (!X_rec || !y_rec)) return gpry_fail(ctx, -1, "gpry_hmc_chains: NULL argument");
     GPRY_TRY(require_model(ctx, true));
@@ -191,15 +257,15 @@ int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const dou
     const int d = ctx->d;
     const int64_t n = nchains;
     // one buffer: [X0 | y0 | Lp | records X | records y | last X | last y | accepted | evaluations | gradients |
-    //              end points X | their y | dH | G0], a hook's region empty unless it is asked for
-    const int64_t sz[14] = {8 * n * d, 8 * n, 8 * (int64_t)d * d, 8 * n * nrec * d, 8 * n * nrec, 8 * n * d, 8 * n, 8 * n,
+    //              end points X | their y | dH | G0 | reflections], a hook's region empty unless it is asked for
+    const int64_t sz[15] = {8 * n * d, 8 * n, 8 * (int64_t)d * d, 8 * n * nrec * d, 8 * n * nrec, 8 * n * d, 8 * n, 8 * n,
                             8 * n, 8 * n, X_prop ? 8 * n * nsteps * d : 0, X_prop ? 8 * n * nsteps : 0,
-                            dH_prop ? 8 * n * nsteps : 0, G0 ? 8 * n * d : 0};
-    int64_t off[15];
+                            dH_prop ? 8 * n * nsteps : 0, G0 ? 8 * n * d : 0, reflect && nreflect ? 8 * n : 0};
+    int64_t off[16];
     ns_layout(sz, off);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[14]));
+    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[15]));
     char* b = (char*)ctx->dmc;
     HIP_TRY(ctx, hipMemcpyAsync(b + off[0], X0, sz[0], hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(b + off[1], y0, sz[1], hipMemcpyHostToDevice, ctx->stream));
@@ -218,17 +284,35 @@ int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const dou
     double* dyp = X_prop ? (double*)(b + off[11]) : nullptr;
     double* ddH = dH_prop ? (double*)(b + off[12]) : nullptr;
     double* dG0 = G0 ? (double*)(b + off[13]) : nullptr;
-#define HM(DP, KID) hipLaunchKernelGGL((hmc_chain_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, \
-                                       ap, dX0, dy0, dL, eps, nleap, T, minus_inf_value, (unsigned)batch, nsteps, thin, dXr, \
-                                       dyr, dXl, dyl, dna, dnc, dng, dXp, dyp, ddH, dG0)
-    DISPATCH_DP_KID(d, ctx->kernel_id, HM)
+    int64_t* dnr = sz[14] ? (int64_t*)(b + off[14]) : nullptr;
+#define HM(DP, KID, RF, RFARG)                                                                                           \
+    hipLaunchKernelGGL((hmc_chain_kernel<DP, KID, RF>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX0, dy0, \
+                       dL, eps, nleap, T, minus_inf_value, (unsigned)batch, nsteps, thin, dXr, dyr, dXl, dyl, dna, dnc,  \
+                       dng, dXp, dyp, ddH, dG0, RFARG)
+#define HM_PLAIN(DP, KID) HM(DP, KID, false, HmcRf<false>{})
+#define HM_RF(DP, KID) HM(DP, KID, true, (HmcRf<true>{max_reflect, dnr}))
+    if (reflect) { DISPATCH_DP_KID(d, ctx->kernel_id, HM_RF) }
+    else { DISPATCH_DP_KID(d, ctx->kernel_id, HM_PLAIN) }
+#undef HM_RF
+#undef HM_PLAIN
 #undef HM
     HIP_TRY(ctx, hipGetLastError());
-    void* dst[11] = {X_rec, y_rec, X_last, y_last, naccept, ncalls, ngrad, X_prop, y_prop, dH_prop, G0};
-    for (int i = 3; i < 14; i++)
+    if (!reflect && nreflect) memset(nreflect, 0, 8 * n);
+    void* dst[12] = {X_rec, y_rec, X_last, y_last, naccept, ncalls, ngrad, X_prop, y_prop, dH_prop, G0, nreflect};
+    for (int i = 3; i < 15; i++)
         if (sz[i] > 0) HIP_TRY(ctx, hipMemcpyAsync(dst[i - 3], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
     return 0;
+}
+
+int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0, int64_t nchains,
+                    const double* Lp, double eps, int nleap, double T, double minus_inf_value, uint64_t seed,
+                    int64_t batch, int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
+                    int64_t* naccept, int64_t* ncalls, int64_t* ngrad, double* X_prop, double* y_prop, double* dH_prop,
+                    double* G0, double* device_ms) {
+    return gpry_hmc_chains_reflect(ctx, lo, hi, X0, y0, nchains, Lp, eps, nleap, T, minus_inf_value, seed, batch, nsteps,
+                                   thin, X_rec, y_rec, X_last, y_last, naccept, ncalls, ngrad, X_prop, y_prop, dH_prop, G0, 0,
+                                   0, nullptr, device_ms);
 }
 
 }  // extern "C"

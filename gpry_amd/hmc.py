@@ -12,6 +12,8 @@ one, tests/tools/hmc_numpy.py):
     -> {"X": (nchains, nsteps // thin, d), "y": (nchains, nsteps // thin), "X_last", "y_last", "naccept", "ncalls",
         "ngrad", "device_ms"}``
 
+(with ``reflect=True, max_reflect=`` as keywords when reflection is on, and then ``"nreflect"`` in the result).
+
 The algorithm, step by step:
 
 * The chains work in the unit cube u = (x - lo) / (hi - lo); the prior is uniform on the box.  The target is
@@ -23,6 +25,13 @@ The algorithm, step by step:
   unit-cube coordinates and eps_s = eps (0.8 + 0.4 u), u uniform, drawn per trajectory.  A drift that leaves the box
   rejects the trajectory at once.  The end point is accepted iff its y' (``gpr.predict``, clip and gates included) is
   finite, above ``minus_inf_value`` and log(1 - ua) < (y' - y) / T - (|p'|^2 - |p|^2) / 2.
+* Reflection (``reflect=True``, off by default): the drift becomes a billiard flow of duration eps_s inside the unit
+  cube.  Where a coordinate's wall is hit before the time is up, the chain moves to the wall, its momentum is reflected
+  about the wall's normal in the whitened coordinates q = Lp^-1 u (p -= 2 (r . p) / (r . r) r, r the wall coordinate's row
+  of Lp), and the drift goes on with what time is left; a single drift that would need more than ``max_reflect``
+  reflections rejects the trajectory as a box exit does without reflection.  Reflection keeps |p|^2 and the flow is
+  volume-preserving and reversible, so the acceptance rule is unchanged and the chain stays exact (Neal 2011, section
+  5.5.1.5).  No trajectory is then lost to the walls, and the step size answers to the energy error alone.
 * Adaptation: the first mass-matrix inverse is ``covmat`` (raw coordinates) or the exp(y - y_max)-weighted covariance of
   the training set, in unit-cube coordinates; ``Lp`` is its Cholesky factor (``nested.cholesky_ridged``), no scale.
   Then ``learn_batches`` batches of ``learn_every`` trajectories.  After each, the covariance is re-estimated from the
@@ -45,11 +54,12 @@ import numpy as np
 from gpry_amd.mcmc import MCMCResult, _Records, _starts, _temperature_weights, _weighted_cov
 from gpry_amd.nested import cholesky_ridged
 
-HMCResult = namedtuple("HMCResult", MCMCResult._fields + ("eps", "nleap", "ngrad"))
+HMCResult = namedtuple("HMCResult", MCMCResult._fields + ("eps", "nleap", "ngrad", "nreflect"))
 HMCResult.__doc__ = """Output of ``run_hmc``.  The fields of ``MCMCResult`` (ncalls: evaluations of the mean, adaptation
 and starts included; acceptance: accepted / proposed trajectories of the sampling phase; covmat: the frozen mass-matrix
 inverse, raw coordinates), and eps, nleap: the frozen step size and leapfrog steps per trajectory; ngrad: the gradient
-evaluations, each about the cost of one evaluation of the mean."""
+evaluations, each about the cost of one evaluation of the mean; nreflect: the reflections at the walls over the whole run
+(0 without ``reflect``)."""
 
 DEFAULT_NCHAINS = 256
 DEFAULT_LEARN_EVERY = 40
@@ -69,9 +79,10 @@ def leapfrog_steps(eps):
 def run_hmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, eps=None, accept_target=DEFAULT_ACCEPT_TARGET,
             learn_every=DEFAULT_LEARN_EVERY, learn_batches=DEFAULT_LEARN_BATCHES, batch_steps=DEFAULT_BATCH_STEPS, thin=1,
             Rminus1_stop=0.01, max_ncalls=None, max_batches=DEFAULT_MAX_BATCHES, skip=0.33, reset_temperature=True,
-            minus_inf_value=-np.inf):
+            minus_inf_value=-np.inf, reflect=False, max_reflect=64):
     """HMC run of the surrogate on ``dev``; see the module's docstring.  X0, y0: the training set the starts are drawn
-    from.  ``eps``: the first step size (default d^(-1/4)).  Returns an ``HMCResult``."""
+    from.  ``eps``: the first step size (default d^(-1/4)).  ``reflect``: trajectories reflect at the walls of the box,
+    at most ``max_reflect`` times per drift.  Returns an ``HMCResult``."""
     t_start = time()
     bounds = np.asarray(bounds, dtype=float)
     lo, hi = np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
@@ -93,6 +104,9 @@ def run_hmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, ep
                          f"learn_batches = {learn_batches}: need 1 <= thin <= batch_steps and learn_every >= 2")
     if not 0.0 <= skip < 1.0:
         raise ValueError(f"skip = {skip} must lie in [0, 1)")
+    reflect, max_reflect = bool(reflect), int(max_reflect)
+    if reflect and not 1 <= max_reflect <= 1024:
+        raise ValueError(f"max_reflect = {max_reflect} must lie in 1 .. 1024")
     if int(max_batches) < 1:
         raise ValueError(f"max_batches = {max_batches}: at least one sampling batch is needed")
     X0, y0 = np.atleast_2d(np.asarray(X0, dtype=float)), np.asarray(y0, dtype=float).ravel()
@@ -103,15 +117,18 @@ def run_hmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, ep
     C_u = (np.asarray(covmat, dtype=float) if covmat is not None else _weighted_cov(Xt, yt)) / np.outer(span, span)
     Lp = cholesky_ridged(C_u)
     nleap = leapfrog_steps(eps)
-    device_ms, ncalls, ngrad, batch = 0.0, 0, 0, 0
+    device_ms, ncalls, ngrad, nreflect, batch = 0.0, 0, 0, 0, 0
+    own = dict(reflect=True, max_reflect=max_reflect) if reflect else {}
 
     def step(nsteps, thin_):
-        nonlocal Xs, ys, device_ms, ncalls, ngrad, batch
-        out = dev.hmc_chains(lo, hi, Xs, ys, Lp, eps, nleap, T, minus_inf_value, seed, batch, nsteps, thin_)
+        nonlocal Xs, ys, device_ms, ncalls, ngrad, nreflect, batch
+        out = dev.hmc_chains(lo, hi, Xs, ys, Lp, eps, nleap, T, minus_inf_value, seed, batch, nsteps, thin_, **own)
         batch += 1
         device_ms += out["device_ms"]
         ncalls += int(np.sum(out["ncalls"]))
         ngrad += int(np.sum(out["ngrad"]))
+        if reflect:
+            nreflect += int(np.sum(out["nreflect"]))
         Xs, ys = out["X_last"], out["y_last"]
         return out
 
@@ -147,4 +164,5 @@ def run_hmc(dev, bounds, seed, nchains, X0, y0, temperature=1.0, covmat=None, ep
     w = _temperature_weights(y, T, reset_temperature)
     return HMCResult(X=X, y=y, w=w, Rminus1=np.array(Rm), acceptance=nacc / max(nprop, 1), ncalls=ncalls,
                      batches=nbatch, covmat=C_u * np.outer(span, span), converged=converged,
-                     device_s=device_ms / 1e3, wall_s=time() - t_start, eps=eps, nleap=nleap, ngrad=ngrad)
+                     device_s=device_ms / 1e3, wall_s=time() - t_start, eps=eps, nleap=nleap, ngrad=ngrad,
+                     nreflect=nreflect)

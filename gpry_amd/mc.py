@@ -64,8 +64,8 @@ def nested_settings(d, sampler_options=None):
     return out
 
 
-# run_hmc's arguments: those of run_mcmc (counted in trajectories) and its own two
-HMC_KEYS = {**MCMC_KEYS, "eps": "eps", "accept_target": "accept_target"}
+# run_hmc's arguments: those of run_mcmc (counted in trajectories) and its own four
+HMC_KEYS = {**MCMC_KEYS, "eps": "eps", "accept_target": "accept_target", "reflect": "reflect", "max_reflect": "max_reflect"}
 
 
 def _chain_settings(d, sampler_options, keys, sampler):
@@ -129,9 +129,11 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     keeps every t-th interior state of the chains as a weighted phantom row, see ``run_nested``) or
     ``"mcmc"`` (options Rminus1_stop, temperature, covmat, max_samples -> max_ncalls, and run_mcmc's nchains,
     learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature) or ``"hmc"`` (run_hmc's
-    arguments: those of "mcmc", counted in trajectories, and eps, accept_target).  Unknown options are warned about and
-    ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.  The
-    run's details are kept in ``mc_sample_from_gp.last_result``."""
+    arguments: those of "mcmc", counted in trajectories, and eps, accept_target, and reflect, default False: with
+    ``{"reflect": True}`` the trajectories reflect at the walls of the box instead of being rejected there, at most
+    max_reflect, default 64, times per drift).  Unknown options are warned about and ignored.  seed: int, or None for
+    fresh entropy.  output: also write the reference's file format.  The run's details are kept in
+    ``mc_sample_from_gp.last_result``."""
     if not isinstance(sampler, str) or sampler.lower() not in ("nested", "mcmc", "hmc"):
         raise ValueError(f"sampler must be 'nested', 'mcmc' or 'hmc', got {sampler!r}")
     sampler = sampler.lower()

@@ -354,6 +354,32 @@ int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const dou
                     int64_t batch, int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
                     int64_t* naccept, int64_t* ncalls, int64_t* ngrad, double* X_prop, double* y_prop, double* dH_prop,
                     double* G0, double* device_ms);
+/* gpry_hmc_chains_reflect: gpry_hmc_chains with an optional reflective drift (Neal 2011, section 5.5.1.5; with a mass
+ *   matrix, specular reflection in the whitened coordinates q = Lp^-1 u).  reflect = 0: gpry_hmc_chains itself, bit for
+ *   bit (max_reflect is not read; nreflect, if given, is set to 0).  reflect != 0: the drift of one leapfrog step is a
+ *   billiard flow of duration tau = eps_s inside [0, 1]^d.  Repeat until the drift is done:
+ *   1. velocity v_t = sum_{k <= t} rn(Lp[t][k] p_k), the sum of the plain drift in its order (rn: the product rounded to
+ *      double before it is added; no FMA);
+ *   2. hit times t_k = ((v_k > 0 ? 1.0 : 0.0) - u_k) / v_k where v_k != 0, +inf otherwise; j: the lowest index with the
+ *      smallest t_k;
+ *   3. no hit, or !(t_j < tau): u_t += rn(tau v_t), and the drift is done (a drift without a hit is the plain one, bit
+ *      for bit);
+ *   4. otherwise, if this drift has made max_reflect reflections already, the trajectory is rejected where it stands,
+ *      unevaluated, as a box exit is by gpry_hmc_chains; else u_t += rn(t_j v_t) for t != j and u_j = the wall (1.0 for
+ *      v_j > 0, else 0.0), p_k -= rn((rn(2 a) / b) r_k) for k <= j with r = row j of Lp, a = sum_{k <= j} rn(r_k p_k)
+ *      (= v_j), b = sum_{k <= j} rn(r_k r_k), tau -= t_j, and the reflection is counted.
+ *   After every move u is clamped to [0, 1], and after the drift x_t = lo_t + rn(u_t (hi_t - lo_t)) to [lo_t, hi_t]: both
+ *   act at rounding level only.  Kicks, gradient, end point, acceptance rule, counters (no draw is added) and records are
+ *   those of gpry_hmc_chains.  The chain stays exact: the flow is volume-preserving and time-reversible in q, a
+ *   reflection keeps |p|^2, and the set of trajectories within the cap is invariant under "trajectory, then momentum
+ *   flip".  nreflect (nullable, nchains): the reflections each chain made in this call.  Refused (-1) before anything
+ *   runs: reflect != 0 with max_reflect outside 1 .. 1024, and what gpry_hmc_chains refuses. */
+int gpry_hmc_chains_reflect(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0,
+                            int64_t nchains, const double* Lp, double eps, int nleap, double T, double minus_inf_value,
+                            uint64_t seed, int64_t batch, int nsteps, int thin, double* X_rec, double* y_rec,
+                            double* X_last, double* y_last, int64_t* naccept, int64_t* ncalls, int64_t* ngrad,
+                            double* X_prop, double* y_prop, double* dH_prop, double* G0, int reflect, int max_reflect,
+                            int64_t* nreflect, double* device_ms);
 
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the

@@ -1,9 +1,11 @@
 """HMC against Metropolis MCMC of the surrogate on the device, from fixed seeds, on three models: the bench's fitted model
 (BASELINE configs[2]: 4080 training rows, d = 16) and peaked Gaussian surrogates at d = 16 and d = 30 (2000 training points,
-Matern-5/2, fixed hyper-parameters).  Per model: run_mcmc at its defaults and run_hmc at its defaults to R - 1 < 0.01
-(evaluations = mean + gradient, wall seconds, acceptance, eps, nleap, the effective sample size of the slowest coordinate
-per 1e6 evaluations and per second); on the bench's model also the device time per trajectory at 256 / 512 / 1024 chains.
-Warm context (one short run of each sampler first), medians over --reps runs.  Writes a JSON file and a markdown table.
+Matern-5/2, fixed hyper-parameters).  Per model: run_mcmc at its defaults, run_hmc at its defaults and run_hmc with
+reflect=True (the row hmc-reflect, with its reflections per trajectory) to R - 1 < 0.01 (evaluations = mean + gradient, wall
+seconds, acceptance, eps, nleap, the effective sample size of the slowest coordinate per 1e6 evaluations and per second);
+on the bench's model also the device time per trajectory at 256 / 512 / 1024 chains; on peaked16 the cost of the
+reflection flag where no wall is touched: device ms per trajectory of 256 chains with reflect on and off, calls
+alternating, medians over 2 x reps + 1 calls of 100 trajectories each.  Warm context (one short run of each sampler first), medians over --reps runs.  Writes a JSON file and a markdown table.
 
     python tools/time_hmc.py [--json profiles/hmc.json] [--md profiles/hmc_tables.md] [--reps 3] [--max-ncalls 6e7]
 """
@@ -54,7 +56,7 @@ def main():
     ap.add_argument("--models", default="bench,peaked16,peaked30")
     args = ap.parse_args()
     import bench
-    from gpry_amd.hmc import leapfrog_steps, run_hmc
+    from gpry_amd.hmc import DEFAULT_BATCH_STEPS, DEFAULT_LEARN_BATCHES, DEFAULT_LEARN_EVERY, leapfrog_steps, run_hmc
     from gpry_amd.mcmc import _weighted_cov, run_mcmc
     from gpry_amd.nested import cholesky_ridged
     out = {"models": {}, "reps": args.reps}
@@ -81,14 +83,19 @@ def main():
                         ess_per_1e6=ess / r.ncalls * 1e6, ess_per_s=ess / r.wall_s, converged=r.converged,
                         Rminus1=float(r.Rminus1[-1]))
 
-        def hmc(seed):
-            r = run_hmc(dev, bounds, seed, 256, gpr.X_train, gpr.y_train, max_ncalls=int(args.max_ncalls), **kw)
+        def hmc(seed, **own):
+            r = run_hmc(dev, bounds, seed, 256, gpr.X_train, gpr.y_train, max_ncalls=int(args.max_ncalls), **own, **kw)
             ess, ev = ess_slowest(r.X, 256), r.ncalls + r.ngrad
+            ntraj = 256 * (DEFAULT_LEARN_BATCHES * DEFAULT_LEARN_EVERY + r.batches * DEFAULT_BATCH_STEPS)
             return dict(evals=ev, wall_s=r.wall_s, device_s=r.device_s, acceptance=r.acceptance, ess=ess,
                         ess_per_1e6=ess / ev * 1e6, ess_per_s=ess / r.wall_s, converged=r.converged,
-                        Rminus1=float(r.Rminus1[-1]), eps=r.eps, nleap=r.nleap)
+                        Rminus1=float(r.Rminus1[-1]), eps=r.eps, nleap=r.nleap, reflections=r.nreflect / ntraj)
 
-        m = {"N": gpr.n, "d": d, "mcmc": one(mcmc, args.reps), "hmc": one(hmc, args.reps)}
+        def hmc_reflect(seed):
+            return hmc(seed, reflect=True)
+
+        m = {"N": gpr.n, "d": d, "mcmc": one(mcmc, args.reps), "hmc": one(hmc, args.reps),
+             "hmc-reflect": one(hmc_reflect, args.reps)}
         print(name, json.dumps(m, default=float), flush=True)
         if name == "bench":
             # device time per trajectory against the number of chains, at the adapted eps / nleap of the runs above
@@ -111,6 +118,26 @@ def main():
                                            nleap=nleap, eps=eps)
                 print(f"nchains {n}: {np.median(ms):.3f} ms per trajectory of all chains (nleap = {nleap}), "
                       f"{np.median(gr):.3g} evaluations/s", flush=True)
+        if name == "peaked16":
+            # the cost of the flag where no wall is touched: the same call with reflect off and on, alternating
+            span = bounds[:, 1] - bounds[:, 0]
+            Lp = cholesky_ridged(_weighted_cov(gpr.X_train, gpr.y_train) / np.outer(span, span))
+            eps = m["hmc"]["eps"]
+            nleap = leapfrog_steps(eps)
+            X0 = np.ascontiguousarray(gpr.X_train[np.random.default_rng(0).choice(gpr.n, 256)])
+            ms, nrefl = {False: [], True: []}, 0
+            for r in range(2 * (2 * args.reps + 2)):
+                rf = bool(r % 2)
+                o = dev.hmc_chains(bounds[:, 0], bounds[:, 1], X0, np.full(256, np.nan), Lp, eps, nleap, 1.0, -np.inf, 7,
+                                   r // 2, 100, 1, **(dict(reflect=True) if rf else {}))
+                if r >= 2:                          # (the first call of each is the warm-up)
+                    ms[rf].append(o["device_ms"] / 100)
+                    nrefl += int(np.sum(o.get("nreflect", 0)))
+            m["flag"] = dict(ms_per_trajectory_off=float(np.median(ms[False])), ms_per_trajectory_on=float(np.median(ms[True])),
+                             off=ms[False], on=ms[True], nleap=nleap, eps=eps, reflections=nrefl)
+            print(f"flag on peaked16: {np.median(ms[False]):.4f} ms per trajectory of 256 chains with reflect off "
+                  f"({min(ms[False]):.4f} .. {max(ms[False]):.4f}), {np.median(ms[True]):.4f} on ({min(ms[True]):.4f} .. "
+                  f"{max(ms[True]):.4f}); {nrefl} reflections", flush=True)
         out["models"][name] = m
         if args.json:
             with open(args.json, "w") as f:
@@ -120,22 +147,34 @@ def main():
             f.write(markdown(out))
 
 
+def _num(v, fmt):
+    return "–" if v != v else format(v, fmt)
+
+
 def markdown(out):
     L = [f"Measured by `python tools/time_hmc.py --reps {out['reps']}`, one {out.get('device', '?')}; medians over seeds "
          f"1..{out['reps']}, 256 chains, warm context.", "",
          "| model | sampler | evaluations | wall s | device s | acceptance | eps | nleap | ESS slowest | ESS / 1e6 evaluations | "
-         "ESS / s | R - 1 | converged |", "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+         "ESS / s | R - 1 | converged | reflections / trajectory |", "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for name, m in out["models"].items():
-        for s in ("mcmc", "hmc"):
+        for s in ("mcmc", "hmc", "hmc-reflect"):
             r = m[s]
             L.append(f"| {name} (N = {m['N']}, d = {m['d']}) | {s} | {r['evals']:.3g} | {r['wall_s']:.2f} | {r['device_s']:.2f} | "
-                     f"{r['acceptance']:.3f} | {r.get('eps', float('nan')):.3f} | {r.get('nleap', float('nan')):.0f} | "
-                     f"{r['ess']:.3g} | {r['ess_per_1e6']:.3g} | {r['ess_per_s']:.3g} | {r['Rminus1']:.4f} | {r['converged']} |")
+                     f"{r['acceptance']:.3f} | {_num(r.get('eps', float('nan')), '.3f')} | {_num(r.get('nleap', float('nan')), '.0f')} | "
+                     f"{r['ess']:.3g} | {r['ess_per_1e6']:.3g} | {r['ess_per_s']:.3g} | {r['Rminus1']:.4f} | {r['converged']} | "
+                     f"{_num(r.get('reflections', float('nan')), '.2f')} |")
     for name, m in out["models"].items():
         if "chains" in m:
             L += ["", f"| chains ({name}) | device ms per trajectory | evaluations / s | nleap |", "|---|---|---|---|"]
             for n, r in m["chains"].items():
                 L.append(f"| {n} | {r['ms_per_trajectory']:.3f} | {r['evals_per_s']:.3g} | {r['nleap']} |")
+    for name, m in out["models"].items():
+        if "flag" in m:
+            r = m["flag"]
+            L += ["", f"| reflect ({name}, 256 chains, nleap = {r['nleap']}) | device ms per trajectory | range |", "|---|---|---|",
+                  f"| off | {r['ms_per_trajectory_off']:.4f} | {min(r['off']):.4f} .. {max(r['off']):.4f} |",
+                  f"| on ({r['reflections']} reflections) | {r['ms_per_trajectory_on']:.4f} | {min(r['on']):.4f} .. "
+                  f"{max(r['on']):.4f} |"]
     return "\n".join(L) + "\n"
 
 
