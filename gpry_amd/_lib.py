@@ -76,6 +76,8 @@ SIGNATURES = {
     "gpry_ns_knn": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _P(C.c_double)]),
     "gpry_mcmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_double, C.c_uint64,
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_mcmc_ladders": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_double, C.c_uint64,
+                                    C.c_int64, C.c_int, C.c_int, C.c_int] + [_vp] * 11 + [_P(C.c_double)]),
     "gpry_hmc_chains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, C.c_double, C.c_double,
                                   C.c_uint64, C.c_int64, C.c_int, C.c_int] + [_vp] * 12),
     "gpry_hmc_chains_reflect": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, C.c_double,
@@ -523,6 +525,45 @@ class Device:
                                                _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]), _ptr(out["y_last"]),
                                                _ptr(out["naccept"]), _ptr(out["ncalls"]), _ptr(out.get("X_prop")),
                                                _ptr(out.get("y_prop")), C.byref(ms)), "gpry_mcmc_chains")
+        out["device_ms"] = ms.value
+        return out
+
+    # -- tempered Metropolis ladders of the mean (gpry_amd/tempering.py drives this one) ------
+    def mcmc_ladders(self, lo, hi, X0, y0, nrungs, Lp, T, minus_inf_value, seed, batch, nsteps, thin, swap_every,
+                     proposals=False):
+        """``nsteps`` Metropolis steps of ``len(X0) // nrungs`` ladders of ``nrungs`` chains (chain a * nrungs + r is slot r
+        of ladder a) with the proposal factors Lp (nrungs, d, d) and temperatures T (nrungs,), a swap round between
+        adjacent slots after every ``swap_every``-th step (0: none): the dict of ``mcmc_chains`` over all chains plus
+        ``nswap_try`` / ``nswap_acc`` (nladders, nrungs - 1); with ``proposals`` also ``X_prop``, ``y_prop`` and
+        ``swap_log`` (nladders, nsteps // swap_every, nrungs - 1): 1 accepted, 0 rejected, -1 not tried
+        (gpry_mcmc_ladders)."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X0 = _f64(X0)
+        nrungs = int(nrungs)
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise ValueError(f"expected start states of shape (nchains, {self.d}), got {X0.shape}")
+        n, d = X0.shape
+        if nrungs < 1 or n % nrungs:
+            raise ValueError(f"{n} start states do not form ladders of nrungs = {nrungs}")
+        nl = n // nrungs
+        y0, Lp, T = _f64(y0, (n,)), _f64(Lp, (nrungs, d, d)), _f64(T, (nrungs,))
+        nsteps, thin, swap_every = int(nsteps), int(thin), int(swap_every)
+        nrec = nsteps // thin if thin > 0 else 0
+        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
+                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64),
+                   nswap_try=np.zeros((nl, nrungs - 1), np.int64), nswap_acc=np.zeros((nl, nrungs - 1), np.int64))
+        log = None
+        if proposals:
+            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)),
+                       swap_log=np.full((nl, nsteps // swap_every if swap_every > 0 else 0, nrungs - 1), -1, np.int8))
+            log = out["swap_log"] if swap_every > 0 else None
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_mcmc_ladders(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), nl, nrungs, _ptr(Lp),
+                                                _ptr(T), float(minus_inf_value), int(seed), int(batch), nsteps, thin,
+                                                swap_every, _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]),
+                                                _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
+                                                _ptr(out["nswap_try"]), _ptr(out["nswap_acc"]), _ptr(out.get("X_prop")),
+                                                _ptr(out.get("y_prop")), _ptr(log), C.byref(ms)), "gpry_mcmc_ladders")
         out["device_ms"] = ms.value
         return out
 

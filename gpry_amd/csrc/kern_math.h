@@ -259,6 +259,112 @@ __device__ __forceinline__ double mean_slice(const double* x, const double* __re
     return out;
 }
 
+// One slice of the posterior mean of UP TO R POINTS in one pass over the training rows: every row and every alpha is
+// loaded once and used for each active point.  x: the points' raw coordinates, point p at x + p * GPRY_MAX_DIM; mask: bit
+// p set = point p is active (the same value in every thread; a point that is masked out costs nothing and out[p] is
+// not written).  For every active point the arithmetic is mean_slice's, operation for operation: the two scaled
+// coordinates per lane, fma(d1, d1, d0 * d0) and the xor-shuffle sum over the P lanes, phase 2's groups
+// (v0 + v1) + (v2 + v3) of the rows j0 + 256 q in ascending j0, the one-barrier tree -- so out[p] (valid in thread 0)
+// has the bits of mean_slice of point p alone.  The rows of r^2 are kept in chunks of MEAN_MULTI_CH = 1024 per point
+// instead of 4096: thread t adds the same groups in the same order for any chunk size that is a multiple of 1024 (the
+// CH parameter of mean_slice, which server.hip uses).  r2s: R x MEAN_MULTI_CH doubles; the tree's 256 partial sums of
+// point p go through the first 256 of its chunk, which phase 2 has finished with by then.
+#define MEAN_MULTI_CH 1024
+template <int DP, int KID, int R>
+__device__ __forceinline__ void mean_slice_multi(const double* x, unsigned mask, const double* __restrict__ Xs,
+                                                 const double* __restrict__ alpha_, int64_t row_lo, int64_t rows_per_split,
+                                                 const KernParams& kp, const AffParams& ap, double* r2s /*[R][MEAN_MULTI_CH]*/,
+                                                 double (&out)[R]) {
+    constexpr int P = DP / 2, CH = MEAN_MULTI_CH;
+    const int t = threadIdx.x, sub = t % P, rloc = t / P;
+    double x0[R], x1[R], acc[R];
+#pragma unroll
+    for (int p = 0; p < R; p++) {
+        x0[p] = 0.0; x1[p] = 0.0; acc[p] = 0.0;
+        if (mask >> p & 1u) {
+            const double* xp = x + p * GPRY_MAX_DIM;
+            const int k0 = 2 * sub, k1 = 2 * sub + 1;
+            if (k0 < kp.d) { double v = xp[k0]; if (kp.has_aff) v = (v - ap.lo[k0]) / ap.span[k0]; x0[p] = v / ap.ls[k0]; }
+            if (k1 < kp.d) { double v = xp[k1]; if (kp.has_aff) v = (v - ap.lo[k1]) / ap.span[k1]; x1[p] = v / ap.ls[k1]; }
+        }
+    }
+    const bool piece_ok = 2 * sub < kp.dpad;
+    const int64_t row_hi = (row_lo + rows_per_split < kp.N) ? row_lo + rows_per_split : kp.N;
+    for (int64_t c0 = row_lo; c0 < row_hi; c0 += CH) {
+        const int nrow = (int)((row_hi - c0 < CH) ? row_hi - c0 : CH);
+        // phase 1: eight passes of rows loaded back to back, each used for every active point
+        constexpr int RP = 256 / P;
+        for (int r0 = 0; r0 < nrow; r0 += 8 * RP) {
+            double2 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int row = r0 + u * RP + rloc;
+                v[u] = make_double2(0.0, 0.0);
+                if (row < nrow && piece_ok)
+                    v[u] = *reinterpret_cast<const double2*>(Xs + (c0 + row) * kp.dpad + 2 * sub);
+            }
+#pragma unroll
+            for (int p = 0; p < R; p++) {
+                if (!(mask >> p & 1u)) continue;
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int row = r0 + u * RP + rloc;
+                    const double d0 = x0[p] - v[u].x, d1 = x1[p] - v[u].y;
+                    double part = piece_ok ? fma(d1, d1, d0 * d0) : 0.0;
+#pragma unroll
+                    for (int o = 1; o < P; o <<= 1) part += __shfl_xor(part, o);
+                    if (sub == 0 && row < nrow) r2s[p * CH + row] = part;
+                }
+            }
+        }
+        __syncthreads();
+        // phase 2: one row per lane, four independent chains per point (one trip: CH = 1024)
+        for (int j0 = t; j0 < nrow; j0 += 1024) {
+            double al[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int j = j0 + 256 * q;
+                al[q] = alpha_[c0 + (j < nrow ? j : 0)];
+            }
+#pragma unroll
+            for (int p = 0; p < R; p++) {
+                if (!(mask >> p & 1u)) continue;
+                double v[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int j = j0 + 256 * q;
+                    v[q] = j < nrow ? al[q] * (kp.C * corr_r2_fast<KID>(r2s[p * CH + j])) : 0.0;
+                }
+                acc[p] += (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        }
+        __syncthreads();
+    }
+    // mean_slice's tree, once per active point, with the two barriers shared
+#pragma unroll
+    for (int p = 0; p < R; p++)
+        if (mask >> p & 1u) r2s[p * CH + t] = acc[p];
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < R; p++) {
+        if (!(mask >> p & 1u)) continue;
+        const double* red = r2s + p * CH;
+        double o = 0.0;
+        if (t < 64) {
+            double v = (red[t] + red[t + 128]) + (red[t + 64] + red[t + 192]);
+            v += __shfl_down(v, 32);
+            v += __shfl_down(v, 16);
+            v += __shfl_down(v, 8);
+            v += __shfl_down(v, 4);
+            v += __shfl_down(v, 2);
+            v += __shfl_down(v, 1);
+            o = v;
+        }
+        out[p] = o;
+    }
+    __syncthreads();
+}
+
 
 // ------------------------------------------------------------------------------------
 // Gates of ONE point (gpry_set_gates), shared by the resident predict kernel (server.hip) and the nested sampler

@@ -1,8 +1,9 @@
-// What the device samplers of the surrogate's mean share: nested.hip (nested sampling), mcmc.hip (Metropolis) and
-// hmc.hip (Hamiltonian Monte Carlo).  ns_eval is gpry_predict(x[None]) bit for bit (see nested.hip for the argument);
-// ns_philox is the counter-based generator all draw from, restated in numpy by tests/tools/ns_philox.py.  Phases of the
-// counter's word 0: 0-2 belong to the nested sampler (nested.hip), 3 to the Metropolis chains (mcmc.hip), 4 to the
-// Hamiltonian chains (hmc.hip).
+// What the device samplers of the surrogate's mean share: nested.hip (nested sampling), mcmc.hip (Metropolis),
+// mcmc_ladders.hip (tempered Metropolis ladders) and hmc.hip (Hamiltonian Monte Carlo).  ns_eval is
+// gpry_predict(x[None]) bit for bit (see nested.hip for the argument), ns_eval_multi the same for several points in one
+// pass; ns_philox is the counter-based generator all draw from, restated in numpy by tests/tools/ns_philox.py.  Phases
+// of the counter's word 0: 0-2 belong to the nested sampler (nested.hip), 3 to the Metropolis chains (mcmc.hip, and
+// mcmc_ladders.hip, which adds draw 17 for its swaps), 4 to the Hamiltonian chains (hmc.hip).
 #pragma once
 #include "kern_math.h"
 
@@ -63,6 +64,48 @@ __device__ double ns_eval(const double* x, const NsArgs& a, const KernParams& kp
     const double y = *s_y;
     __syncthreads();
     return y;
+}
+
+// y of up to R points at once (point p: raw coordinates in LDS at x + p * GPRY_MAX_DIM; mask: bit p set = point p is
+// evaluated, the same value in every thread): y[p] of every active point, valid in every thread, with the bits of
+// ns_eval of that point alone -- mean_slice_multi's slices added from 0.0 in slice order, ns_eval's finish, the gates
+// point by point.  A point that is masked out costs nothing and its y[p] is left as it was; with no active point there
+// is no pass and no barrier.  r2s: R x MEAN_MULTI_CH doubles (also the gates' tree); s_y: R doubles.
+template <int DP, int KID, int R>
+__device__ __forceinline__ void ns_eval_multi(const double* x, unsigned mask, const NsArgs& a, const KernParams& kp,
+                                              const AffParams& ap, double* r2s, double* s_y, double (&y)[R]) {
+    if (!mask) return;
+    double mu[R];
+#pragma unroll
+    for (int p = 0; p < R; p++) mu[p] = 0.0;
+    for (int s = 0; s < a.nsplit; s++) {
+        double v[R];
+        mean_slice_multi<DP, KID, R>(x, mask, a.Xs, a.alpha_, (int64_t)s * a.rows_per_split, a.rows_per_split, kp, ap, r2s,
+                                     v);
+#pragma unroll
+        for (int p = 0; p < R; p++)
+            if (mask >> p & 1u) mu[p] = mu[p] + v[p];          // (thread 0 holds the slice sums)
+    }
+    unsigned gated = 0;
+    if (a.gates) {
+#pragma unroll
+        for (int p = 0; p < R; p++)
+            if ((mask >> p & 1u) && point_gate_bits(x + p * GPRY_MAX_DIM, a.gate, kp, ap, r2s)) gated |= 1u << p;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int p = 0; p < R; p++) {
+            if (!(mask >> p & 1u)) continue;
+            double yy = fmin(ns_rn(mu[p] * a.y_std) + a.y_mean, a.clip_hi);
+            if (gated >> p & 1u) yy = -INFINITY;
+            s_y[p] = yy;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < R; p++)
+        if (mask >> p & 1u) y[p] = s_y[p];
+    __syncthreads();
 }
 
 // What the two chain kernels (ns_chain_kernel, mcmc_chain_kernel) share beyond the above: the helper below and no more.

@@ -1,9 +1,10 @@
 """The Monte Carlo sample of the surrogate that a run ends with (gpry/mc.py), made on the device.
 
-``mc_sample_from_gp(gpr, sampler="nested" | "mcmc" | "hmc")`` runs one of the device samplers of the surrogate's mean:
-the nested sampler of ``gpry_amd/nested.py`` in place of PolyChord / UltraNest (gpry/mc.py:328-456), or, in place of
-Cobaya's MCMC (gpry/mc.py:173-327), the Metropolis chains of ``gpry_amd/mcmc.py`` or the Hamiltonian chains of
-``gpry_amd/hmc.py``.  All evaluate ``gpr.predict(x[None])`` bit for bit, the classifier and trust region included.
+``mc_sample_from_gp(gpr, sampler="nested" | "mcmc" | "hmc" | "tempered")`` runs one of the device samplers of the
+surrogate's mean: the nested sampler of ``gpry_amd/nested.py`` in place of PolyChord / UltraNest (gpry/mc.py:328-456), or,
+in place of Cobaya's MCMC (gpry/mc.py:173-327), the Metropolis chains of ``gpry_amd/mcmc.py``, the Hamiltonian chains of
+``gpry_amd/hmc.py`` or the tempered Metropolis ladders of ``gpry_amd/tempering.py``.  All evaluate
+``gpr.predict(x[None])`` bit for bit, the classifier and trust region included.
 ``mc_sample_from_gp_ns`` keeps the reference's signature, so that ``gpry_amd.integration.patch_gpry_mc`` can put it
 under an unmodified ``Runner.generate_mc_sample``.
 """
@@ -68,12 +69,18 @@ def nested_settings(d, sampler_options=None):
 HMC_KEYS = {**MCMC_KEYS, "eps": "eps", "accept_target": "accept_target", "reflect": "reflect", "max_reflect": "max_reflect"}
 
 
+# run_tempered's arguments: those of run_mcmc (nchains counts the ladders) and the ladder's four
+TEMPERED_KEYS = {**MCMC_KEYS, "nchains": "nladders", "rungs": "rungs", "T_max": "T_max", "temperatures": "temperatures",
+                 "swap_every": "swap_every"}
+
+
 def _chain_settings(d, sampler_options, keys, sampler):
     """Keyword arguments of a chain sampler's run loop from Cobaya-style options; Xnumber strings such as ``"50d"``
     are multiples of d.  Unknown keys: a warning, and they are dropped (``_known``)."""
     out = {}
     for k, v in _known(sampler_options, keys, sampler).items():
-        if k in ("max_samples", "max_ncalls", "nchains", "learn_every", "batch_steps", "thin") and v is not None:
+        if k in ("max_samples", "max_ncalls", "nchains", "learn_every", "batch_steps", "thin", "rungs",
+                 "swap_every") and v is not None:
             v = get_Xnumber(v, "d", d, int, k)
         out[keys[k]] = v
     return out
@@ -87,6 +94,11 @@ def mcmc_settings(d, sampler_options=None):
 def hmc_settings(d, sampler_options=None):
     """run_hmc's keyword arguments from Cobaya-style options (unknown keys: a warning, and they are dropped)."""
     return _chain_settings(d, sampler_options, HMC_KEYS, "hmc")
+
+
+def tempered_settings(d, sampler_options=None):
+    """run_tempered's keyword arguments from Cobaya-style options (unknown keys: a warning, and they are dropped)."""
+    return _chain_settings(d, sampler_options, TEMPERED_KEYS, "tempered")
 
 
 def _bounds(gpr, bounds):
@@ -131,11 +143,13 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature) or ``"hmc"`` (run_hmc's
     arguments: those of "mcmc", counted in trajectories, and eps, accept_target, and reflect, default False: with
     ``{"reflect": True}`` the trajectories reflect at the walls of the box instead of being rejected there, at most
-    max_reflect, default 64, times per drift).  Unknown options are warned about and ignored.  seed: int, or None for
-    fresh entropy.  output: also write the reference's file format.  The run's details are kept in
-    ``mc_sample_from_gp.last_result``."""
-    if not isinstance(sampler, str) or sampler.lower() not in ("nested", "mcmc", "hmc"):
-        raise ValueError(f"sampler must be 'nested', 'mcmc' or 'hmc', got {sampler!r}")
+    max_reflect, default 64, times per drift) or ``"tempered"`` (run_tempered's arguments: those of "mcmc", with nchains
+    the number of ladders, and rungs, default 6, T_max, temperatures, swap_every, default 5: ladders of Metropolis
+    chains at rising temperatures that exchange states, for surrogates with separated modes).  Unknown options are
+    warned about and ignored.  seed: int, or None for fresh entropy.  output: also write the reference's file format.
+    The run's details are kept in ``mc_sample_from_gp.last_result``."""
+    if not isinstance(sampler, str) or sampler.lower() not in ("nested", "mcmc", "hmc", "tempered"):
+        raise ValueError(f"sampler must be 'nested', 'mcmc', 'hmc' or 'tempered', got {sampler!r}")
     sampler = sampler.lower()
     b = _bounds(gpr, bounds)
     d = len(b)
@@ -158,6 +172,13 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
         _push_model(gpr, sampler)
         res = run_hmc(gpr.device, b, seed, nchains, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value, **s)
         gpr.n_eval += res.ngrad
+    elif sampler == "tempered":
+        from gpry_amd.tempering import DEFAULT_NLADDERS, run_tempered
+        s = tempered_settings(d, sampler_options)
+        nladders = s.pop("nladders", DEFAULT_NLADDERS)
+        _push_model(gpr, sampler)
+        res = run_tempered(gpr.device, b, seed, nladders, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value,
+                           **s)
     else:
         from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
         s = mcmc_settings(d, sampler_options)

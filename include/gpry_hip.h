@@ -322,6 +322,32 @@ int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const do
                      int64_t nchains, const double* Lp, double T, double minus_inf_value, uint64_t seed, int64_t batch,
                      int nsteps, int thin, double* X_rec, double* y_rec, double* X_last, double* y_last,
                      int64_t* naccept, int64_t* ncalls, double* X_prop, double* y_prop, double* device_ms);
+/* gpry_mcmc_ladders: tempered Metropolis ladders (parallel tempering; mcmc_ladders.hip, driven by gpry_amd/tempering.py),
+ *   for surrogates with separated modes, which the chains above cannot leave.  `nladders` ladders of `nrungs` (1 .. 8)
+ *   chains, one workgroup per ladder.  Slot r of ladder a is chain c = a nrungs + r; every per-chain array has the layout
+ *   of gpry_mcmc_chains with nchains = nladders nrungs, in chain order c.  Slot r has its own proposal factor Lp[r]
+ *   (Lp: nrungs x d x d) and temperature T[r]; its Metropolis step is that of gpry_mcmc_chains for chain c with Lp[r] and
+ *   T[r]: the same counters (3, j, batch, c, s), box test and acceptance rule.  The proposals of a ladder's slots are
+ *   evaluated together, in one pass over the training rows; each y is gpry_predict of its point alone, bit for bit.
+ *   Swap rounds: if swap_every > 0 and (s + 1) % swap_every == 0, round q = (s + 1) / swap_every - 1 follows step s.  Its
+ *   pairs are the slots (r, r + 1) with r = q (mod 2).  A pair is tried iff both current y are finite and above
+ *   minus_inf_value; with us = the first uniform of the counters (3, 17, batch, c_r, s), c_r the chain of slot r, the swap
+ *   is accepted iff log(1 - us) < (1 / T[r] - 1 / T[r + 1]) (y_{r+1} - y_r), and exchanges the states (x, u, y) of the two
+ *   slots; temperatures and proposals stay with the slot.  The records of step s are taken after its swap round.
+ *   Outputs: those of gpry_mcmc_chains, and nswap_try / nswap_acc (nladders x (nrungs - 1); NULL allowed when nrungs = 1):
+ *   the swaps tried and accepted per ladder and adjacent pair.  Test hooks: X_prop / y_prop as in gpry_mcmc_chains;
+ *   swap_log (nullable; nladders x (nsteps / swap_every) x (nrungs - 1)): 1 accepted, 0 tried and rejected, -1 not tried
+ *   (the pairs of the other parity included).  With swap_every = 0 every output of slot r equals that of chain c of
+ *   gpry_mcmc_chains called with Lp[r], T[r] and the same X0 / y0 / seed / batch, and nrungs = 1 is gpry_mcmc_chains; the
+ *   outputs of ladder a do not depend on nladders or on the context.  Refused (-1, with gpry_last_error) before anything
+ *   runs: nrungs outside 1 .. 8; a T[r] that is not positive and finite; swap_every < 0; nladders nrungs > 0x7fffffff;
+ *   swap_log given with swap_every = 0; and what gpry_mcmc_chains refuses.  Staging as gpry_mcmc_chains ("mcmc_mapped"
+ *   applies).  device_ms (nullable): device time of the call, copies included. */
+int gpry_mcmc_ladders(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0,
+                      int64_t nladders, int nrungs, const double* Lp, const double* T, double minus_inf_value,
+                      uint64_t seed, int64_t batch, int nsteps, int thin, int swap_every, double* X_rec, double* y_rec,
+                      double* X_last, double* y_last, int64_t* naccept, int64_t* ncalls, int64_t* nswap_try,
+                      int64_t* nswap_acc, double* X_prop, double* y_prop, int8_t* swap_log, double* device_ms);
 
 /* ---- Hamiltonian Monte Carlo of the posterior mean (hmc.hip; adaptation, R - 1 and weights in gpry_amd/hmc.py) ----------
  * A second sampler for the same three uses as gpry_mcmc_chains (gpry/mc.py:173-327, gpry/convergence.py:430-476,
