@@ -83,6 +83,8 @@ SIGNATURES = {
     "gpry_hmc_chains_reflect": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_double, C.c_int, C.c_double,
                                           C.c_double, C.c_uint64, C.c_int64, C.c_int, C.c_int] + [_vp] * 11
                                 + [C.c_int, C.c_int, _vp, _vp]),
+    "gpry_maximize_mean": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double,
+                                     C.c_double, C.c_double] + [_vp] * 12 + [_P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -143,6 +145,10 @@ def _given_arrays(y_given, sigma_given, M):
         if sigma_given.shape != (M,):
             raise ValueError(f"sigma_given has shape {sigma_given.shape}, the pool has {M} rows")
     return y_given, sigma_given
+
+
+# status codes of gpry_maximize_mean
+MAX_STATUS = ("CONVERGED_G", "CONVERGED_F", "STALLED", "MAXITER", "BAD_START", "BAD_GRADIENT")
 
 
 class GpryHipError(RuntimeError):
@@ -602,6 +608,44 @@ class Device:
                                              _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
                                              _ptr(out["ngrad"]), _ptr(out.get("X_prop")), _ptr(out.get("y_prop")),
                                              _ptr(out.get("dH_prop")), _ptr(out.get("G0")), *own, C.byref(ms)), name)
+        out["device_ms"] = ms.value
+        return out
+
+    # -- maximisation of the mean (gpry_amd/maximize.py drives this one) -----------------------
+    def maximize_mean(self, lo, hi, X0, y0, fixed, H0, max_iter, max_halvings, gtol, ftol, minus_inf_value, hooks=False):
+        """Projected BFGS ascents of the mean inside the box from the ``len(X0)`` starts (X0, y0) (y0 NaN: evaluated
+        first); ``fixed`` (d,): the coordinates that keep X0's values; ``H0`` (d, d): the first inverse-Hessian guess and
+        reset value, unit-cube coordinates (gpry_maximize_mean).  A dict with ``X`` (nstart, d), ``y``, ``G`` (the
+        unit-cube gradient at X), ``iters``, ``ncalls``, ``ngrad``, ``status`` (``MAX_STATUS``) and ``device_ms``; with
+        ``hooks`` also the traces ``U_tr`` (nstart, max_iter + 1, d), ``y_tr``, ``G_tr``, ``nhalv_tr`` and ``reset_tr``
+        (nstart, max_iter), unused slots NaN / -1."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X0 = _f64(X0)
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise ValueError(f"expected starts of shape (nstart, {self.d}), got {X0.shape}")
+        n, d = X0.shape
+        y0, H0 = _f64(y0, (n,)), _f64(H0, (d, d))
+        fixed = np.ascontiguousarray(fixed)
+        if fixed.shape != (d,) or fixed.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise ValueError(f"expected a boolean mask of shape ({d},), got {fixed.dtype} {fixed.shape}")
+        fixed = fixed.astype(np.uint8)
+        max_iter, max_halvings = int(max_iter), int(max_halvings)
+        out = dict(X=np.empty((n, d)), y=np.empty(n), G=np.empty((n, d)), iters=np.zeros(n, np.int32),
+                   ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
+        tr = {}
+        if hooks:
+            m = max(max_iter, 0)
+            tr = dict(U_tr=np.empty((n, m + 1, d)), y_tr=np.empty((n, m + 1)), G_tr=np.empty((n, m + 1, d)),
+                      nhalv_tr=np.empty((n, m), np.int32), reset_tr=np.empty((n, m), np.int32))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_maximize_mean(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(fixed), _ptr(H0),
+                                                 max_iter, max_halvings, float(gtol), float(ftol), float(minus_inf_value),
+                                                 _ptr(out["X"]), _ptr(out["y"]), _ptr(out["G"]), _ptr(out["iters"]),
+                                                 _ptr(out["ncalls"]), _ptr(out["ngrad"]), _ptr(out["status"]),
+                                                 _ptr(tr.get("U_tr")), _ptr(tr.get("y_tr")), _ptr(tr.get("G_tr")),
+                                                 _ptr(tr.get("nhalv_tr")), _ptr(tr.get("reset_tr")), C.byref(ms)),
+                    "gpry_maximize_mean")
+        out.update(tr)
         out["device_ms"] = ms.value
         return out
 

@@ -1,0 +1,231 @@
+"""Maximum and profiles of the surrogate's posterior mean, with the ascents run on the device.
+
+A run ends with a weighted sample of the surrogate (``gpry_amd/mc.py``); this module adds what a user asks for next: the
+surrogate's best-fit point (``maximize_gp``) and profile likelihoods over one or two parameters (``profile_gp``).  Whole
+batches of constrained local maximisations run in one HIP kernel (``gpry_amd/csrc/maximize.hip``), value and gradient of
+the mean evaluated inside it.  This module keeps the rest (starts, the first inverse-Hessian guess, the grid and its
+continuation passes) and talks to the device through one call, so any object with the same method can stand in for it
+(the CPU tests use a numpy one, tests/tools/maximize_numpy.py):
+
+``dev.maximize_mean(lo, hi, X0, y0, fixed, H0, max_iter, max_halvings, gtol, ftol, minus_inf_value)
+    -> {"X": (nstart, d), "y", "G": (nstart, d), "iters", "ncalls", "ngrad", "status", "device_ms"}``
+
+The device's part, per start: a projected BFGS ascent in the unit cube u = (x - lo) / (hi - lo) with an Armijo
+backtracking search; coordinates on a wall with the gradient pointing outward, and the ``fixed`` ones, do not move; the
+objective is ``gpr.predict(x[None])`` bit for bit (a gated point is -inf and is never accepted), the gradient that of
+the unclipped, ungated mean.  ``status`` is an index into ``MAX_STATUS``; the full statement is in include/gpry_hip.h
+(gpry_maximize_mean).
+
+No multi-GPU split of the starts, and no maximisation of the acquisition function (it needs sigma and its gradient,
+O(N^2) per point: a different kernel).
+"""
+from collections import namedtuple
+from time import time
+
+import numpy as np
+
+from gpry_amd.mcmc import _weighted_cov
+from gpry_amd.nested import cholesky_ridged
+
+MAX_STATUS = ("CONVERGED_G", "CONVERGED_F", "STALLED", "MAXITER", "BAD_START", "BAD_GRADIENT")
+DISTINCT_TOL = 1e-6
+
+MaxResult = namedtuple("MaxResult", ["x", "y", "X_all", "y_all", "G_all", "status", "iters", "ncalls", "ngrad",
+                                     "n_distinct", "device_s", "wall_s"])
+MaxResult.__doc__ = """Output of ``maximize_gp``.  x, y: the best end point (the largest finite y).  X_all, y_all, G_all:
+every start's end point, its y and its unit-cube gradient; status (index into ``MAX_STATUS``), iters, ncalls (evaluations
+of the mean), ngrad per start.  n_distinct: the end points with a finite y that lie further than 1e-6 apart in the unit
+cube, i.e. the local maxima found.  device_s / wall_s: time in the device call / in the whole function."""
+
+ProfileResult = namedtuple("ProfileResult", ["grid", "y", "X", "status", "ncalls", "device_s"])
+ProfileResult.__doc__ = """Output of ``profile_gp``.  grid (G, len(params)): the fixed values; y (G,): the largest mean
+with them fixed (-inf: no start of the row was usable); X (G, d): where; status (G,): the status of the start that gave
+it (-1: none); ncalls: evaluations of the mean, all passes (``gpr.n_eval`` grows by it); device_s: time in the device calls."""
+
+
+def _setup(gpr, bounds):
+    from gpry_amd.mc import _bounds
+    b = _bounds(gpr, bounds)
+    if b.ndim != 2 or b.shape[1] != 2 or not np.all(b[:, 0] < b[:, 1]):
+        raise ValueError(f"bounds must be (d, 2) with lo < hi, got {b!r}")
+    return b, np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+
+
+def _usable(X, y, lo, hi, minus_inf_value):
+    """``mcmc._starts``' usability test: finite y above ``minus_inf_value``, inside the box; best first."""
+    X, y = np.atleast_2d(np.asarray(X, dtype=float)), np.asarray(y, dtype=float).ravel()
+    ok = np.isfinite(y) & (y > minus_inf_value) & np.all((X >= lo) & (X <= hi), axis=1)
+    X, y = X[ok], y[ok]
+    order = np.argsort(-y, kind="stable")
+    return X[order], y[order]
+
+
+def _h0(covmat, Xt, yt, span):
+    d = len(span)
+    if covmat is not None:
+        C = np.asarray(covmat, dtype=float)
+        if C.shape != (d, d) or not np.all(np.isfinite(C)):
+            raise ValueError(f"covmat must be a finite ({d}, {d}) matrix")
+        H0 = C / np.outer(span, span)
+        if not np.allclose(H0, H0.T) or np.min(np.linalg.eigvalsh(H0)) <= 0:
+            raise ValueError("covmat must be symmetric positive definite")
+        return np.ascontiguousarray(0.5 * (H0 + H0.T))
+    if len(Xt) == 0:
+        return np.eye(d)
+    L = cholesky_ridged(np.atleast_2d(_weighted_cov(Xt, yt)) / np.outer(span, span))
+    return np.ascontiguousarray(L @ L.T)
+
+
+def _check_controls(max_iter, max_halvings, gtol, ftol):
+    if int(max_iter) != max_iter or int(max_iter) < 0:
+        raise ValueError(f"max_iter = {max_iter!r} must be an int >= 0")
+    if int(max_halvings) != max_halvings or int(max_halvings) < 0:
+        raise ValueError(f"max_halvings = {max_halvings!r} must be an int >= 0")
+    if not (np.isfinite(gtol) and gtol >= 0) or not (np.isfinite(ftol) and ftol >= 0):
+        raise ValueError(f"gtol = {gtol}, ftol = {ftol} must be finite and >= 0")
+
+
+def _mask(fixed, d):
+    m = np.zeros(d, bool)
+    if fixed is None:
+        return m
+    f = np.asarray(fixed)
+    if f.dtype == bool:
+        if f.shape != (d,):
+            raise ValueError(f"a boolean fixed mask must have shape ({d},), got {f.shape}")
+        return f.copy()
+    f = np.atleast_1d(f)
+    if f.ndim != 1 or not np.issubdtype(f.dtype, np.integer) or np.any((f < 0) | (f >= d)) or len(set(f.tolist())) != len(f):
+        raise ValueError(f"fixed = {fixed!r}: distinct parameter indices in 0 .. {d - 1} or a boolean mask are needed")
+    m[f] = True
+    return m
+
+
+def n_distinct(X, y, lo, hi, tol=DISTINCT_TOL):
+    """The end points with a finite y further apart than ``tol`` in the unit cube (greedy, best first)."""
+    fin = np.isfinite(y)
+    U = ((X - lo) / (hi - lo))[fin][np.argsort(-y[fin], kind="stable")]
+    kept = np.empty_like(U)
+    n = 0
+    for u in U:
+        if n == 0 or np.all(np.max(np.abs(kept[:n] - u), axis=1) > tol):
+            kept[n] = u
+            n += 1
+    return n
+
+
+def maximize_gp(gpr, bounds=None, nstarts=64, starts=None, fixed=None, covmat=None, max_iter=200, max_halvings=12,
+                gtol=1e-6, ftol=0.0, seed=None):
+    """The maximum of the surrogate's posterior mean inside ``bounds`` (default ``gpr.trust_bounds``, else
+    ``gpr.bounds``), from many local ascents on the device: a ``MaxResult``.
+
+    Starts: the ``nstarts`` best usable training points (finite y above ``gpr.minus_inf_value``, inside the box), or the
+    rows of ``starts`` when given.  fixed: indices (or a boolean mask) of the coordinates that keep their start values.
+    H0, the first inverse-Hessian guess: ``covmat`` (raw coordinates) or the exp(y - y_max)-weighted covariance of the
+    training set, in the unit cube.  gtol: bound on the unit-cube gradient over the free coordinates; ftol: stop when a
+    step gains no more than ftol max(1, |y|) (0: off; the ascent then ends on gtol or when no step improves y any more,
+    status STALLED).  ``seed`` is accepted for symmetry with the samplers; the algorithm has no randomness.  The
+    defaults are provisional: nothing about them has been tuned on a real run yet.  ``gpr.n_eval`` grows by ``ncalls``,
+    the evaluations of the mean (the gradients are counted in ``ngrad``)."""
+    t_start = time()
+    from gpry_amd.mc import _push_model
+    b, lo, hi = _setup(gpr, bounds)
+    d = len(lo)
+    _check_controls(max_iter, max_halvings, gtol, ftol)
+    mask = _mask(fixed, d)
+    Xt, yt = _usable(gpr.X_train, gpr.y_train, lo, hi, gpr.minus_inf_value)
+    if starts is not None:
+        X0 = np.ascontiguousarray(np.atleast_2d(np.asarray(starts, dtype=float)))
+        if X0.ndim != 2 or X0.shape[1] != d or len(X0) == 0 or not np.all(np.isfinite(X0)):
+            raise ValueError(f"starts must be finite rows of dimension {d}, got shape {X0.shape}")
+        if not np.all((X0 >= lo) & (X0 <= hi)):
+            raise ValueError("every start must lie inside the bounds")
+    else:
+        if int(nstarts) != nstarts or int(nstarts) < 1:
+            raise ValueError(f"nstarts = {nstarts!r}: at least one start is needed")
+        if len(Xt) == 0:
+            raise ValueError("no training point with a finite y inside the bounds to start from")
+        X0 = np.ascontiguousarray(Xt[:int(nstarts)])
+    H0 = _h0(covmat, Xt, yt, hi - lo)
+    _push_model(gpr, "maximize")
+    out = gpr.device.maximize_mean(lo, hi, X0, np.full(len(X0), np.nan), mask, H0, int(max_iter), int(max_halvings),
+                                   float(gtol), float(ftol), gpr.minus_inf_value)
+    gpr.n_eval += int(np.sum(out["ncalls"]))
+    y = out["y"]
+    fin = np.isfinite(y) & (y > gpr.minus_inf_value)
+    if not fin.any():
+        raise ValueError("no start has a finite mean above minus_inf_value")
+    best = int(np.flatnonzero(fin)[np.argmax(y[fin])])
+    return MaxResult(x=out["X"][best].copy(), y=float(y[best]), X_all=out["X"], y_all=y, G_all=out["G"],
+                     status=out["status"], iters=out["iters"], ncalls=out["ncalls"], ngrad=out["ngrad"],
+                     n_distinct=n_distinct(out["X"], np.where(fin, y, np.nan), lo, hi), device_s=out["device_ms"] / 1e3,
+                     wall_s=time() - t_start)
+
+
+def profile_gp(gpr, params, grid, bounds=None, nstarts=16, continuation=1, covmat=None, max_iter=200, max_halvings=12,
+               gtol=1e-6, ftol=0.0):
+    """Profile of the surrogate's posterior mean over the parameters ``params`` (one index or a tuple of indices):
+    for every row of ``grid`` ((G,) or (G, len(params)); every value inside the bounds) the maximum of the mean over
+    the other coordinates: a ``ProfileResult``.
+
+    For every grid row the starts are the ``nstarts`` best usable training points with the fixed coordinates overwritten
+    by the row's values; all G nstarts ascents go through one device call (one mask serves them all).  Then
+    ``continuation`` passes: every row is restarted from the optima of its two neighbours in grid order, their fixed
+    coordinates overwritten, and the better result is kept, which removes the jumps between branches that independent
+    maximisations leave.  The other arguments and the remark on the defaults are ``maximize_gp``'s."""
+    from gpry_amd.mc import _push_model
+    b, lo, hi = _setup(gpr, bounds)
+    d = len(lo)
+    _check_controls(max_iter, max_halvings, gtol, ftol)
+    par = np.atleast_1d(np.asarray(params))
+    if par.ndim != 1 or len(par) == 0 or not np.issubdtype(par.dtype, np.integer):
+        raise ValueError(f"params = {params!r}: one index or a tuple of indices is needed")
+    mask = _mask(par, d)
+    grid = np.asarray(grid, dtype=float)
+    if grid.ndim == 1 and len(par) == 1:
+        grid = grid[:, None]
+    if grid.ndim != 2 or grid.shape[1] != len(par) or len(grid) == 0:
+        raise ValueError(f"grid of shape {grid.shape} does not fit {len(par)} parameter(s)")
+    if not np.all(np.isfinite(grid)) or not np.all((grid >= lo[par]) & (grid <= hi[par])):
+        raise ValueError("every grid value must lie inside the bounds")
+    if int(nstarts) != nstarts or int(nstarts) < 1 or int(continuation) != continuation or int(continuation) < 0:
+        raise ValueError(f"nstarts = {nstarts!r}, continuation = {continuation!r}")
+    G, ns = len(grid), int(nstarts)
+    Xt, yt = _usable(gpr.X_train, gpr.y_train, lo, hi, gpr.minus_inf_value)
+    if len(Xt) == 0:
+        raise ValueError("no training point with a finite y inside the bounds to start from")
+    H0 = _h0(covmat, Xt, yt, hi - lo)
+    _push_model(gpr, "maximize")
+    ctl = (int(max_iter), int(max_halvings), float(gtol), float(ftol), gpr.minus_inf_value)
+    device_ms, ncalls = 0.0, 0
+
+    def run(X0):
+        nonlocal device_ms, ncalls
+        out = gpr.device.maximize_mean(lo, hi, np.ascontiguousarray(X0), np.full(len(X0), np.nan), mask, H0, *ctl)
+        device_ms += out["device_ms"]
+        n = int(np.sum(out["ncalls"]))
+        ncalls += n
+        gpr.n_eval += n
+        y = np.where(np.isfinite(out["y"]) & (out["y"] > gpr.minus_inf_value), out["y"], -np.inf)
+        return out["X"], y, out["status"]
+
+    base = Xt[:ns]
+    X0 = np.repeat(base[None], G, axis=0)
+    X0[:, :, par] = grid[:, None, :]
+    Xo, yo, so = run(X0.reshape(-1, d))
+    Xo, yo, so = Xo.reshape(G, -1, d), yo.reshape(G, -1), so.reshape(G, -1)
+    j = np.argmax(yo, axis=1)
+    rows = np.arange(G)
+    X, y, st = Xo[rows, j].copy(), yo[rows, j].copy(), so[rows, j].astype(np.int64)
+    st[np.isneginf(y)] = -1
+    for _ in range(int(continuation)):
+        src = [(i, k) for i in range(G) for k in (i - 1, i + 1) if 0 <= k < G and np.isfinite(y[k])]
+        if not src:
+            break
+        Xc = np.array([X[k] for _, k in src])
+        Xc[:, par] = grid[[i for i, _ in src]]
+        Xn, yn, sn = run(Xc)
+        for r, (i, _) in enumerate(src):
+            if yn[r] > y[i]:
+                X[i], y[i], st[i] = Xn[r], yn[r], sn[r]
+    return ProfileResult(grid=grid, y=y, X=X, status=st, ncalls=ncalls, device_s=device_ms / 1e3)

@@ -407,6 +407,51 @@ int gpry_hmc_chains_reflect(gpry_ctx* ctx, const double* lo, const double* hi, c
                             double* X_prop, double* y_prop, double* dH_prop, double* G0, int reflect, int max_reflect,
                             int64_t* nreflect, double* device_ms);
 
+/* ---- Maximum and profiles of the posterior mean (maximize.hip; starts, H0, grids and continuation in
+ * gpry_amd/maximize.py) ------------------------------------------------------------------------------------------------
+ * gpry_maximize_mean: `nstart` local maximisations of the mean inside the box [lo, hi], one workgroup each, from the rows
+ * of X0 (nstart x d) / y0 (nstart; NaN: the start is evaluated first and counted in ncalls).  No randomness.  Unit-cube
+ * coordinates u = (x - lo) / (hi - lo).  The objective y(x) is gpry_predict of the point, bit for bit (clip and gates
+ * included: a gated point is -inf).  The gradient g is that of the unclipped, ungated mean with respect to u, as in
+ * gpry_hmc_chains.  fixed: d bytes, one mask per call; a coordinate with fixed[k] != 0 keeps the value X0 gives it, bit for
+ * bit.  H0: d x d, row-major, symmetric positive definite, unit-cube coordinates: the first inverse-Hessian guess H and
+ * the value H is reset to.  rn(.) below: the product rounded to double before it is added (no FMA); every sum runs in the
+ * order of the coordinates, from 0.0.
+ *   A start whose y is not finite or not > minus_inf_value, or which lies outside the box, ends at once with BAD_START
+ *   (no gradient; G_out NaN); one whose first gradient is not finite with BAD_GRADIENT.  Then, from the state (u, y, g, H):
+ *   1. Free set: k is free unless fixed[k], or u_k == 0 && g_k <= 0, or u_k == 1 && g_k >= 0.  No free coordinate, or
+ *      max_{k free} |g_k| <= gtol: stop, CONVERGED_G.  Else, after max_iter iterations: stop, MAXITER.
+ *   2. Direction: if the free set differs from the last iteration's and H != H0, H = H0 (a reset).  p_k = sum_{j free}
+ *      rn(H_kj g_j) for free k, 0 otherwise.  If sum_{k free} rn(p_k g_k) is not > 0: with H != H0, H = H0 (a reset) and
+ *      p again; with H == H0 stop, STALLED.
+ *   3. Search: t = 1, 1/2, ..., at most max_halvings + 1 trials.  u'_k = clamp(u_k + rn(t p_k), 0, 1) for free k, u_k
+ *      otherwise; x'_k = clamp(lo_k + rn(u'_k (hi_k - lo_k)), lo_k, hi_k) where u'_k != u_k (hi_k itself where u'_k == 1),
+ *      x_k otherwise.  u' == u in
+ *      every coordinate: stop, STALLED.  The trial is accepted iff y' = y(x') is finite, y' > minus_inf_value and
+ *      y' >= y + rn(1e-4 sum_{k free} rn(g_k (u'_k - u_k))).  If every trial fails: with H != H0, H = H0 (a reset), p
+ *      again and one more search; with H == H0 stop, STALLED (the normal end once improvements fall below the rounding
+ *      of y).
+ *   4. g' = the gradient at x'.  Not finite: the accepted point becomes the state, stop, BAD_GRADIENT.
+ *   5. s = u' - u, q = g - g', both 0 outside the free set; sq = sum rn(s_k q_k), ss, qq likewise, Hq_k = sum_{j free}
+ *      rn(H_kj q_j), qHq = sum rn(q_k Hq_k).  If sq > rn(1e-10 sqrt(rn(ss qq))): rho = 1 / sq, c = rn(rn(rho rho) qHq) + rho,
+ *      H_kj = (H_kj - rn(rho (rn(s_k Hq_j) + rn(Hq_k s_j)))) + rn(c rn(s_k s_j)) for free k, j (H != H0 from here on).
+ *   6. (u', y', g') becomes the state, the iteration is counted.  y' - y <= rn(ftol max(1, |y'|)): stop, CONVERGED_F.
+ * Outputs per start: X_out (nstart x d), y_out, G_out (nstart x d; g at X_out), iters (completed iterations), ncalls
+ * (evaluations of the mean), ngrad, status (0 CONVERGED_G, 1 CONVERGED_F, 2 STALLED, 3 MAXITER, 4 BAD_START,
+ * 5 BAD_GRADIENT).  A start's outputs depend on its row alone, not on nstart, its position or the context.
+ * Test hooks, all NULL or all given (no memory and no kernel code for them otherwise): U_tr (nstart x (max_iter + 1) x d),
+ * y_tr (nstart x (max_iter + 1)), G_tr (as U_tr): the state at the start of iteration i, i = 0 .. iters; nhalv_tr and
+ * reset_tr (nstart x max_iter, int): of every iteration that reached its search, the halvings of the accepted trial (-1:
+ * none was accepted) and the resets of H.  Unused slots are NaN / -1.
+ * Refused (-1, with gpry_last_error): d > 32; lo >= hi; max_iter outside 0 .. 100000; max_halvings outside 0 .. 1000; gtol or
+ * ftol negative or not finite; an H0 entry that is not finite.  Stops the resident predict kernel first.  device_ms
+ * (nullable): device time of the call, copies included. */
+int gpry_maximize_mean(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0,
+                       int64_t nstart, const unsigned char* fixed, const double* H0, int max_iter, int max_halvings,
+                       double gtol, double ftol, double minus_inf_value, double* X_out, double* y_out, double* G_out,
+                       int* iters, int64_t* ncalls, int64_t* ngrad, int* status, double* U_tr, double* y_tr, double* G_tr,
+                       int* nhalv_tr, int* reset_tr, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
