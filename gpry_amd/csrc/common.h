@@ -150,6 +150,12 @@ struct gpry_ctx {
     // top-k scratch
     unsigned long long* dkeys = nullptr; int64_t keys_cap = 0;
     unsigned int* dhist = nullptr;
+    // "select_fused": 12 x 256 digit counters, one array per pass, and behind them the 12 SelState slots the passes hand on
+    unsigned int* dselp = nullptr;
+    enum { SELP_HIST_WORDS = 12 * 256, SELP_WORDS = 12 * 256 + 12 * 8 };
+    int opt_select_fused = 1;          // 1: every select pass derives the previous pass's digit itself (no scan launches; sweep_topk.hip)
+    int opt_prune_one_select = 1;      // 1: the first contraction round answers from its own records where these provably are the shortlist
+    int opt_sweep_small_map = 1;       // 1: a one-pass contraction of at most 512 tiles launches one workgroup per tile, longest row tile first (sweep_gemm.hip)
     gpry_cand* dcand = nullptr; int64_t cand_cap = 0;
     unsigned long long* dsel = nullptr;  // DSEL_WORDS words: select state and the counters of the sweep
     enum { DSEL_NAN = 0,       // count_nan_kernel (between selections)
@@ -312,6 +318,8 @@ enum GemmEpi { EPI_STORE = 0, EPI_STORE_NEG = 1, EPI_SUB = 2, EPI_SUMSQ = 3 };
 // decides the balance: tiles of equal k-length are neighbours (row-wise triangular order for lower-only
 // square outputs, column-major where the length depends on the tile column), longest first
 enum GemmTileMap { TM_ROWMAJOR = 0, TM_SWEEP = 1, TM_BALANCED = 2 };
+// bit 12 of GemmArgs::tile_map, for sweep_gemm_dma_sp_launch alone: the small-launch map is allowed (option "sweep_small_map")
+#define TM_SWEEP_SMALL (1 << 12)
 
 struct GemmBatchItem { int64_t a_off, b_off, c_off; int M, N, K, pad; };
 

@@ -243,7 +243,7 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
     overlap_plan_free(ctx);
     void* bufs[] = {ctx->dX, ctx->dXs, ctx->dy, ctx->dnoise, ctx->dA, ctx->dV, ctx->dW, ctx->dW2, ctx->dW3,
                     ctx->dalpha_, ctx->dvec, ctx->dinfo, ctx->dparams, ctx->dXc, ctx->dmask, ctx->dy_all,
-                    ctx->dsig_all, ctx->dacq_all, ctx->dKst, ctx->dpart, ctx->dkeys, ctx->dhist,
+                    ctx->dsig_all, ctx->dacq_all, ctx->dKst, ctx->dpart, ctx->dkeys, ctx->dhist, ctx->dselp,
                     ctx->dcand, ctx->dsel, ctx->dU, ctx->dXkb, ctx->dkbout, ctx->pr.dXc, ctx->pr.dmask,
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
@@ -311,6 +311,9 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("sweep_overlap", opt_sweep_overlap, 0, 1, (void)0),
     OPT_INT("sweep_prune", opt_sweep_prune, 0, 1, (void)0),
     OPT_INT("sweep_mean_bound", opt_sweep_mean_bound, 0, 1, (void)0),
+    OPT_INT("sweep_small_map", opt_sweep_small_map, 0, 1, (void)0),
+    OPT_INT("select_fused", opt_select_fused, 0, 1, (void)0),
+    OPT_INT("prune_one_select", opt_prune_one_select, 0, 1, (void)0),
     OPT_INT("chol_stacked", opt_chol_stacked, 0, BIG, c->lml_cache = false),
     OPT_INT("chol_stacked_dense", opt_chol_stacked_dense, 0, 1, c->lml_cache = false),
     OPT_INT("predict_gates", opt_predict_gates, 0, 1, (void)0),

@@ -389,6 +389,7 @@ static int contract_sweep(gpry_ctx* ctx, const double* Kst, int64_t ncols, doubl
     g.A = ctx->dV; g.lda = ctx->Np; g.B = Kst; g.ldb = ncols; g.C = ss_part; g.ldc = ncols;
     g.M = (int)ctx->Np; g.N = (int)ncols; g.K = (int)ctx->Np;
     g.kmode = KM_A_LOWER; g.lower_only = 0; g.tile_map = TM_SWEEP | (3 << 4);     // super-tiles of 8 row tiles x 8 candidate tiles
+    if (ctx->opt_sweep_small_map) g.tile_map |= TM_SWEEP_SMALL;                   // (a launch of few tiles: one workgroup per tile)
     // LDS-DMA staging + software pipeline (sweep_gemm.hip); "gemm_dma" = 0: the register-staged engine (comparator)
     if (ctx->opt_gemm_dma) return sweep_gemm_dma_sp_launch(ctx, g);
     return gemm_f64_launch(ctx, g, false, false, EPI_SUMSQ);

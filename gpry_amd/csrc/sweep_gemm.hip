@@ -22,6 +22,7 @@
 #define A_DOUBLES 2048   // 128 x 16, unpadded
 #define B_DOUBLES 2304   // 16 x 144
 #define BUF_DOUBLES (A_DOUBLES + B_DOUBLES)
+#define SMALL_MAP_TILES 512   // workgroup slots of the device (256 CUs x 2): launches up to here take the small-launch map
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -112,6 +113,7 @@ __global__ __launch_bounds__(256, 2) void sweep_gemm_dma_sp_kernel(GemmArgs g) {
     const int ta = (g.tile_map >> 4) & 15, tc = 6 - ta;
     const int nsi = (tiles_m + (1 << ta) - 1) >> ta, nsj = (tiles_n + (1 << tc) - 1) >> tc;
     const int q = blockIdx.x >> 3;                       // position in the XCD's queue
+    const bool small_map = (g.tile_map & TM_SWEEP_SMALL) && tiles_m * tiles_n <= SMALL_MAP_TILES;
     int ti, tj;
     bool valid, desc;
     {
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void sweep_gemm_dma_sp_kernel(GemmArgs g) {
         ti = (si << ta) + rowin;
         tj = (sj << tc) + (within & ((1 << tc) - 1));
         valid = s < nsi * nsj && si >= 0 && ti < tiles_m && tj < tiles_n;
-        if (nsi == 1) {
+        if (nsi == 1 || small_map) {
             // A model of up to 1024 rows is ONE super-row whose row tiles differ by up to 8x in length: every super-tile mixes
             // them, and the launch ends with long tiles running beside idle slots (a k = 1024 tile takes ~ 200 us of a 1.9-ms
             // launch at M = 1e5).  Longest row tile first over the WHOLE launch instead: the tail is made of the shortest tiles;
@@ -150,7 +152,10 @@ __global__ __launch_bounds__(256, 2) void sweep_gemm_dma_sp_kernel(GemmArgs g) {
             ti = tiles_m - 1 - row;
             tj = (int)blockIdx.x - row * tiles_n;
             valid = row < tiles_m;
-            desc = false;           // (as above for si = 0: the walk direction is a function of the row tile alone)
+            // A launch of few tiles over a larger model (the compact batches of a pruned sweep: TM_SWEEP_SMALL, one workgroup per
+            // tile) takes the same order: the super-tile map would give each of the first nsi * nsj XCDs a whole super-tile and
+            // leave the others idle, the longest 64 tiles two to a CU.  The walk direction stays the row tile's own.
+            desc = nsi > 1 && ((nsi - 1 - (ti >> ta)) & 1);     // (nsi = 1: false, as above for si = 0)
         }
     }
     if (valid) {
@@ -293,7 +298,8 @@ int sweep_gemm_dma_sp_launch(gpry_ctx* ctx, const GemmArgs& g) {
     const int tiles_m = g.M / BM, tiles_n = g.N / BN;
     const int a = (g.tile_map >> 4) & 15, c = 6 - a;
     const int64_t nsi = (tiles_m + (1 << a) - 1) >> a, nsj = (tiles_n + (1 << c) - 1) >> c;
-    const dim3 grid(nsi == 1 ? (unsigned)(tiles_m * tiles_n) : (unsigned)(((nsi * nsj + 7) / 8 * 8) * 64));
+    const bool small_map = (g.tile_map & TM_SWEEP_SMALL) && tiles_m * tiles_n <= SMALL_MAP_TILES;
+    const dim3 grid(nsi == 1 || small_map ? (unsigned)(tiles_m * tiles_n) : (unsigned)(((nsi * nsj + 7) / 8 * 8) * 64));
     hipLaunchKernelGGL(sweep_gemm_dma_sp_kernel, grid, dim3(256), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

@@ -93,6 +93,105 @@ __global__ void select_emit_kernel(const unsigned long long* __restrict__ keys, 
     if ((threadIdx.x & 63) == 0 && best_below) atomicMax(&counters[1], best_below);
 }
 
+// ---- option "select_fused": the same 12 passes without the scan launches ----------------------------------------
+// Pass p histograms into its own counters hist[p]; the launch of pass p + 1 (and the emit launch for p = 11) first derives
+// the digit of pass p from them -- every block for itself: a suffix scan of the 256 counters over 256 threads -- and block 0
+// leaves the state in slot p + 1 for the launch after it.  A launch reads slot p and writes slot p + 1: no slot is read and
+// written in one launch, and no workgroup waits for another.  One memset per select clears all the counters.
+
+// state after pass `pass`, from the state `s` pass `pass` was histogrammed with and its counters (select_scan_kernel's walk:
+// the largest digit whose suffix count reaches k_rem); blockDim.x = 256, every thread returns the same state
+__device__ __forceinline__ SelState next_state(SelState s, const unsigned int* __restrict__ hist, int pass) {
+    __shared__ unsigned long long suf[2][256 + 1];
+    __shared__ unsigned long long pick[2];      // digit, count above it
+    const int t = threadIdx.x;
+    suf[0][t] = hist[t];
+    if (t == 0) { suf[0][256] = 0; suf[1][256] = 0; }
+    __syncthreads();
+    int cur = 0;
+    for (int off = 1; off < 256; off <<= 1) {      // suf[t] = sum of the counters t .. 255
+        suf[cur ^ 1][t] = suf[cur][t] + (t + off < 256 ? suf[cur][t + off] : 0ull);
+        cur ^= 1;
+        __syncthreads();
+    }
+    const unsigned long long k = s.k_rem, here = suf[cur][t], above = suf[cur][t + 1];
+    if (here >= k && above < k) { pick[0] = (unsigned long long)t; pick[1] = above; }
+    if (t == 0 && here < k) { pick[0] = 0ull; pick[1] = here; }         // (fewer keys than k_rem: digit 0, as the walk ends)
+    __syncthreads();
+    const unsigned long long dsel = pick[0];
+    s.k_rem = k - pick[1];
+    if (pass < 8) s.hi |= dsel << (56 - 8 * pass);
+    else s.lo |= ((unsigned int)dsel) << (24 - 8 * (pass - 8));
+    __syncthreads();                            // (the arrays are free again)
+    return s;
+}
+__device__ __forceinline__ SelState first_state(unsigned long long K) {
+    SelState s; s.hi = 0ull; s.lo = 0u; s.pad = 0u; s.k_rem = K; s.count_ge = 0ull;
+    return s;
+}
+
+// hist: this pass's 256 counters (cleared); slots: the 12 states, slot p = the state pass p is histogrammed with
+__global__ __launch_bounds__(256) void select_hist_fused_kernel(const unsigned long long* __restrict__ keys, int64_t M,
+                                                                unsigned long long K, SelState* __restrict__ slots,
+                                                                int pass, unsigned int* __restrict__ hist_all) {
+    __shared__ unsigned int h[256];
+    h[threadIdx.x] = 0;
+    const SelState s = pass == 0 ? first_state(K) : next_state(slots[pass - 1], hist_all + 256 * (pass - 1), pass - 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) slots[pass] = s;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < M; base += stride) {      // (uniform over the block)
+        const int64_t i = base + threadIdx.x;
+        unsigned long long k = i < M ? keys[i] : 0ull;
+        const bool act = k != 0ull && prefix_match(k, (unsigned)i, s, pass);       // (0: excluded, or past the end)
+        const unsigned dg = act ? digit_of(k, (unsigned)i, pass) : 0u;
+        const unsigned long long m = __ballot(act);
+        if (m == 0ull) continue;
+        // all active lanes on one digit (the leading bytes of a pool of similar values): one add of their number
+        const int first = __ffsll((long long)m) - 1;
+        const unsigned d0 = (unsigned)__shfl((int)dg, first);
+        if (__ballot(act && dg == d0) == m) {
+            if (lane == first) atomicAdd(&h[d0], (unsigned)__popcll(m));
+        } else if (act) atomicAdd(&h[dg], 1u);
+    }
+    __syncthreads();
+    unsigned int* hist = hist_all + 256 * pass;
+    if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+// select_emit_kernel behind the fused passes: the threshold from slot 11 and the counters of pass 11; one atomicMax per block
+__global__ __launch_bounds__(256) void select_emit_fused_kernel(const unsigned long long* __restrict__ keys, int64_t M,
+                                                                const SelState* __restrict__ slots,
+                                                                const unsigned int* __restrict__ hist_all,
+                                                                const double* __restrict__ acq, const double* __restrict__ y,
+                                                                const double* __restrict__ sig, gpry_cand* __restrict__ out,
+                                                                int64_t cap, unsigned long long* counters) {
+    __shared__ unsigned long long wbest[4];
+    const SelState s = next_state(slots[11], hist_all + 256 * 11, 11);
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    unsigned long long best_below = 0ull;
+    for (; i < M; i += stride) {
+        unsigned long long k = keys[i];
+        if (k == 0ull) continue;
+        bool ge = (k > s.hi) || (k == s.hi && (unsigned)i >= s.lo);
+        if (ge) {
+            unsigned long long pos = atomicAdd(&counters[0], 1ull);
+            if ((int64_t)pos < cap) { gpry_cand c; c.acq = acq[i]; c.y = y[i]; c.sigma = sig[i]; c.idx = i; out[pos] = c; }
+        } else if (k > best_below) best_below = k;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        unsigned long long o = __shfl_xor(best_below, off);
+        if (o > best_below) best_below = o;
+    }
+    if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = best_below;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) if (wbest[w] > best_below) best_below = wbest[w];
+        if (best_below) atomicMax(&counters[1], best_below);
+    }
+}
+
 // all sweep results as shortlist records (small pools: selected on the host)
 __global__ void cand_records_kernel(const double* __restrict__ acq, const double* __restrict__ y, const double* __restrict__ sig,
                                     int64_t M, gpry_cand* __restrict__ out) {
@@ -141,9 +240,27 @@ static int device_select(gpry_ctx* ctx, const double* src, int64_t M, int64_t K,
         HIP_TRY(ctx, hipStreamSynchronize(st));
         return 0;
     }
+    unsigned long long* dcnt = ctx->dsel + gpry_ctx::DSEL_EMIT;
+    if (ctx->opt_select_fused) {
+        if (!ctx->dselp) GPRY_TRY(dev_alloc(ctx, &ctx->dselp, gpry_ctx::SELP_WORDS));
+        SelState* slots = reinterpret_cast<SelState*>(ctx->dselp + gpry_ctx::SELP_HIST_WORDS);      // 12 x 32 bytes
+        HIP_TRY(ctx, hipMemsetAsync(dcnt, 0, 16, st));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dselp, 0, sizeof(unsigned int) * gpry_ctx::SELP_HIST_WORDS, st));
+        const unsigned nbh = nb < 2048 ? nb : 2048, nbe = nb < 1024 ? nb : 1024;
+        for (int pass = 0; pass < 12; pass++)
+            hipLaunchKernelGGL(select_hist_fused_kernel, dim3(nbh), dim3(256), 0, st, ctx->dkeys, M, (unsigned long long)K, slots,
+                               pass, ctx->dselp);
+        hipLaunchKernelGGL(select_emit_fused_kernel, dim3(nbe), dim3(256), 0, st, ctx->dkeys, M, slots, ctx->dselp, ctx->dacq_all,
+                           ctx->dy_all, ctx->dsig_all, ctx->dcand, K, dcnt);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(cnt, dcnt, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if ((int64_t)cnt[0] != K)
+            return gpry_fail(ctx, -4, "topk: selected %llu candidates, expected %lld", cnt[0], (long long)K);
+        return 0;
+    }
     SelState s0; memset(&s0, 0, sizeof(s0)); s0.k_rem = (unsigned long long)K;
     SelState* dst = reinterpret_cast<SelState*>(ctx->dsel + gpry_ctx::DSEL_STATE);      // 32 bytes
-    unsigned long long* dcnt = ctx->dsel + gpry_ctx::DSEL_EMIT;
     HIP_TRY(ctx, hipMemcpyAsync(dst, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(dcnt, 0, 16, st));
     HIP_TRY(ctx, hipMemsetAsync(ctx->dhist, 0, 256 * sizeof(unsigned int), st));
@@ -250,6 +367,55 @@ __global__ void cand_idx_kernel(const gpry_cand* __restrict__ c, int64_t n, int6
     if (i < n && c[i].sigma == PRUNED_SIGMA) idx[atomicAdd(cnt, 1ull)] = c[i].idx;
 }
 
+// the records (acq, y, sigma, idx) of the selected candidates as the resident arrays hold them now
+__global__ void cand_refresh_kernel(const gpry_cand* __restrict__ c, int64_t n, const double* __restrict__ acq,
+                                    const double* __restrict__ y, const double* __restrict__ sig, gpry_cand* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t idx = c[i].idx;
+    gpry_cand r;
+    r.acq = acq[idx]; r.y = y[idx]; r.sigma = sig[idx]; r.idx = idx;
+    out[i] = r;
+}
+static unsigned long long acq_key_host(double a) {
+    unsigned long long b; memcpy(&b, &a, 8);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// Option "prune_one_select", for the FIRST round after stage A alone (nothing outside the selected set is contracted): the
+// nsel selected records are now exact, every other candidate that counts still holds its bound, and the largest of those
+// bound keys is `below` (cnt[1] of the select).  If the Kp-th best exact record lies strictly above it, the Kp best records
+// of the mixed array are the Kp best of these nsel, and the value behind them is the larger of record Kp + 1 and that bound:
+// what sweep_topk_plain would select from all M values.  *done = 0 in every other case (a tie with the outside bound, too few
+// records, a NaN, a record that was not contracted): the caller goes on as without the option.
+static int prune_first_round_answer(gpry_ctx* ctx, int64_t Kp, int64_t n_exclude, int64_t nsel, unsigned long long below,
+                                    gpry_cand* top, int64_t* n_out, double* bound, int* done) {
+    *done = 0;
+    const int64_t n_valid = ctx->sw_M - (n_exclude > 0 ? n_exclude : 0);
+    if (Kp <= 0 || Kp > nsel || Kp > n_valid) return 0;
+    gpry_cand* rec = nullptr;
+    {
+        StageScope s(ctx, "sweep_prune_select");
+        GPRY_TRY(ensure_pinned(ctx, (int64_t)sizeof(gpry_cand) * nsel));
+        rec = static_cast<gpry_cand*>(ctx->hpin);
+        hipLaunchKernelGGL(cand_refresh_kernel, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dcand, nsel,
+                           ctx->dacq_all, ctx->dy_all, ctx->dsig_all, static_cast<gpry_cand*>(ctx->hpin_dev));
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (int64_t i = 0; i < nsel; i++) if (rec[i].acq != rec[i].acq) return 0;
+    std::sort(rec, rec + nsel, cand_before);
+    for (int64_t i = 0; i < Kp; i++) if (rec[i].sigma == PRUNED_SIGMA) return 0;
+    if (!(acq_key_host(rec[Kp - 1].acq) > below)) return 0;
+    for (int64_t i = 0; i < Kp; i++) top[i] = rec[i];
+    *n_out = Kp;
+    unsigned long long kb = below;
+    if (nsel > Kp && acq_key_host(rec[Kp].acq) > kb) kb = acq_key_host(rec[Kp].acq);
+    *bound = kb ? key_to_acq(kb) : -INFINITY;
+    *done = 1;
+    return 0;
+}
+
 // The survivors of the contracted set (the n_gidx candidates in ctx->dgidx): tau = the Kp-th best exact acquisition among
 // them outside the exclusions -- a lower bound of the full sweep's Kp-th value -- and *n_surv = the number of candidates whose
 // bound is not below tau; every other candidate is out.  *n_surv = -1 if fewer than Kp of them count.
@@ -296,6 +462,7 @@ static int prune_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t
                       gpry_cand* top, int64_t* n_out, double* bound) {
     const int64_t M = ctx->sw_M;
     ctx->prune.last_K = Kp;
+    bool first_round = ctx->opt_prune_one_select && ctx->prune.rounds == 0 && ctx->prune.n_eval == 0;
     for (;;) {
         if (ctx->prune.n_eval > 0) {
             GPRY_TRY(sweep_topk_plain(ctx, Kp, exclude, n_exclude, top, n_out, bound));
@@ -342,6 +509,12 @@ static int prune_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t
         ctx->prune.n_gidx = n;
         ctx->prune.rounds++;
         ctx->prune.evaluated_total += n;
+        if (first_round) {
+            first_round = false;
+            int done = 0;
+            GPRY_TRY(prune_first_round_answer(ctx, Kp, n_exclude, nsel, cnt[1], top, n_out, bound, &done));
+            if (done) return 0;
+        }
     }
 }
 

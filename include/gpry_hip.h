@@ -142,6 +142,16 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *                             adds a rigorous slack for them and for rounding, and computes y exactly only for the candidates it
  *                             contracts (same records and, after gpry_sweep_fetch, the same arrays bit for bit).  0: y exactly for
  *                             every candidate in the mean pass
+ *     "sweep_small_map" 0/1   1 (default): a one-pass contraction of at most 512 tiles of 128 x 128 (the compact batches of a pruned
+ *                             sweep) launches one workgroup per tile, longest row tile first, consecutive candidate tiles on
+ *                             different XCDs; 0: the super-tile map of the large launches (the comparator).  A row tile walks k in
+ *                             the same direction under both maps: same bits
+ *     "select_fused" 0/1      1 (default): the 12 passes of the device radix select of gpry_sweep_topk each derive the digit of the
+ *                             pass before them from its own counters (no scan launches; per-wave aggregation of the histogram, one
+ *                             atomic per workgroup in the emit); 0: a histogram and a scan launch per pass (the comparator; same set)
+ *     "prune_one_select" 0/1  1 (default): the first contraction round of a pruned sweep answers from its own records when the Kp-th
+ *                             exact value lies strictly above every bound outside them (no second select over the pool); 0: always
+ *                             the select over all candidates (the comparator; same records and bound)
  *     "chol_stacked"          up to this padded training-set size (default 2048; at most 3584) the inverse factor V = L^-1 comes
  *                             out of the launches of the Cholesky factorisation itself (the identity appended to the matrix as
  *                             extra rows); 0: always the recursive inverse behind the factorisation.  Same L; V, and what is
