@@ -85,6 +85,8 @@ SIGNATURES = {
                                 + [C.c_int, C.c_int, _vp, _vp]),
     "gpry_maximize_mean": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double,
                                      C.c_double, C.c_double] + [_vp] * 12 + [_P(C.c_double)]),
+    "gpry_maximize_acq": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int,
+                                    C.c_int, C.c_double, C.c_double, C.c_double] + [_vp] * 14 + [_P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -645,6 +647,47 @@ class Device:
                                                  _ptr(tr.get("U_tr")), _ptr(tr.get("y_tr")), _ptr(tr.get("G_tr")),
                                                  _ptr(tr.get("nhalv_tr")), _ptr(tr.get("reset_tr")), C.byref(ms)),
                     "gpry_maximize_mean")
+        out.update(tr)
+        out["device_ms"] = ms.value
+        return out
+
+    # -- maximisation of the LogExp acquisition (gpry_amd/maximize.py: maximize_acq drives this one) ----
+    def maximize_acq(self, lo, hi, X0, fixed, H0, zeta, baseline, sigma_n, max_iter, max_halvings, gtol, ftol,
+                     minus_inf_value, hooks=False):
+        """Projected BFGS ascents of the LogExp acquisition a = 2 zeta (y - baseline) + log sqrt(sigma^2 - sigma_n^2)
+        inside the box from the rows of ``X0``, value and exact gradient evaluated inside the kernel
+        (gpry_maximize_acq); ``fixed`` and ``H0`` as in ``maximize_mean``.  A dict with ``X`` (nstart, d), ``a``, ``y``,
+        ``sigma`` (at X), ``G`` (the unit-cube gradient of a at X), ``iters``, ``ncalls``, ``ngrad``, ``status``
+        (``MAX_STATUS``) and ``device_ms``; with ``hooks`` also the traces ``U_tr`` (nstart, max_iter + 1, d), ``a_tr``,
+        ``G_tr``, ``nhalv_tr`` and ``reset_tr`` (nstart, max_iter), unused slots NaN / -1."""
+        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
+        X0 = _f64(X0)
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise ValueError(f"expected starts of shape (nstart, {self.d}), got {X0.shape}")
+        n, d = X0.shape
+        H0 = _f64(H0, (d, d))
+        fixed = np.ascontiguousarray(fixed)
+        if fixed.shape != (d,) or fixed.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise ValueError(f"expected a boolean mask of shape ({d},), got {fixed.dtype} {fixed.shape}")
+        fixed = fixed.astype(np.uint8)
+        max_iter, max_halvings = int(max_iter), int(max_halvings)
+        out = dict(X=np.empty((n, d)), a=np.empty(n), y=np.empty(n), sigma=np.empty(n), G=np.empty((n, d)),
+                   iters=np.zeros(n, np.int32), ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64),
+                   status=np.zeros(n, np.int32))
+        tr = {}
+        if hooks:
+            m = max(max_iter, 0)
+            tr = dict(U_tr=np.empty((n, m + 1, d)), a_tr=np.empty((n, m + 1)), G_tr=np.empty((n, m + 1, d)),
+                      nhalv_tr=np.empty((n, m), np.int32), reset_tr=np.empty((n, m), np.int32))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_maximize_acq(self._h, _ptr(lo), _ptr(hi), _ptr(X0), n, _ptr(fixed), _ptr(H0), float(zeta),
+                                                float(baseline), float(sigma_n), max_iter, max_halvings, float(gtol),
+                                                float(ftol), float(minus_inf_value), _ptr(out["X"]), _ptr(out["a"]),
+                                                _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["G"]), _ptr(out["iters"]),
+                                                _ptr(out["ncalls"]), _ptr(out["ngrad"]), _ptr(out["status"]),
+                                                _ptr(tr.get("U_tr")), _ptr(tr.get("a_tr")), _ptr(tr.get("G_tr")),
+                                                _ptr(tr.get("nhalv_tr")), _ptr(tr.get("reset_tr")), C.byref(ms)),
+                    "gpry_maximize_acq")
         out.update(tr)
         out["device_ms"] = ms.value
         return out

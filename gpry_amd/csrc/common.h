@@ -22,7 +22,7 @@ struct StageTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
-// post-processing of a sweep's partial sums (sweep.hip: finish_y, finish_sd, logexp_value)
+// post-processing of a sweep's partial sums (sweep.hip: finish_y; acq_math.h: finish_sd, logexp_value)
 struct FinishParams {
     double C, y_mean, y_std, clip_hi, zeta, baseline, sigma_n;
     int want_std, want_acq;

@@ -1,24 +1,9 @@
 // The candidate sweep: posterior mean, sigma and LogExp acquisition of a pool of candidates in chunks (gpry_sweep_logexp,
 // gpry_sweep_logexp_given, the panel paths of gpry_predict), stage A and the compact batches of a pruned sweep.
 #include "sweep.h"
+#include "acq_math.h"
 #include <algorithm>
 
-// LogExp.f on one (mean, std) pair (gpry/acquisition_functions.py:1068-1074): log sqrt(0) = -inf and a
-// mean of -inf give -inf, as numpy does under the errstate the reference sets (gp_acquisition.py:1099)
-__device__ __forceinline__ double logexp_value(double y, double sd, double zeta, double baseline, double sigma_n) {
-    // std**2 - noise**2 as numpy evaluates it: both squares rounded, then the difference.  Contracted
-    // into one FMA the cancellation just above sigma_n moved the result by 1e-9 relative (found by the
-    // reference's own F5 edge vectors).  -ffp-contract=fast fuses in the backend whatever the source
-    // pragmas say, so the products are pinned behind empty asm statements.
-    double s2 = sd * sd, n2 = sigma_n * sigma_n;
-    asm volatile("" : "+v"(s2));
-    asm volatile("" : "+v"(n2));
-    double v = s2 - n2;
-    if (v < 0.0) v = 0.0;
-    double lin = (2.0 * zeta) * (y - baseline);
-    asm volatile("" : "+v"(lin));
-    return lin + log(sqrt(v));
-}
 __global__ void logexp_kernel(const double* __restrict__ mu, const double* __restrict__ sd, int64_t n, double zeta,
                               double baseline, double sigma_n, double* __restrict__ acq) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -30,7 +15,8 @@ int launch_logexp(gpry_ctx* ctx, const double* mu, const double* sd, int64_t n, 
     return 0;
 }
 
-// THE FINISH, once: every finish kernel below takes y, sigma and the prior sigma from these three, so that a candidate gets
+// THE FINISH, once: every finish kernel below takes y, sigma and the prior sigma from finish_y below and finish_sd /
+// logexp_value of acq_math.h, so that a candidate gets
 // the same operations on the same values -- the same bits -- whichever kernel finishes it.  The exactness of the pruned sweep
 // rests on that (ub >= acq bit for bit, y of a contracted candidate = y of the full sweep).
 // The per-tile partials of column `col`, added in ascending tile order from 0.0
@@ -47,18 +33,6 @@ __device__ __forceinline__ double finish_y(double mu_, unsigned mk, const Finish
     if (mk) y = -INFINITY;
     return y;
 }
-// sigma from the sum of squares ss = |V k*|^2; predict_std has no trust-region gate: only the classifier bit zeroes it.
-// finish_sd(0.0, ..) is the prior sigma of the bound kernels: the finish sums non-negative per-tile terms (ss >= 0), so
-// var = C - ss <= C, and every later step (sqrt, * y_std, and in logexp_value the rounded square, - sigma_n^2, max, log) is
-// monotone under round-to-nearest -- the acquisition at the prior sigma is an upper bound of the exact one, bit for bit.
-__device__ __forceinline__ double finish_sd(double ss, unsigned mk, const FinishParams& fp) {
-    double var = fp.C - ss;
-    if (var < 0.0) var = 0.0;
-    double sd = sqrt(var) * fp.y_std;
-    if (mk & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
-    return sd;
-}
-
 // per candidate: reduce the partials, apply the reference's post-processing chain
 // (gpry/gpr.py:1180-1231) and LogExp.f (gpry/acquisition_functions.py:1068-1074)
 __global__ void sweep_finish_kernel(const double* __restrict__ mean_part, const double* __restrict__ ss_part,

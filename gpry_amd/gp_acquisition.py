@@ -87,7 +87,8 @@ class BatchOptimizer(GenericGPAcquisition):
     optimiser (scipy's L-BFGS-B with the analytic x-gradient) as the reference.  On the device: the optimiser
     runs of a proposal advance side by side, the posterior evaluations of a round in one ``gpry_predict_grad_batch``
     (``lockstep``; one ``gpry_predict_point`` per step with ``lockstep=False``, the reference's one-run-after-another
-    form), and each lie extends the factor by a border row (``gpry_append_rows``, O(N^2)) where the reference rebuilds
+    form; with ``acq_optimizer="device"``, opt-in and never what "auto" resolves to, the runs of a proposal are ascents
+    inside ONE kernel, ``gpry_maximize_acq``, see ``_optimize_on_device``), and each lie extends the factor by a border row (``gpry_append_rows``, O(N^2)) where the reference rebuilds
     and refactorises the model (gpry/gp_acquisition.py:488-491 -> gpry/gpr.py:1015-1017, O(N^3)).
 
     Parity of the side-by-side form with the one-after-another loop is to the tolerance of the posterior (1e-8 of the
@@ -116,10 +117,15 @@ class BatchOptimizer(GenericGPAcquisition):
             if acq_optimizer == "fmin_l_bfgs_b" and not self.acq_func.hasgradient:
                 raise ValueError("In order to use the 'fmin_l_bfgs_b' optimizer the acquisition function needs "
                                  "to be able to return gradients. Got %s" % self.acq_func)
-            if acq_optimizer not in ("fmin_l_bfgs_b", "sampling"):
-                raise ValueError("Supported internal optimizers are 'auto', 'lbfgs' or 'sampling', "
+            if acq_optimizer not in ("fmin_l_bfgs_b", "sampling", "device"):
+                raise ValueError("Supported internal optimizers are 'auto', 'lbfgs', 'sampling' or 'device', "
                                  "got {0}".format(acq_optimizer))
+            if acq_optimizer == "device" and type(self.acq_func) is not gpryacqfuncs.LogExp:
+                raise ValueError("acq_optimizer='device' maximises the LogExp acquisition function only (with one scalar "
+                                 "noise level), got %s" % self.acq_func)
         self.acq_optimizer = acq_optimizer
+        # acq_optimizer="device": the controls of the ascents (gpry_maximize_acq); provisional, nothing about them is tuned
+        self.device_controls = dict(max_iter=200, max_halvings=12, gtol=1e-6, ftol=0.0)
         self.n_restarts_optimizer = get_Xnumber(n_restarts_optimizer, "d", self.n_d, int, "n_restarts_optimizer")
         self.n_repeats_propose = n_repeats_propose
         self.mean_ = None
@@ -236,6 +242,46 @@ class BatchOptimizer(GenericGPAcquisition):
             Xo, Fo, _ = lockstep.minimize_lockstep(fg, proposal_X[todo], np.asarray(tbounds, dtype=float))
             proposal_X[todo], acq_X[todo] = Xo, Fo
 
+    def _optimize_on_device(self, gpr, n_runs, use_bounds, rng, proposal_X, acq_X, stats):
+        """The ``n_runs`` optimiser runs of one proposal as ONE device call (``acq_optimizer="device"``): the starting points
+        are drawn run by run by ``_starting_point`` (the generator is consumed as in the other paths), then every run that
+        is not settled already is a box-constrained BFGS ascent of the acquisition inside one kernel
+        (``gpry_maximize_acq``: value and exact gradient evaluated there, no host round trip per step), over ``use_bounds``
+        in raw coordinates.  Fills ``proposal_X`` / ``acq_X`` (= -a) as ``_optimize_side_by_side`` does.  Nothing here falls
+        back to another optimiser: an acquisition function, noise model or classifier without a device form raises."""
+        from gpry_amd.maximize import acq_h0, acq_parameters
+        from gpry_amd.mc import _push_model
+        self.proposer.update(gpr)
+        self.proposer.update_bounds(use_bounds)
+        px = self.preprocessing_X
+        zeta, sigma_n = acq_parameters(self.acq_func, gpr, gpr.d)
+        todo = []
+        for i in range(n_runs):
+            x0, settled = self._starting_point(gpr, i, use_bounds, rng)
+            proposal_X[i] = x0
+            if settled is None:
+                todo.append(i)
+            else:
+                acq_X[i] = settled
+        if not todo:
+            return
+        use_bounds = np.asarray(use_bounds, dtype=float)
+        lo, hi = np.ascontiguousarray(use_bounds[:, 0]), np.ascontiguousarray(use_bounds[:, 1])
+        X0 = px.inverse_transform(proposal_X[todo]) if px is not None else proposal_X[todo]
+        X0 = np.clip(X0, lo, hi)                # (the way through preprocessing_X and back may miss a wall by an ulp)
+        _push_model(gpr, 'BatchOptimizer(acq_optimizer="device")')
+        c = self.device_controls
+        out = gpr.device.maximize_acq(lo, hi, np.ascontiguousarray(X0), np.zeros(gpr.d, bool), acq_h0(gpr, None, lo, hi), zeta,
+                                      float(gpr.y_max), sigma_n, c["max_iter"], c["max_halvings"], c["gtol"], c["ftol"],
+                                      gpr.minus_inf_value)
+        gpr.n_eval += int(np.sum(out["ncalls"]))
+        proposal_X[todo] = px.transform(out["X"]) if px is not None else out["X"]
+        acq_X[todo] = -1 * out["a"]
+        stats["device_ms"] += out["device_ms"]
+        stats["device_status"] += np.bincount(out["status"], minlength=6)
+        stats["device_ncalls"] += int(np.sum(out["ncalls"]))
+        stats["device_ngrad"] += int(np.sum(out["ngrad"]))
+
     def multi_add(self, gpr, n_points=1, bounds=None, rng=None, force_resample=False):
         """``n_points`` proposals, each the best of ``n_restarts_optimizer`` optimiser runs on the model
         augmented by the previous proposals at their predicted means (gpry/gp_acquisition.py:391-497)."""
@@ -248,8 +294,12 @@ class BatchOptimizer(GenericGPAcquisition):
         n_runs = self.n_restarts_optimizer
         proposal_X, acq_X = np.empty((n_runs, gpr_.d)), np.empty((n_runs,))
         side_by_side = self._can_lockstep(gpr_)
+        on_device = isinstance(self.acq_optimizer, str) and self.acq_optimizer == "device"
+        dstats = {"device_ms": 0.0, "device_status": np.zeros(6, np.int64), "device_ncalls": 0, "device_ngrad": 0}
         for ipoint in range(n_points):
-            if side_by_side:
+            if on_device:
+                self._optimize_on_device(gpr_, n_runs, use_bounds, rng, proposal_X, acq_X, dstats)
+            elif side_by_side:
                 self._optimize_side_by_side(gpr_, n_runs, use_bounds, rng, proposal_X, acq_X)
             else:
                 for i in range(n_runs):
@@ -267,6 +317,11 @@ class BatchOptimizer(GenericGPAcquisition):
             X_opts[ipoint], y_lies[ipoint], acq_vals[ipoint] = X_opt[0], y_lie[0], -1 * acq_X[best]
         gpr.n_eval = gpr_.n_eval
         self.stats = {"border_updates": getattr(gpr_, "n_border_updates", 0), "side_by_side": bool(side_by_side)}
+        if on_device:
+            from gpry_amd.maximize import MAX_STATUS
+            self.stats.update(device_optimizer=True, device_ms=dstats["device_ms"], device_ncalls=dstats["device_ncalls"],
+                              device_ngrad=dstats["device_ngrad"],
+                              device_status={MAX_STATUS[k]: int(v) for k, v in enumerate(dstats["device_status"])})
         return X_opts, y_lies, acq_vals
 
     def _constrained_optimization(self, obj_func, initial_X, bounds):

@@ -1,4 +1,5 @@
-"""Maximum and profiles of the surrogate's posterior mean, with the ascents run on the device.
+"""Maximum and profiles of the surrogate's posterior mean, and the maximum of the LogExp acquisition, with the ascents
+run on the device.
 
 A run ends with a weighted sample of the surrogate (``gpry_amd/mc.py``); this module adds what a user asks for next: the
 surrogate's best-fit point (``maximize_gp``) and profile likelihoods over one or two parameters (``profile_gp``).  Whole
@@ -16,8 +17,17 @@ objective is ``gpr.predict(x[None])`` bit for bit (a gated point is -inf and is 
 the unclipped, ungated mean.  ``status`` is an index into ``MAX_STATUS``; the full statement is in include/gpry_hip.h
 (gpry_maximize_mean).
 
-No multi-GPU split of the starts, and no maximisation of the acquisition function (it needs sigma and its gradient,
-O(N^2) per point: a different kernel).
+``maximize_acq`` does the same for the LogExp acquisition a = 2 zeta (y - y_max) + log sqrt(sigma^2 - sigma_n^2), which
+needs sigma and its gradient, O(N^2) per point (``gpry_amd/csrc/maximize_acq.hip``), through
+
+``dev.maximize_acq(lo, hi, X0, fixed, H0, zeta, baseline, sigma_n, max_iter, max_halvings, gtol, ftol, minus_inf_value)
+    -> {"X", "a", "y", "sigma", "G", "iters", "ncalls", "ngrad", "status", "device_ms"}``
+
+with the same ascent and the exact gradient of a (gpry_maximize_acq in include/gpry_hip.h).
+``BatchOptimizer(acq_optimizer="device")`` of gpry_amd/gp_acquisition.py runs its restarts through it.
+
+No multi-GPU split of the starts; a start has a workgroup to itself (several starts do not share a pass over V); models
+above 4096 padded rows are refused by ``maximize_acq``.
 """
 from collections import namedtuple
 from time import time
@@ -36,6 +46,14 @@ MaxResult.__doc__ = """Output of ``maximize_gp``.  x, y: the best end point (the
 every start's end point, its y and its unit-cube gradient; status (index into ``MAX_STATUS``), iters, ncalls (evaluations
 of the mean), ngrad per start.  n_distinct: the end points with a finite y that lie further than 1e-6 apart in the unit
 cube, i.e. the local maxima found.  device_s / wall_s: time in the device call / in the whole function."""
+
+AcqMaxResult = namedtuple("AcqMaxResult", ["x", "acq", "y", "sigma", "X_all", "acq_all", "y_all", "sigma_all", "G_all",
+                                           "status", "iters", "ncalls", "ngrad", "n_distinct", "device_s", "wall_s"])
+AcqMaxResult.__doc__ = """Output of ``maximize_acq``.  x, acq, y, sigma: the best end point (the largest finite
+acquisition), its acquisition, mean and standard deviation.  X_all, acq_all, y_all, sigma_all, G_all: every start's end
+point, its values and the unit-cube gradient of the acquisition there; status (index into ``MAX_STATUS``), iters, ncalls
+(evaluations of the acquisition), ngrad per start.  n_distinct: the end points with a finite acquisition that lie further
+than 1e-6 apart in the unit cube.  device_s / wall_s: time in the device call / in the whole function."""
 
 ProfileResult = namedtuple("ProfileResult", ["grid", "y", "X", "status", "ncalls", "device_s"])
 ProfileResult.__doc__ = """Output of ``profile_gp``.  grid (G, len(params)): the fixed values; y (G,): the largest mean
@@ -229,3 +247,95 @@ def profile_gp(gpr, params, grid, bounds=None, nstarts=16, continuation=1, covma
             if yn[r] > y[i]:
                 X[i], y[i], st[i] = Xn[r], yn[r], sn[r]
     return ProfileResult(grid=grid, y=y, X=X, status=st, ncalls=ncalls, device_s=device_ms / 1e3)
+
+
+def acq_parameters(acq_func, gpr, d):
+    """``(zeta, sigma_n)`` of the acquisition function for the device ascent: a ``LogExp`` (None: ``LogExp(dimension=d)``)
+    with a scalar noise level.  Anything else raises a ValueError that says so."""
+    from collections.abc import Iterable
+    from gpry_amd.acquisition_functions import LogExp
+    if acq_func is None:
+        acq_func = LogExp(dimension=d)
+    if type(acq_func) is not LogExp:
+        raise ValueError(f"the device ascent of the acquisition function supports gpry_amd.acquisition_functions.LogExp "
+                         f"only, got {acq_func!r}")
+    sigma_n = acq_func._noise(gpr)[1]
+    if isinstance(sigma_n, Iterable) or not np.isfinite(sigma_n) or sigma_n < 0:
+        raise ValueError("the device ascent of the acquisition function needs one scalar noise level >= 0 (give LogExp a "
+                         f"sigma_n, or the regressor a scalar noise_level), got {sigma_n!r}")
+    zeta = float(acq_func.zeta)
+    if not np.isfinite(zeta):
+        raise ValueError(f"zeta = {zeta}")
+    return zeta, float(sigma_n)
+
+
+def acq_h0(gpr, covmat, lo, hi):
+    """The first inverse-Hessian guess of ``maximize_acq`` in the unit cube: ``covmat`` (raw coordinates) as in
+    ``maximize_gp``, else diag((l_k / (hi_k - lo_k))^2) with l the kernel's length scales in raw coordinates (the identity
+    for a regressor without a kernel_)."""
+    d, span = len(lo), hi - lo
+    if covmat is not None:
+        return _h0(covmat, np.empty((0, d)), np.empty(0), span)
+    kernel = getattr(gpr, "kernel_", None)
+    if kernel is None:
+        return np.eye(d)
+    ls = np.broadcast_to(np.exp(np.asarray(kernel.theta, dtype=float)[1:]), (d,)).copy()
+    px = getattr(gpr, "preprocessing_X", None)
+    if px is not None and hasattr(px, "transform_bounds"):
+        tb = np.asarray(px.transform_bounds(np.stack([lo, hi], axis=1)), dtype=float)
+        ls = ls * span / (tb[:, 1] - tb[:, 0])
+    return np.diag((ls / span) ** 2)
+
+
+def maximize_acq(gpr, acq_func=None, bounds=None, starts=None, nstarts=64, fixed=None, covmat=None, max_iter=200,
+                 max_halvings=12, gtol=1e-6, ftol=0.0, rng=None):
+    """The maximum of the LogExp acquisition a(x) = 2 zeta (y(x) - y_max) + log sqrt(sigma(x)^2 - sigma_n^2) inside
+    ``bounds`` (default ``gpr.trust_bounds``, else ``gpr.bounds``), from many local ascents on the device: an
+    ``AcqMaxResult``.
+
+    acq_func: a ``gpry_amd.acquisition_functions.LogExp`` (default ``LogExp(dimension=d)``); zeta is its own, sigma_n its
+    ``_noise(gpr)`` (one scalar noise level), the baseline ``gpr.y_max``.  Anything else raises a ValueError.  Starts:
+    the rows of ``starts``, or ``nstarts`` points uniform in the box drawn from ``rng`` (training rows are poor starts
+    here: sigma^2 - sigma_n^2 is about 0 on them and a is -inf).  fixed, max_iter, max_halvings, gtol, ftol: as in
+    ``maximize_gp``.  H0: ``covmat`` (raw coordinates), else diag((l_k / (hi_k - lo_k))^2) with l the kernel's length
+    scales in raw coordinates; provisional, like the other defaults: nothing about them has been tuned on a real run.
+
+    The device climbs with the exact gradient of a.  The reference's ``BaseLogExp.__call__`` returns
+    ``std_grad / (std - sigma_n) + 2 zeta mu_grad``, the derivative of log(sigma - sigma_n) and not of the
+    log sqrt(sigma^2 - sigma_n^2) that ``LogExp.f`` evaluates: its sigma term is off by the factor (sigma + sigma_n) / sigma;
+    a line search needs a gradient consistent with its value, so the device does not mirror that formula.
+    ``gpr.n_eval`` grows by ``ncalls``."""
+    t_start = time()
+    from gpry_amd.mc import _push_model
+    from gpry_amd.tools import get_random_generator
+    b, lo, hi = _setup(gpr, bounds)
+    d = len(lo)
+    _check_controls(max_iter, max_halvings, gtol, ftol)
+    mask = _mask(fixed, d)
+    zeta, sigma_n = acq_parameters(acq_func, gpr, d)
+    if starts is not None:
+        X0 = np.ascontiguousarray(np.atleast_2d(np.asarray(starts, dtype=float)))
+        if X0.ndim != 2 or X0.shape[1] != d or len(X0) == 0 or not np.all(np.isfinite(X0)):
+            raise ValueError(f"starts must be finite rows of dimension {d}, got shape {X0.shape}")
+        if not np.all((X0 >= lo) & (X0 <= hi)):
+            raise ValueError("every start must lie inside the bounds")
+    else:
+        if int(nstarts) != nstarts or int(nstarts) < 1:
+            raise ValueError(f"nstarts = {nstarts!r}: at least one start is needed")
+        X0 = np.ascontiguousarray(get_random_generator(rng).uniform(lo, hi, (int(nstarts), d)))
+    H0 = acq_h0(gpr, covmat, lo, hi)
+    _push_model(gpr, "maximize_acq")
+    out = gpr.device.maximize_acq(lo, hi, X0, mask, H0, zeta, float(gpr.y_max), sigma_n, int(max_iter), int(max_halvings),
+                                  float(gtol), float(ftol), gpr.minus_inf_value)
+    gpr.n_eval += int(np.sum(out["ncalls"]))
+    acq = out["a"]
+    fin = np.isfinite(acq)
+    if not fin.any():
+        raise ValueError("no start has a finite acquisition")
+    best = int(np.flatnonzero(fin)[np.argmax(acq[fin])])
+    return AcqMaxResult(x=out["X"][best].copy(), acq=float(acq[best]), y=float(out["y"][best]),
+                        sigma=float(out["sigma"][best]), X_all=out["X"], acq_all=acq, y_all=out["y"],
+                        sigma_all=out["sigma"], G_all=out["G"], status=out["status"], iters=out["iters"],
+                        ncalls=out["ncalls"], ngrad=out["ngrad"],
+                        n_distinct=n_distinct(out["X"], np.where(fin, acq, np.nan), lo, hi),
+                        device_s=out["device_ms"] / 1e3, wall_s=time() - t_start)

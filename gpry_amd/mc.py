@@ -13,7 +13,7 @@ import warnings
 
 import numpy as np
 
-from gpry_amd.maximize import maximize_gp, profile_gp  # noqa: F401  (beside mc_sample_from_gp: the best fit and profiles)
+from gpry_amd.maximize import maximize_acq, maximize_gp, profile_gp  # noqa: F401  (beside mc_sample_from_gp: the best fit and profiles)
 from gpry_amd.tools import generic_params_names, get_Xnumber
 
 # PolyChord's defaults (the Runner passes nlive = 50d)

@@ -462,6 +462,44 @@ int gpry_maximize_mean(gpry_ctx* ctx, const double* lo, const double* hi, const 
                        int* iters, int64_t* ncalls, int64_t* ngrad, int* status, double* U_tr, double* y_tr, double* G_tr,
                        int* nhalv_tr, int* reset_tr, double* device_ms);
 
+/* ---- Maximum of the LogExp acquisition (maximize_acq.hip; starts and H0 in gpry_amd/maximize.py: maximize_acq, and
+ * gpry_amd/gp_acquisition.py: BatchOptimizer(acq_optimizer="device")) ---------------------------------------------------
+ * gpry_maximize_acq: `nstart` local maximisations of a(x) = 2 zeta (y(x) - baseline) + log sqrt(sigma(x)^2 - sigma_n^2)
+ * inside the box [lo, hi], one workgroup each, from the rows of X0 (nstart x d).  The statement of the algorithm is that of
+ * gpry_maximize_mean, word for word -- free set, direction, Armijo search, the stops, the resets of H, the BFGS update, the
+ * rn(.) fences, the status codes, the layout of the traces -- with these differences:
+ *   - the objective is a(x) instead of y(x), and the gradient g is the exact gradient of a with respect to u;
+ *   - a start is always evaluated first (there is no y0 argument) and counted in ncalls.
+ * Objective, per point x (raw coordinates): y = gpry_predict of the point, bit for bit, clip and gates included.
+ * k*_j = C kappa(|x / l - X_j / l|), j < N.  u = V k* with V = L^-1 (row i over the columns 0 .. i; rows and columns >= N
+ * are not read), ss = sum u_i^2, both in a fixed order.  sigma = sqrt(max(C - ss, 0)) y_std, and 0 where the classifier of
+ * the device gates rejects the point.  a = LogExp.f(y, sigma) exactly as the sweep computes it (the same device function:
+ * rn(sigma sigma) - rn(sigma_n sigma_n), clamped at 0, log sqrt, + rn((2 zeta) (y - baseline))).  a counts as -inf unless
+ * y is finite, y > minus_inf_value and dv = rn(sigma sigma) - rn(sigma_n sigma_n) > 0 (the reference's mask,
+ * gpry/acquisition_functions.py:983-992): such a trial is never accepted, such a start ends with BAD_START (a_out -inf).
+ * Gradient, at a start and at an accepted trial: w = V^T u (= K^-1 k*), in a fixed order; with G_jk = d k(x, X_j) / d x_k
+ * in the kernel's coordinates (gpry_predict_grad), m = G^T alpha_ and v = G^T w (d sigma_^2 / dx = -2 v in transformed
+ * units), and s_k = (hi_k - lo_k) / x_span_k (x_span_k = 1 without an x-affine map):
+ *   g_k = s_k (rn(rn((2 zeta) y_std) m_k) + rn(rn(y_std y_std) (-v_k)) / dv).
+ * This is the gradient of the value the search tests, d/du [2 zeta y + (1/2) log(sigma^2 - sigma_n^2)].  It is NOT the
+ * reference's BaseLogExp gradient std_grad / (std - sigma_n) + 2 zeta mu_grad (gpry/acquisition_functions.py:993-1007),
+ * which is the derivative of log(sigma - sigma_n): its sigma term differs from the one above by the factor
+ * (sigma + sigma_n) / sigma (and carries y_std once more, gpry/gpr.py:1236-1266); an Armijo search needs the gradient of
+ * its own value.  A gradient with a component that is not finite: BAD_GRADIENT, as in gpry_maximize_mean.
+ * Outputs per start: X_out (nstart x d), a_out, y_out and sigma_out (of X_out), G_out (nstart x d; g at X_out, NaN after
+ * BAD_START), iters, ncalls (evaluations of a: passes over V), ngrad (gradients: second passes over V), status.  A start's
+ * outputs depend on its row alone, not on nstart, its position or the context.  Test hooks as in gpry_maximize_mean, a_tr
+ * in the place of y_tr.
+ * Refused (-1, with gpry_last_error) before anything runs: what gpry_maximize_mean refuses; sigma_n negative or not finite;
+ * zeta or baseline not finite; a model of more than 4096 padded rows (the kernel keeps k*, u and w of a point in LDS).
+ * Stops the resident predict kernel first.  device_ms (nullable): device time of the call, copies included. */
+int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, int64_t nstart,
+                      const unsigned char* fixed, const double* H0, double zeta, double baseline, double sigma_n,
+                      int max_iter, int max_halvings, double gtol, double ftol, double minus_inf_value, double* X_out,
+                      double* a_out, double* y_out, double* sigma_out, double* G_out, int* iters, int64_t* ncalls,
+                      int64_t* ngrad, int* status, double* U_tr, double* a_tr, double* G_tr, int* nhalv_tr, int* reset_tr,
+                      double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
