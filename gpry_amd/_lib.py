@@ -87,6 +87,7 @@ SIGNATURES = {
                                      C.c_double, C.c_double] + [_vp] * 12 + [_P(C.c_double)]),
     "gpry_maximize_acq": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                     C.c_int, C.c_double, C.c_double, C.c_double] + [_vp] * 14 + [_P(C.c_double)]),
+    "gpry_hessian_mean": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -689,6 +690,23 @@ class Device:
                                                 _ptr(tr.get("nhalv_tr")), _ptr(tr.get("reset_tr")), C.byref(ms)),
                     "gpry_maximize_acq")
         out.update(tr)
+        out["device_ms"] = ms.value
+        return out
+
+    # -- value, gradient and Hessian of the mean (gpry_amd/maximize.py: hessian_gp, laplace_gp drive this one) ----
+    def hessian_mean(self, X):
+        """Value, gradient and Hessian of the posterior mean at the rows of ``X`` (npts, d), raw coordinates and units of
+        y (gpry_hessian_mean): a dict with ``y`` (npts,; ``predict(x[None])`` bit for bit, a gated point is -inf), ``g``
+        (npts, d) and ``H`` (npts, d, d), both of the unclipped, ungated mean, H symmetric to the last bit, and
+        ``device_ms``.  A Matern-1/2 model is refused."""
+        X = _f64(X)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError(f"expected points of shape (npts, {self.d}), got {X.shape}")
+        n, d = X.shape
+        out = dict(y=np.empty(n), g=np.empty((n, d)), H=np.empty((n, d, d)))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_hessian_mean(self._h, _ptr(X), n, _ptr(out["y"]), _ptr(out["g"]), _ptr(out["H"]),
+                                                C.byref(ms)), "gpry_hessian_mean")
         out["device_ms"] = ms.value
         return out
 

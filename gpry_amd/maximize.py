@@ -26,9 +26,20 @@ needs sigma and its gradient, O(N^2) per point (``gpry_amd/csrc/maximize_acq.hip
 with the same ascent and the exact gradient of a (gpry_maximize_acq in include/gpry_hip.h).
 ``BatchOptimizer(acq_optimizer="device")`` of gpry_amd/gp_acquisition.py runs its restarts through it.
 
+``hessian_gp`` returns value, gradient and Hessian of the mean at a batch of points from one more kernel
+(``gpry_amd/csrc/hessian.hip``, the Hessian's bulk a weighted Gram on the FP64 matrix pipe), through
+
+``dev.hessian_mean(X) -> {"y": (npts,), "g": (npts, d), "H": (npts, d, d), "device_ms"}``
+
+(stand-in: tests/tools/hessian_numpy.py); ``laplace_gp`` makes the Gaussian approximation at a maximum from it (covariance
+and Laplace evidence), and ``covmat="laplace"`` takes the first inverse-Hessian guess of ``maximize_gp`` / ``profile_gp``
+and the first proposal of the chain samplers (``mc_sample_from_gp``) from the curvature instead of the scatter of the
+training set.  A Matern-1/2 model has no Hessian at its training rows and is refused by all of these.
+
 No multi-GPU split of the starts; a start has a workgroup to itself (several starts do not share a pass over V); models
 above 4096 padded rows are refused by ``maximize_acq``.
 """
+import warnings
 from collections import namedtuple
 from time import time
 
@@ -61,6 +72,14 @@ with them fixed (-inf: no start of the row was usable); X (G, d): where; status 
 it (-1: none); ncalls: evaluations of the mean, all passes (``gpr.n_eval`` grows by it); device_s: time in the device calls."""
 
 
+LaplaceResult = namedtuple("LaplaceResult", ["x", "y", "g", "H", "free", "cov", "logZ", "negdef", "device_s", "wall_s"])
+LaplaceResult.__doc__ = """Output of ``laplace_gp``.  x: the point; y, g (d,), H (d, d): ``gpr.predict(x[None])`` and the
+gradient and Hessian of the unclipped, ungated mean there, raw coordinates.  free (d,) bool: the coordinates the
+approximation is over (not fixed, not held by a wall of the box); negdef: -H over the free set has a Cholesky factor;
+cov (k, k): its inverse, None when not negdef; logZ: the Laplace evidence under the uniform prior over the box, NaN
+unless every coordinate is free and negdef holds.  device_s / wall_s: time in the device calls / in the whole function."""
+
+
 def _setup(gpr, bounds):
     from gpry_amd.mc import _bounds
     b = _bounds(gpr, bounds)
@@ -78,8 +97,53 @@ def _usable(X, y, lo, hi, minus_inf_value):
     return X[order], y[order]
 
 
-def _h0(covmat, Xt, yt, span):
+def _refuse_matern12(gpr, d, who):
+    """A Matern-1/2 mean has a kink at every training row: no Hessian.  (The stand-ins of the tests carry a ``kernel_id``.)"""
+    kernel = getattr(gpr, "kernel_", None)
+    kid = kernel.device_spec(d)[0] if hasattr(kernel, "device_spec") else getattr(gpr, "kernel_id", None)
+    if kid == 1:
+        raise ValueError(f"{who}: the mean of a Matern-1/2 model is not differentiable at the training rows; it has no "
+                         "Hessian")
+
+
+def _inv_spd(A):
+    """The inverse of a symmetric positive definite matrix and its log-determinant through its Cholesky factor, or None
+    when it has none."""
+    if not np.all(np.isfinite(A)):
+        return None
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        return None
+    Li = np.linalg.solve(L, np.eye(len(A)))
+    return Li.T @ Li, 2.0 * float(np.sum(np.log(np.diag(L))))
+
+
+def _laplace_h0(gpr, Xt, span):
+    """inv(-H_uu) at the best usable training point, unit-cube coordinates; None (and a warning) where -H_uu is not
+    positive definite."""
+    _refuse_matern12(gpr, len(span), 'covmat="laplace"')
+    inv = None
+    if len(Xt):
+        H = hessian_gp(gpr, Xt[:1])[2][0]
+        inv = _inv_spd(-H * np.outer(span, span))
+    if inv is None:
+        warnings.warn('covmat="laplace": minus the Hessian of the mean at the best training point is not positive '
+                      "definite; the weighted covariance of the training set is used instead")
+        return None
+    return np.ascontiguousarray(0.5 * (inv[0] + inv[0].T))
+
+
+def _h0(covmat, Xt, yt, span, gpr=None):
     d = len(span)
+    if isinstance(covmat, str):
+        if covmat != "laplace" or gpr is None:
+            raise ValueError(f"covmat = {covmat!r}: a ({d}, {d}) matrix or None is needed"
+                             + ("" if gpr is None else ', or "laplace"'))
+        H0 = _laplace_h0(gpr, Xt, span)
+        if H0 is not None:
+            return H0
+        covmat = None
     if covmat is not None:
         C = np.asarray(covmat, dtype=float)
         if C.shape != (d, d) or not np.all(np.isfinite(C)):
@@ -140,7 +204,9 @@ def maximize_gp(gpr, bounds=None, nstarts=64, starts=None, fixed=None, covmat=No
     Starts: the ``nstarts`` best usable training points (finite y above ``gpr.minus_inf_value``, inside the box), or the
     rows of ``starts`` when given.  fixed: indices (or a boolean mask) of the coordinates that keep their start values.
     H0, the first inverse-Hessian guess: ``covmat`` (raw coordinates) or the exp(y - y_max)-weighted covariance of the
-    training set, in the unit cube.  gtol: bound on the unit-cube gradient over the free coordinates; ftol: stop when a
+    training set, in the unit cube; ``covmat="laplace"``: the inverse of minus the Hessian of the mean at the best usable
+    training point (``hessian_gp``; where that is not positive definite: a warning, and the weighted covariance).
+    gtol: bound on the unit-cube gradient over the free coordinates; ftol: stop when a
     step gains no more than ftol max(1, |y|) (0: off; the ascent then ends on gtol or when no step improves y any more,
     status STALLED).  ``seed`` is accepted for symmetry with the samplers; the algorithm has no randomness.  The
     defaults are provisional: nothing about them has been tuned on a real run yet.  ``gpr.n_eval`` grows by ``ncalls``,
@@ -164,7 +230,7 @@ def maximize_gp(gpr, bounds=None, nstarts=64, starts=None, fixed=None, covmat=No
         if len(Xt) == 0:
             raise ValueError("no training point with a finite y inside the bounds to start from")
         X0 = np.ascontiguousarray(Xt[:int(nstarts)])
-    H0 = _h0(covmat, Xt, yt, hi - lo)
+    H0 = _h0(covmat, Xt, yt, hi - lo, gpr)
     _push_model(gpr, "maximize")
     out = gpr.device.maximize_mean(lo, hi, X0, np.full(len(X0), np.nan), mask, H0, int(max_iter), int(max_halvings),
                                    float(gtol), float(ftol), gpr.minus_inf_value)
@@ -212,7 +278,7 @@ def profile_gp(gpr, params, grid, bounds=None, nstarts=16, continuation=1, covma
     Xt, yt = _usable(gpr.X_train, gpr.y_train, lo, hi, gpr.minus_inf_value)
     if len(Xt) == 0:
         raise ValueError("no training point with a finite y inside the bounds to start from")
-    H0 = _h0(covmat, Xt, yt, hi - lo)
+    H0 = _h0(covmat, Xt, yt, hi - lo, gpr)
     _push_model(gpr, "maximize")
     ctl = (int(max_iter), int(max_halvings), float(gtol), float(ftol), gpr.minus_inf_value)
     device_ms, ncalls = 0.0, 0
@@ -247,6 +313,85 @@ def profile_gp(gpr, params, grid, bounds=None, nstarts=16, continuation=1, covma
             if yn[r] > y[i]:
                 X[i], y[i], st[i] = Xn[r], yn[r], sn[r]
     return ProfileResult(grid=grid, y=y, X=X, status=st, ncalls=ncalls, device_s=device_ms / 1e3)
+
+
+def _hessian(gpr, X, who):
+    """``dev.hessian_mean`` of the rows of X with the model pushed first and the evaluations counted."""
+    from gpry_amd.mc import _push_model
+    X = np.ascontiguousarray(np.atleast_2d(np.asarray(X, dtype=float)))
+    d = len(np.asarray(gpr.bounds))
+    if X.ndim != 2 or X.shape[1] != d or len(X) == 0 or not np.all(np.isfinite(X)):
+        raise ValueError(f"{who}: finite rows of dimension {d} are needed, got shape {X.shape}")
+    _refuse_matern12(gpr, d, who)
+    _push_model(gpr, "hessian")
+    out = gpr.device.hessian_mean(X)
+    gpr.n_eval += len(X)
+    return out
+
+
+def hessian_gp(gpr, X):
+    """``(y, g, H)`` of the surrogate's posterior mean at the rows of ``X`` (npts, d), raw coordinates, in one device
+    call: y (npts,) is ``gpr.predict(x[None])`` bit for bit (clip and gates included, a gated point is -inf); g (npts, d)
+    and H (npts, d, d) are the gradient and the Hessian of the unclipped, ungated mean, H symmetric to the last bit.
+    A Matern-1/2 model raises a ValueError.  ``gpr.n_eval`` grows by npts."""
+    out = _hessian(gpr, X, "hessian_gp")
+    return out["y"], out["g"], out["H"]
+
+
+def laplace_gp(gpr, x=None, bounds=None, fixed=None, **maximize_kwargs):
+    """The Gaussian approximation of exp(mean) at ``x`` inside ``bounds`` (default ``gpr.trust_bounds``, else
+    ``gpr.bounds``): a ``LaplaceResult``.
+
+    x: the point; None: the best point of ``maximize_gp(gpr, bounds=bounds, fixed=fixed, **maximize_kwargs)``.  free:
+    every coordinate except the ``fixed`` ones and those on a wall of the box with the gradient pointing outward
+    (x_k == lo_k and g_k <= 0, or x_k == hi_k and g_k >= 0: the ascent's own rule for a coordinate that does not move).
+    With H_ff the Hessian over the k free coordinates: negdef says whether -H_ff has a Cholesky factor, cov = (-H_ff)^-1
+    (None when it has none), and
+    logZ = y + (k / 2) log 2 pi - (1 / 2) log det(-H_ff) - sum_free log(hi - lo), the evidence under the uniform prior over
+    the box (the nested sampler's convention), NaN unless all d coordinates are free and negdef holds.  A Matern-1/2
+    model raises a ValueError."""
+    t_start = time()
+    b, lo, hi = _setup(gpr, bounds)
+    d = len(lo)
+    mask = _mask(fixed, d)
+    _refuse_matern12(gpr, d, "laplace_gp")
+    device_s = 0.0
+    if x is None:
+        r = maximize_gp(gpr, bounds=b, fixed=fixed, **maximize_kwargs)
+        x, device_s = r.x, r.device_s
+    else:
+        if maximize_kwargs:
+            raise TypeError(f"{sorted(maximize_kwargs)} are arguments of the maximisation, which a given x does not run")
+        x = np.array(x, dtype=float).ravel()
+        if x.shape != (d,) or not np.all(np.isfinite(x)) or not np.all((x >= lo) & (x <= hi)):
+            raise ValueError(f"x must be a finite point of dimension {d} inside the bounds, got {x!r}")
+    out = _hessian(gpr, x[None], "laplace_gp")
+    device_s += out["device_ms"] / 1e3
+    y, g, H = float(out["y"][0]), out["g"][0], out["H"][0]
+    free = ~mask & ~((x == lo) & (g <= 0)) & ~((x == hi) & (g >= 0))
+    k = int(free.sum())
+    inv = _inv_spd(-H[np.ix_(free, free)]) if k else (np.zeros((0, 0)), 0.0)
+    negdef = inv is not None
+    logZ = np.nan
+    if negdef and k == d:
+        logZ = y + 0.5 * k * np.log(2.0 * np.pi) - 0.5 * inv[1] - float(np.sum(np.log(hi - lo)))
+    return LaplaceResult(x=x, y=y, g=g, H=H, free=free, cov=inv[0] if negdef else None, logZ=float(logZ), negdef=negdef,
+                         device_s=device_s, wall_s=time() - t_start)
+
+
+def laplace_covmat(gpr, bounds, covmat="laplace"):
+    """The first proposal covariance of a chain sampler for ``covmat="laplace"``: ``laplace_gp``'s cov at the maximum
+    of the mean, or None (and a warning: the sampler then starts from the weighted covariance of the training set)
+    unless every coordinate is free there and negdef holds.  Any other string raises a ValueError."""
+    if covmat != "laplace":
+        raise ValueError(f'covmat = {covmat!r}: a matrix, None or "laplace" is needed')
+    r = laplace_gp(gpr, bounds=bounds)
+    if r.negdef and r.free.all():
+        return r.cov
+    warnings.warn('covmat="laplace": the maximum of the mean ' +
+                  ("lies on a wall of the box" if not r.free.all() else "has a Hessian that is not negative definite") +
+                  "; the weighted covariance of the training set is used instead")
+    return None
 
 
 def acq_parameters(acq_func, gpr, d):

@@ -13,7 +13,8 @@ import warnings
 
 import numpy as np
 
-from gpry_amd.maximize import maximize_acq, maximize_gp, profile_gp  # noqa: F401  (beside mc_sample_from_gp: the best fit and profiles)
+from gpry_amd.maximize import (hessian_gp, laplace_covmat, laplace_gp, maximize_acq, maximize_gp,  # noqa: F401
+                               profile_gp)  # (beside mc_sample_from_gp: the best fit, its curvature and profiles)
 from gpry_amd.tools import generic_params_names, get_Xnumber
 
 # PolyChord's defaults (the Runner passes nlive = 50d)
@@ -102,6 +103,13 @@ def tempered_settings(d, sampler_options=None):
     return _chain_settings(d, sampler_options, TEMPERED_KEYS, "tempered")
 
 
+def _string_covmat(gpr, b, s):
+    """``covmat="laplace"`` among a chain sampler's settings: the covariance of the Gaussian approximation at the maximum
+    of the mean in its place (``maximize.laplace_covmat``; None where that has none).  Other strings are refused."""
+    if isinstance(s.get("covmat"), str):
+        s["covmat"] = laplace_covmat(gpr, b, s["covmat"])
+
+
 def _bounds(gpr, bounds):
     if bounds is None:
         bounds = gpr.trust_bounds if getattr(gpr, "trust_bounds", None) is not None else gpr.bounds
@@ -140,7 +148,8 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     nlive, num_repeats, precision_criterion, nprior, max_ncalls; PolyChord's defaults 25d, 5d, 0.001, nlive; and
     clustering, default False: a whitening matrix per cluster of the live set; phantom_thin, default None: an int t
     keeps every t-th interior state of the chains as a weighted phantom row, see ``run_nested``) or
-    ``"mcmc"`` (options Rminus1_stop, temperature, covmat, max_samples -> max_ncalls, and run_mcmc's nchains,
+    ``"mcmc"`` (options Rminus1_stop, temperature, covmat (a matrix, or ``"laplace"``: the inverse of minus the Hessian
+    of the mean at its maximum, ``laplace_gp``, for all three chain samplers), max_samples -> max_ncalls, and run_mcmc's nchains,
     learn_every, learn_batches, batch_steps, max_batches, thin, skip, reset_temperature) or ``"hmc"`` (run_hmc's
     arguments: those of "mcmc", counted in trajectories, and eps, accept_target, and reflect, default False: with
     ``{"reflect": True}`` the trajectories reflect at the walls of the box instead of being rejected there, at most
@@ -169,6 +178,7 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     elif sampler == "hmc":
         from gpry_amd.hmc import DEFAULT_NCHAINS, run_hmc
         s = hmc_settings(d, sampler_options)
+        _string_covmat(gpr, b, s)
         nchains = s.pop("nchains", DEFAULT_NCHAINS)
         _push_model(gpr, sampler)
         res = run_hmc(gpr.device, b, seed, nchains, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value, **s)
@@ -176,6 +186,7 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     elif sampler == "tempered":
         from gpry_amd.tempering import DEFAULT_NLADDERS, run_tempered
         s = tempered_settings(d, sampler_options)
+        _string_covmat(gpr, b, s)
         nladders = s.pop("nladders", DEFAULT_NLADDERS)
         _push_model(gpr, sampler)
         res = run_tempered(gpr.device, b, seed, nladders, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value,
@@ -183,6 +194,7 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
     else:
         from gpry_amd.mcmc import DEFAULT_NCHAINS, run_mcmc
         s = mcmc_settings(d, sampler_options)
+        _string_covmat(gpr, b, s)
         nchains = s.pop("nchains", DEFAULT_NCHAINS)
         _push_model(gpr, sampler)
         res = run_mcmc(gpr.device, b, seed, nchains, gpr.X_train, gpr.y_train, minus_inf_value=gpr.minus_inf_value, **s)

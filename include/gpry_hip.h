@@ -500,6 +500,27 @@ int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const d
                       int64_t* ngrad, int* status, double* U_tr, double* a_tr, double* G_tr, int* nhalv_tr, int* reset_tr,
                       double* device_ms);
 
+/* ---- Value, gradient and Hessian of the posterior mean at a batch of points (hessian.hip; the Gaussian approximation,
+ * the Laplace evidence and covmat="laplace" in gpry_amd/maximize.py: hessian_gp, laplace_gp) ------------------------------
+ * The reference stops at first derivatives (gpry/gpr.py:1236-1266 with gpry/kernels.py:257-278 RBF, :326-432 Matern).
+ * gpry_hessian_mean: X (npts x d, raw coordinates), one workgroup per point, one launch.  Outputs in raw coordinates and
+ * units of y:
+ *   y_out (npts)          gpry_predict of the point, bit for bit, clip and gates included (a gated point is -inf);
+ *   g_out (npts x d)      the gradient of the unclipped, ungated mean: gpry_predict_grad's mean_grad times
+ *                         y_std / x_span_k (x_span_k = 1 without an x-affine map);
+ *   H_out (npts x d x d)  the Hessian of the same mean, row-major, symmetric to the last bit (the lower triangle is
+ *                         computed, the upper one copied); finite for a gated point too.
+ * With diff_j = x / l - X_j / l, r = |diff_j|, w(r) the radial factor of the gradient (-exp(-r^2/2) RBF, -3 exp(-sqrt3 r)
+ * Matern 3/2, -(5/3) (1 + sqrt5 r) exp(-sqrt5 r) Matern 5/2) and q(r) = w'(r) / r (exp(-r^2/2); 3 sqrt3 exp(-sqrt3 r) / r,
+ * 0 at r = 0; (25/3) exp(-sqrt5 r)):  S_ab = sum_j alpha_j q_j diff_ja diff_jb,  T = sum_j alpha_j w_j,
+ *   H_ab = y_std C (S_ab + T delta_ab) / (l_a l_b x_span_a x_span_b).
+ * The bits of y, g and H depend on the model and the point alone, not on npts, the point's position or the context.
+ * Refused (-1, with gpry_last_error) before anything runs: a NULL pointer; npts < 1 or > 2^31 - 1; no model; d > 32; a
+ * Matern-1/2 model (its mean is not differentiable at the training rows); a coordinate that is not finite.  Stops the
+ * resident predict kernel first.  device_ms (nullable): device time of the call, copies included. */
+int gpry_hessian_mean(gpry_ctx* ctx, const double* X, int64_t npts, double* y_out, double* g_out, double* H_out,
+                      double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
