@@ -88,6 +88,9 @@ SIGNATURES = {
     "gpry_maximize_acq": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                     C.c_int, C.c_double, C.c_double, C.c_double] + [_vp] * 14 + [_P(C.c_double)]),
     "gpry_hessian_mean": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_predict_cov": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_sample_joint": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp, _vp,
+                                    _P(C.c_int), _P(C.c_double), _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -708,6 +711,48 @@ class Device:
         self._check(self._lib.gpry_hessian_mean(self._h, _ptr(X), n, _ptr(out["y"]), _ptr(out["g"]), _ptr(out["H"]),
                                                 C.byref(ms)), "gpry_hessian_mean")
         out["device_ms"] = ms.value
+        return out
+
+    # -- joint posterior covariance and joint draws (gpry_amd/gpr.py: predict(return_cov=True), sample_y; mc.py) ----
+    def _joint_args(self, X, mask):
+        X = _f64(X)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError(f"expected points of shape (m, {self.d}), got {X.shape}")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (X.shape[0],):
+                raise ValueError(f"expected a mask of shape ({X.shape[0]},), got {mask.shape}")
+        return X, mask
+
+    def predict_cov(self, X, mask=None):
+        """Finalised mean and joint posterior covariance at the rows of ``X`` (m <= 4096, raw coordinates; units of y and
+        y^2; gpry_predict_cov): a dict with ``mean`` (m,), ``cov`` (m, m; symmetric to the last bit, the diagonal not
+        clamped, zero rows and columns for classifier-rejected points) and ``device_ms``."""
+        X, mask = self._joint_args(X, mask)
+        m = X.shape[0]
+        out = dict(mean=np.empty(m), cov=np.empty((m, m)))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_predict_cov(self._h, _ptr(X), m, _ptr(mask), _ptr(out["mean"]), _ptr(out["cov"]),
+                                               C.byref(ms)), "gpry_predict_cov")
+        out["device_ms"] = ms.value
+        return out
+
+    def sample_joint(self, X, S, seed, jitter=None, mask=None, want_Z=False, want_Lc=False):
+        """``S`` joint draws of the surrogate at the rows of ``X`` (gpry_sample_joint): a dict with ``mean`` (m,; the
+        finalised mean), ``Y`` (S, m; centred on the unclipped, ungated mean, -inf in classifier-rejected columns), ``Z``
+        and ``Lc`` (the variates and the Cholesky factor, or None), ``jitter_used`` and ``device_ms``.  ``jitter``: the
+        first rung of the ladder in units of C y_std^2 (None: 1e-10)."""
+        X, mask = self._joint_args(X, mask)
+        m, S = X.shape[0], int(S)
+        ok = 1 <= S <= 65536 and m >= 1           # (the library refuses; no arrays are made for a request it will refuse)
+        out = dict(mean=np.empty(m), Y=np.empty((S, m) if ok else (0, m)),
+                   Z=np.empty((S, m)) if want_Z and ok else None, Lc=np.empty((m, m)) if want_Lc and ok else None)
+        ms, eps, info = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gpry_sample_joint(self._h, _ptr(X), m, _ptr(mask), S, int(seed) & (2 ** 64 - 1),
+                                                -1.0 if jitter is None else float(jitter), _ptr(out["mean"]),
+                                                _ptr(out["Y"]), _ptr(out["Z"]), _ptr(out["Lc"]), C.byref(info),
+                                                C.byref(eps), C.byref(ms)), "gpry_sample_joint")
+        out["jitter_used"], out["device_ms"] = eps.value, ms.value
         return out
 
     def set_gates(self, sv=None, coef=None, gamma=0.0, intercept=0.0, positive_is_finite=True,

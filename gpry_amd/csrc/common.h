@@ -244,6 +244,8 @@ struct gpry_ctx {
     int64_t knn_cap = 0;
     uint8_t* dph = nullptr;            // gpry_ns_generation_phantoms: the chains' recorded states and their y (bytes)
     int64_t ph_cap = 0;
+    uint8_t* djoint = nullptr;         // gpry_predict_cov / gpry_sample_joint: panel, U, the two m-padded squares, draws (bytes)
+    int64_t joint_cap = 0;
 
     // host pinned staging
     void* hpin = nullptr; void* hpin_dev = nullptr; int64_t hpin_cap = 0;   // host / device view of the same buffer

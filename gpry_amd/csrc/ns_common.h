@@ -3,9 +3,12 @@
 // gpry_predict(x[None]) bit for bit (see nested.hip for the argument), ns_eval_multi the same for several points in one
 // pass; ns_philox is the counter-based generator all draw from, restated in numpy by tests/tools/ns_philox.py.  Phases
 // of the counter's word 0: 0-2 belong to the nested sampler (nested.hip), 3 to the Metropolis chains (mcmc.hip, and
-// mcmc_ladders.hip, which adds draw 17 for its swaps), 4 to the Hamiltonian chains (hmc.hip).
+// mcmc_ladders.hip, which adds draw 17 for its swaps), 4 to the Hamiltonian chains (hmc.hip), 5 to the joint draws of
+// the surrogate (joint.hip: counter (5 << 24, draw s, pair j / 2, 0) gives z_s,2(j/2) and z_s,2(j/2)+1).
 #pragma once
 #include "kern_math.h"
+
+#define NS_PHASE_JOINT 5u
 
 struct NsU2 { double a, b; };
 

@@ -1156,6 +1156,11 @@ class GaussianProcessRegressor(_RM, _BE):
         coordinates, scaled once (mean) and twice (std) by ``std_y`` -- as the reference does.
         """
         self.n_eval += len(X)
+        if return_cov:
+            if return_std or return_mean_grad or return_std_grad:
+                raise ValueError("At most one of return_std or return_cov can be requested, and no gradients "
+                                 "together with return_cov.")
+            return self._predict_cov(X, validate, ignore_trust_region)
         if return_std_grad and not (return_std and return_mean_grad):
             raise ValueError("Not returning std_gradient without returning the std and the mean grad.")
         if X.shape[0] != 1 and (return_mean_grad or return_std_grad):
@@ -1224,6 +1229,74 @@ class GaussianProcessRegressor(_RM, _BE):
         if return_std_grad:
             return y_mean, y_std, grad_mean, grad_std
         return (y_mean, y_std, grad_mean) if return_std else (y_mean, grad_mean)
+
+    JOINT_MAX_POINTS = 4096      # gpry_predict_cov / gpry_sample_joint: one m-padded square on the device
+
+    def _joint_mask(self, X, validate, ignore_trust_region):
+        """The gates of a joint call, as ``predict`` decides them: None when the device applies them itself
+        (``_sync_gates``), else the host's mask (with the device's own gates switched off for the call)."""
+        on_device = getattr(self.device, "applies_gates_in_predict", False)
+        if (on_device and (self.infinities_classifier is not None or self.trust_bounds is not None)
+                and self._sync_gates(ignore_trust_region)):
+            return None
+        if on_device and self._dev_gates is not None and self._dev_gates[1]:
+            self.device.set_gates()
+            self._dev_gates = None
+        return self._masks(X, validate, ignore_trust_region)
+
+    def _joint_limit(self, X, what):
+        if X.shape[0] > self.JOINT_MAX_POINTS:
+            raise ValueError(f"{what}: at most {self.JOINT_MAX_POINTS} points per call (got {X.shape[0]}); the joint "
+                             f"covariance of more needs blocked or low-rank draws")
+
+    def _predict_cov(self, X, validate, ignore_trust_region):
+        """``predict(X, return_cov=True)``: ``(mean (m,), cov (m, m))`` in untransformed units, sklearn's closed form
+        (_gpr.py:430-438) on the device (``gpry_predict_cov``).  The reference has no such branch (gpry/gpr.py:1062-1067).
+        The diagonal is not clamped at zero; a classifier-rejected point has a zero row and column (:1145)."""
+        X = self._validate_X(X, validate)
+        self._joint_limit(X, "predict(return_cov=True)")
+        if self.X_train_ is None:  # not fit: GP prior
+            y_mean = np.zeros(X.shape[0])
+            if self.trust_bounds is not None and not ignore_trust_region:
+                y_mean[~is_in_bounds(X, self.trust_bounds)] = self.minus_inf_value
+            return y_mean, self.kernel(X)
+        self._ensure_factor()
+        self._push_affine()
+        res = self.device.predict_cov(X, mask=self._joint_mask(X, validate, ignore_trust_region))
+        y_mean = res["mean"]
+        if self.minus_inf_value != -np.inf:
+            y_mean[np.isneginf(y_mean)] = self.minus_inf_value
+        return y_mean, res["cov"]
+
+    def sample_y(self, X, n_samples=1, random_state=0, validate=True, ignore_trust_region=False, jitter=None):
+        """Joint draws of the surrogate at ``X``: ``(m, n_samples)``, sklearn's ``sample_y`` (_gpr.py:470-508), drawn on
+        the device (``gpry_sample_joint``) around the unclipped mean; a classifier-rejected point is -inf in every draw.
+        ``random_state``: an int (used as the seed as it is) or a ``np.random.Generator`` / ``RandomState``, from which one
+        63-bit seed is drawn.  Draw s depends on the seed and s alone, not on ``n_samples``.
+        ``sample_y.last_result`` keeps ``jitter_used`` and ``device_ms`` of the last call."""
+        X = self._validate_X(X, validate)
+        m = X.shape[0]
+        self.n_eval += m
+        self._joint_limit(X, "sample_y")
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"n_samples must be at least 1 (got {n_samples})")
+        if isinstance(random_state, np.random.Generator):
+            seed = int(random_state.integers(0, 2 ** 63))
+        elif isinstance(random_state, np.random.RandomState):
+            seed = int(random_state.randint(0, 2 ** 63, dtype=np.int64))
+        elif random_state is None:
+            seed = int(np.random.default_rng().integers(0, 2 ** 63))
+        else:
+            seed = int(random_state)
+        if self.X_train_ is None:
+            raise ValueError("sample_y needs a model with training data")
+        self._ensure_factor()
+        self._push_affine()
+        res = self.device.sample_joint(X, n_samples, seed, jitter=jitter,
+                                       mask=self._joint_mask(X, validate, ignore_trust_region))
+        type(self).sample_y.last_result = dict(jitter_used=res["jitter_used"], device_ms=res["device_ms"], seed=seed)
+        return np.ascontiguousarray(res["Y"].T)
 
     def predict_with_gradients(self, X, validate=True, ignore_trust_region=False):
         """``predict(x, return_std=True, return_mean_grad=True, return_std_grad=True)`` for every row of
@@ -1344,3 +1417,6 @@ class GaussianProcessRegressor(_RM, _BE):
             return reference_diff_threshold
         ys = np.sort(y)
         return max(reference_diff_threshold, ys[-1] - ys[-min(n, len(ys))] + epsilon)
+
+
+GaussianProcessRegressor.sample_y.last_result = None

@@ -208,6 +208,103 @@ def mc_sample_from_gp(gpr, bounds=None, sampler="nested", sampler_options=None, 
 mc_sample_from_gp.last_result = None
 
 
+class SurrogateSpread:
+    """What ``surrogate_spread`` returns.  Per draw s (arrays of length ``n_draws``): ``dlogZ`` (the change of log Z),
+    ``means`` (n_draws, d), ``covs`` (n_draws, d, d) and ``ess`` (Kish) of the sample reweighted under realisation s.
+    Summaries: ``mean0`` / ``cov0`` (the sample's own mean and covariance), ``logZ_std``, ``mean_shift_sigma`` (d,; the
+    std over draws of the mean in units of the baseline posterior sigma), ``cov_ratio_std`` (d,; the std over draws of
+    var_s / var_0 per parameter), ``ess_min``, ``jitter_used``, ``n_points``, ``device_ms``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return (f"SurrogateSpread(n_points={self.n_points}, n_draws={len(self.dlogZ)}, logZ_std={self.logZ_std:.3g}, "
+                f"mean_shift_sigma={np.array2string(np.asarray(self.mean_shift_sigma), precision=3)}, "
+                f"ess_min={self.ess_min:.1f})")
+
+
+def _systematic(w, k, rng):
+    """Systematic resampling: k indices into the normalised weights ``w`` (one uniform, k evenly spaced positions)."""
+    c = np.cumsum(w)
+    c[-1] = 1.0
+    return np.searchsorted(c, (rng.random() + np.arange(k)) / k, side="right")
+
+
+def surrogate_spread(gpr, X, y, w=None, n_draws=256, seed=None, max_points=4096, jitter=None):
+    """How far the posterior moves because the GP is only an emulator: the Monte Carlo sample ``(X, y, w)`` that
+    ``mc_sample_from_gp`` returned, reweighted under ``n_draws`` joint realisations f_s of the surrogate at its rows
+    (``gpry_sample_joint``).  With mu the unclipped mean the draws are centred on, log r_si = f_s(x_i) - mu(x_i),
+    dlogZ_s = log sum_i w_i r_si, and mean, covariance and Kish effective sample size of the weights w_i r_si.
+
+    More than ``max_points`` (at most 4096) rows of non-zero weight: ``max_points`` of them by systematic resampling on
+    the weights (generator seeded from ``seed``), each kept row weighted by how often it was taken -- equal weights on
+    the resampled rows.  Otherwise all rows with their weights.  ``seed`` is also the seed of the draws (None: fresh
+    entropy).  Warns when the smallest effective sample size is below 5 % of the rows: the surrogate is then too
+    uncertain for the reweighting to mean anything, which is itself the finding.  Returns a ``SurrogateSpread``;
+    ``mc_sample_from_gp.last_result`` is left as it is."""
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    y = np.asarray(y, dtype=float)
+    n, d = X.shape
+    w = np.full(n, 1.0 / max(n, 1)) if w is None else np.asarray(w, dtype=float)
+    if y.shape != (n,) or w.shape != (n,):
+        raise ValueError(f"expected y and w of shape ({n},), got {y.shape} and {w.shape}")
+    n_draws, max_points = int(n_draws), int(max_points)
+    if n_draws < 2:
+        raise ValueError(f"n_draws must be at least 2 (got {n_draws})")
+    if not 1 <= max_points <= gpr.JOINT_MAX_POINTS:
+        raise ValueError(f"max_points must lie in [1, {gpr.JOINT_MAX_POINTS}] (got {max_points})")
+    if seed is None:
+        seed = int(np.random.default_rng().integers(2**63 - 1))
+    seed = int(seed)
+    keep = np.flatnonzero((w > 0) & np.isfinite(w) & np.isfinite(y))
+    if len(keep) == 0:
+        raise ValueError("the sample has no row of positive weight and finite y")
+    wk = w[keep] / w[keep].sum()
+    if len(keep) > max_points:
+        idx, counts = np.unique(_systematic(wk, max_points, np.random.default_rng(seed)), return_counts=True)
+        keep, wk = keep[idx], counts / counts.sum()
+    Xk, yk = np.ascontiguousarray(X[keep]), y[keep]
+    m = len(keep)
+    gpr._ensure_factor()
+    gpr._push_affine()
+    gpr.n_eval += m
+    # a row whose mean sits at the clip has lost mu: there f_s - mu is taken from the variates and the factor instead
+    clip = gpr._clip_hi()
+    clipped = bool(np.isfinite(clip) and np.any(yk >= clip))
+    res = gpr.device.sample_joint(Xk, n_draws, seed, jitter=jitter, mask=gpr._joint_mask(Xk, False, False),
+                                  want_Z=clipped, want_Lc=clipped)
+    with np.errstate(invalid="ignore"):
+        logr = res["Z"] @ res["Lc"].T if clipped else res["Y"] - res["mean"][None, :]
+    logr[~np.isfinite(res["Y"])] = -np.inf            # rows the gates reject take no part
+    a = np.log(wk)[None, :] + logr
+    top = a.max(axis=1)
+    if not np.all(np.isfinite(top)):
+        raise ValueError("every row of the sample is rejected by the classifier or the trust region")
+    e = np.exp(a - top[:, None])
+    tot = e.sum(axis=1)
+    dlogZ = top + np.log(tot)
+    ws = e / tot[:, None]
+    ess = 1.0 / np.sum(ws * ws, axis=1)
+    means = ws @ Xk
+    cen = Xk[None, :, :] - means[:, None, :]
+    covs = np.einsum("si,sia,sib->sab", ws, cen, cen)
+    mean0 = wk @ Xk
+    cov0 = np.einsum("i,ia,ib->ab", wk, Xk - mean0, Xk - mean0)
+    var0 = np.diag(cov0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean_shift_sigma = means.std(axis=0) / np.sqrt(var0)
+        cov_ratio_std = (np.einsum("saa->sa", covs) / var0).std(axis=0)
+    out = SurrogateSpread(dlogZ=dlogZ, means=means, covs=covs, ess=ess, mean0=mean0, cov0=cov0,
+                          logZ_std=float(dlogZ.std()), mean_shift_sigma=mean_shift_sigma, cov_ratio_std=cov_ratio_std,
+                          ess_min=float(ess.min()), jitter_used=res["jitter_used"], n_points=m,
+                          device_ms=res["device_ms"], seed=seed)
+    if out.ess_min < 0.05 * m:
+        warnings.warn(f"surrogate_spread: the smallest effective sample size over the draws is {out.ess_min:.1f} of {m} "
+                      "rows (< 5 %): the surrogate is too uncertain for the reweighted sample to mean anything")
+    return out
+
+
 def mc_sample_from_gp_ns(gpr, bounds=None, params=None, sampler=None, sampler_options=None, output=None, run=True,
                          verbose=3, seed=None):
     """gpry/mc.py:328-456 with the device nested sampler in place of PolyChord / UltraNest: ``(X, y, w)``.  ``sampler``

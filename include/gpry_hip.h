@@ -521,6 +521,40 @@ int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const d
 int gpry_hessian_mean(gpry_ctx* ctx, const double* X, int64_t npts, double* y_out, double* g_out, double* H_out,
                       double* device_ms);
 
+/* ---- Joint posterior covariance and joint draws of the surrogate at a batch of points (joint.hip; the spread of the
+ * posterior mean, covariance and evidence over realisations of the surrogate in gpry_amd/mc.py: surrogate_spread) ------
+ * The reference returns no covariance (gpry/gpr.py:1062-1067); the closed form is sklearn's (_gpr.py:430-438).
+ * gpry_predict_cov: X (m x d, raw coordinates as in gpry_predict), 1 <= m <= 4096.  With U = V K*^T (V = L^-1):
+ *   cov (m x m, row-major)  y_std^2 (K(X*, X*) - U^T U), in units of y^2.  The lower triangle is computed and the upper
+ *                           one copied: cov == cov^T to the last bit.  The diagonal is NOT clamped at 0 (gpry_predict's
+ *                           std is sqrt(max(0, .)) of it).  A row with GPRY_MASK_CLASSIFIED_INF (the caller's mask, with
+ *                           the device gates ORed in under option "predict_gates") has a zero row and column
+ *                           (gpry/gpr.py:1145); GPRY_MASK_OUTSIDE_TRUST changes the mean only.
+ *   mean (nullable, m)      finalised as gpry_predict does: y map, clip_hi, -inf where the merged mask has a bit.  The
+ *                           sum over the training rows is the cross-kernel panel's (as in gpry_predict_grad_batch).
+ * The k-ranges of the two products are split by the model size alone: cov[a][b] depends on the model and the two points,
+ * not on m, on the points' positions in the batch or on the context.
+ * gpry_sample_joint: S joint draws (1 <= S <= 65536) at the same kind of batch, Y (S x m, units of y):
+ *   Y_s = mu + L_c z_s,  mu the UNCLIPPED, UNGATED mean (the clip belongs to the mean, not to a realisation of f; `mean`,
+ *   nullable, is still the finalised mean of gpry_predict_cov), L_c the lower Cholesky factor of cov + eps C y_std^2 I.
+ *   A classifier-rejected row is -inf in every draw and takes no part (identity on its diagonal in the factored matrix).
+ *   eps starts at `jitter` (>= 0; a negative argument means 1e-10).  When the factorisation meets a pivot that is not
+ *   positive -- or a pivot l^2 <= 8 (m + 1) 2^-53 max diag, i.e. zero within the factorisation's own backward error -- eps
+ *   goes to 1e-14 (from 0) or to 100 eps and the matrix is factored again; above 1e-4 the call fails with -3, `info` the
+ *   1-based pivot.  jitter_used: the eps of the factor that was used (the ladder is deterministic).
+ *   z_s,j: Box-Muller (cos for even j, sin for odd j) of the two uniforms of Philox4x32-10 with counter
+ *   (5 << 24, s, j / 2, 0) and key `seed`: a function of (seed, s, j) alone.  Y_s,i sums j ascending in a fixed tiling:
+ *   draw s has the same bits whatever S.
+ *   Z_out (nullable, S x m) the variates, Lc_out (nullable, m x m) the factor with a zero upper triangle.
+ * Both refuse (-1, with gpry_last_error) before anything runs: a NULL required pointer (X, cov, Y); m or S out of range;
+ * no factorised model; d > 32; a coordinate that is not finite; a jitter that is NaN or infinite.  Both stop the resident
+ * predict kernel first.  device_ms (nullable): device time of the call, copies included. */
+int gpry_predict_cov(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* mask, double* mean, double* cov,
+                     double* device_ms);
+int gpry_sample_joint(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* mask, int64_t S, unsigned long long seed,
+                      double jitter, double* mean, double* Y, double* Z_out, double* Lc_out, int* info,
+                      double* jitter_used, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
