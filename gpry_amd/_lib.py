@@ -91,6 +91,8 @@ SIGNATURES = {
     "gpry_predict_cov": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_sample_joint": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp, _vp,
                                     _P(C.c_int), _P(C.c_double), _P(C.c_double)]),
+    "gpry_loo": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_leave_out": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -754,6 +756,43 @@ class Device:
                                                 C.byref(eps), C.byref(ms)), "gpry_sample_joint")
         out["jitter_used"], out["device_ms"] = eps.value, ms.value
         return out
+
+    # -- cross-validation of the training set (gpry_amd/gpr.py: loo, leave_out; mc.py: validate_gp) ------------------
+    LOO_OUTPUTS = ("mean", "var_y", "var_f", "seq_mean", "seq_var_y")
+
+    def loo(self, want=LOO_OUTPUTS):
+        """Leave-one-out and one-step-ahead predictives of the training targets from the resident factor (gpry_loo), in
+        units of y: a dict with ``mean``, ``var_y`` (the predictive of the observation y_i from all other points),
+        ``var_f`` (the latent variance, var_y less the point's noise, not below 0), ``seq_mean``, ``seq_var_y`` (y_k from
+        the points before it), each (N,) or None where ``want`` leaves it out, and ``device_ms``."""
+        out = {k: (np.empty(self.N) if k in want else None) for k in self.LOO_OUTPUTS}
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_loo(self._h, *[_ptr(out[k]) for k in self.LOO_OUTPUTS], C.byref(ms)), "gpry_loo")
+        out["device_ms"] = ms.value
+        return out
+
+    def leave_out(self, groups):
+        """Joint predictive of every group of training targets from the points outside it (gpry_leave_out).  ``groups``: a
+        sequence of index sequences (1 to 64 distinct indices each; groups may overlap).  A dict with ``mean`` and ``cov``
+        (lists, one (n_g,) and one (n_g, n_g) array per group, in the order of the group's indices, units of y), ``chi2``,
+        ``logpdf`` and ``info`` (one per group; info != 0: the group's block of K^-1 was not positive definite and its
+        outputs are NaN), ``dof`` and ``device_ms``."""
+        groups = [np.ascontiguousarray(g, dtype=np.int64).reshape(-1) for g in groups]
+        ng = len(groups)
+        sizes = np.array([len(g) for g in groups], dtype=np.int64)
+        offsets = np.zeros(ng + 1, dtype=np.int64)
+        np.cumsum(sizes, out=offsets[1:])
+        idx = np.concatenate(groups) if ng else np.zeros(0, dtype=np.int64)
+        ok = ng >= 1 and sizes.min() >= 1 and sizes.max() <= 64     # (the library refuses; no arrays for a refused request)
+        mean, cov = np.empty(len(idx) if ok else 0), np.empty(int(np.sum(sizes ** 2)) if ok else 0)
+        chi2, logpdf, info = np.empty(ng), np.empty(ng), np.zeros(ng, dtype=np.int32)
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_leave_out(self._h, _ptr(idx), _ptr(offsets), ng, _ptr(mean), _ptr(cov), _ptr(chi2),
+                                             _ptr(logpdf), _ptr(info), C.byref(ms)), "gpry_leave_out")
+        coff = np.concatenate([[0], np.cumsum(sizes ** 2)])
+        return dict(mean=[mean[offsets[g]:offsets[g + 1]] for g in range(ng)],
+                    cov=[cov[coff[g]:coff[g + 1]].reshape(sizes[g], sizes[g]) for g in range(ng)],
+                    chi2=chi2, logpdf=logpdf, info=info, dof=sizes, device_ms=ms.value)
 
     def set_gates(self, sv=None, coef=None, gamma=0.0, intercept=0.0, positive_is_finite=True,
                   trust_bounds=None):

@@ -246,6 +246,9 @@ struct gpry_ctx {
     int64_t ph_cap = 0;
     uint8_t* djoint = nullptr;         // gpry_predict_cov / gpry_sample_joint: panel, U, the two m-padded squares, draws (bytes)
     int64_t joint_cap = 0;
+    uint8_t* dloo = nullptr;           // gpry_loo / gpry_leave_out: partial sums of the pass over V, partial Grams, outputs (bytes)
+    int64_t loo_cap = 0;
+    void* hloo = nullptr; int64_t hloo_cap = 0;    // gpry_loo: pinned landing place of its five output rows (bytes)
 
     // host pinned staging
     void* hpin = nullptr; void* hpin_dev = nullptr; int64_t hpin_cap = 0;   // host / device view of the same buffer

@@ -248,9 +248,10 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
                     ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc, ctx->dknn,
-                    ctx->dph, ctx->djoint};
+                    ctx->dph, ctx->djoint, ctx->dloo};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
+    if (ctx->hloo) (void)hipHostFree(ctx->hloo);
     if (ctx->hbres) (void)hipHostFree(ctx->hbres);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);

@@ -1298,6 +1298,47 @@ class GaussianProcessRegressor(_RM, _BE):
         type(self).sample_y.last_result = dict(jitter_used=res["jitter_used"], device_ms=res["device_ms"], seed=seed)
         return np.ascontiguousarray(res["Y"].T)
 
+    # ---- cross-validation of the training set (gpry_loo, gpry_leave_out; the report: gpry_amd/mc.py: validate_gp) --
+    def _cv_ready(self, what):
+        if getattr(self, "X_train_", None) is None or not len(self.y_train):
+            raise ValueError(f"{what} needs a model with training data")
+        self._ensure_factor()
+        self._push_affine()
+
+    def loo(self):
+        """Leave-one-out and one-step-ahead predictives of the training targets, on the device (``gpry_loo``) from the
+        factor it holds: at the current hyper-parameters and with the pre-processors as they are, nothing is refitted
+        (Rasmussen & Williams 5.4.2).  A dict of arrays (n,) over ``X_train`` / ``y_train`` (the finite training set), in
+        untransformed units: ``mean`` and ``var_y``, the predictive of the observation ``y_train[i]`` from all other
+        points; ``var_f``, the latent variance (``var_y`` less the point's noise, not below 0: what
+        ``predict(return_std=True)`` of the model without point i gives at ``X_train[i]``); ``seq_mean`` and
+        ``seq_var_y``, the predictive of ``y_train[k]`` from the points before it; and ``device_ms``.  The predictives are
+        unclipped and ungated, as those of ``predict(return_cov=True)`` are: ``clip_factor``, the classifier and the
+        trust region play no part."""
+        self._cv_ready("loo")
+        return self.device.loo()
+
+    def leave_out(self, groups):
+        """The joint predictive of each group of training targets from the points outside it (``gpry_leave_out``), same
+        conventions as ``loo``.  ``groups``: a sequence of index sequences into ``X_train`` / ``y_train`` (1 to 64
+        distinct indices each; groups may overlap), or ``"last"``: the finite points of the last ``append_to_data``.
+        A dict: ``mean`` and ``cov`` (lists: (n_g,) and (n_g, n_g) per group, in the order of the group's indices),
+        ``chi2`` = (y_G - mean)^T cov^-1 (y_G - mean) with ``dof`` = n_g degrees of freedom, ``logpdf`` (the log density
+        of y_G under that predictive), ``info`` (non-zero: the group's block of K^-1 was not positive definite, its
+        outputs are NaN), ``groups`` (the index arrays) and ``device_ms``.  Unclipped and ungated."""
+        self._cv_ready("leave_out")
+        if isinstance(groups, str):
+            if groups != "last":
+                raise ValueError(f"groups: index sequences or 'last' (got {groups!r})")
+            k = int(getattr(self, "n_last_appended_finite", 0))
+            if k < 1:
+                raise ValueError("groups='last': the last append_to_data added no finite point")
+            groups = [np.arange(len(self.y_train) - k, len(self.y_train))]
+        groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+        res = self.device.leave_out(groups)
+        res["groups"] = groups
+        return res
+
     def predict_with_gradients(self, X, validate=True, ignore_trust_region=False):
         """``predict(x, return_std=True, return_mean_grad=True, return_std_grad=True)`` for every row of
         ``X`` in ONE device call (``gpry_predict_grad_batch``): ``(mean (m,), std (m,), mean_grad (m, d),

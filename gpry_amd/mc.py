@@ -305,6 +305,51 @@ def surrogate_spread(gpr, X, y, w=None, n_draws=256, seed=None, max_points=4096,
     return out
 
 
+class GPValidation:
+    """What ``validate_gp`` returns.  ``loo`` and ``seq`` (leave-one-out, one-step-ahead) each hold ``z`` (n,; the
+    z-scores (y - mean) / sqrt(var_y)), ``rms`` (of z; 1 for a calibrated model), ``frac1`` / ``frac2`` (the fractions
+    with |z| <= 1 and |z| <= 2; ``GAUSS1`` = 0.683 and ``GAUSS2`` = 0.954 for a Gaussian), ``mean_logpdf`` (the mean log
+    predictive density of the observations) and ``outliers`` (the indices with |z| > 3).  With groups: ``groups`` holds
+    ``chi2``, ``dof``, ``logpdf``, ``info`` (one per group) and ``indices``.  ``n`` and ``device_ms``."""
+    GAUSS1, GAUSS2 = 0.6826894921370859, 0.9544997361036416
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        part = "; ".join(f"{k}: rms z {v['rms']:.3g}, |z|<=1 {v['frac1']:.3f}, |z|<=2 {v['frac2']:.3f}, "
+                         f"{len(v['outliers'])} beyond 3" for k, v in (("loo", self.loo), ("seq", self.seq)))
+        return f"GPValidation(n={self.n}; {part})"
+
+
+def _z_report(y, mean, var):
+    z = (y - mean) / np.sqrt(var)
+    a = np.abs(z)
+    return dict(z=z, rms=float(np.sqrt(np.mean(z * z))), frac1=float(np.mean(a <= 1.0)), frac2=float(np.mean(a <= 2.0)),
+                mean_logpdf=float(np.mean(-0.5 * z * z - 0.5 * np.log(2.0 * np.pi * var))),
+                outliers=np.flatnonzero(a > 3.0))
+
+
+def validate_gp(gpr, groups=None):
+    """Cross-validation of the surrogate against the training set it already holds (Rasmussen & Williams 5.4.2): no
+    likelihood call and no refit, from the factor on the device (``gpr.loo``, ``gpr.leave_out``), at the current
+    hyper-parameters and pre-processors.  Leave-one-out asks whether each point is predicted by all the others;
+    one-step-ahead whether it was predicted by the points acquired before it (its log densities sum to the log marginal
+    likelihood); ``groups`` (index sequences into ``X_train``, or ``"last"``) whether each batch as a whole was
+    predicted by the rest -- the points of a Kriging-believer batch are correlated, so their z-scores are not
+    independent and chi^2 with n_g degrees of freedom is the statistic.  A pure report: it warns of nothing and changes
+    nothing.  Returns a ``GPValidation``."""
+    res = gpr.loo()
+    y = np.asarray(gpr.y_train, dtype=float)
+    out = dict(n=len(y), loo=_z_report(y, res["mean"], res["var_y"]), seq=_z_report(y, res["seq_mean"], res["seq_var_y"]),
+               groups=None, device_ms=res["device_ms"])
+    if groups is not None:
+        g = gpr.leave_out(groups)
+        out["groups"] = dict(chi2=g["chi2"], dof=g["dof"], logpdf=g["logpdf"], info=g["info"], indices=g["groups"])
+        out["device_ms"] += g["device_ms"]
+    return GPValidation(**out)
+
+
 def mc_sample_from_gp_ns(gpr, bounds=None, params=None, sampler=None, sampler_options=None, output=None, run=True,
                          verbose=3, seed=None):
     """gpry/mc.py:328-456 with the device nested sampler in place of PolyChord / UltraNest: ``(X, y, w)``.  ``sampler``

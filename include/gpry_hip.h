@@ -555,6 +555,40 @@ int gpry_sample_joint(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* 
                       double jitter, double* mean, double* Y, double* Z_out, double* Lc_out, int* info,
                       double* jitter_used, double* device_ms);
 
+/* ---- Cross-validation of the training set from the resident factor (loo.hip; the report in gpry_amd/mc.py: validate_gp) --
+ * Rasmussen & Williams section 5.4.2, at the current theta and with the y map as it is (nothing is refitted).  With
+ * V = L^-1, K^-1 = V^T V, alpha_ = K^-1 y_ and the noise vector `alpha` of gpry_set_train (sigma_n^2, transformed units):
+ * gpry_loo: N doubles each, any pointer may be NULL, all in units of y (y^2):
+ *   mean, var_y   the predictive of the OBSERVATION y_i from all other points: y_i - alpha_i / q_i and 1 / q_i with
+ *                 q_i = (K^-1)_ii = sum_k V_ki^2;
+ *   var_f         max(1 / q_i - sigma_n,i^2, 0): the latent variance, what gpry_predict's std^2 of the model without
+ *                 point i is at x_i;
+ *   seq_mean, seq_var_y   the predictive of y_k from the points BEFORE it (one-step-ahead): y_k - w_k / V_kk and
+ *                 1 / V_kk^2 with w = V y_; its z-score is w_k, and the log densities sum to the log marginal likelihood.
+ *   One pass over the lower triangle of V in 64 x 64 tiles, the partial sums added in ascending tile order: q_i and w_k
+ *   depend bit for bit on the model alone (not on the context, nor on which outputs are asked for: both are always formed).
+ * gpry_leave_out: `ngroups` index sets, group g = idx[offsets[g] .. offsets[g + 1]) (offsets[0] = 0), each of 1 to 64
+ *   distinct indices in [0, N); groups may overlap.  With B = (K^-1)_GG = V[:, G]^T V[:, G] (FP64 matrix pipe, the rows
+ *   split by the model size alone) and delta = B^-1 alpha_G:
+ *   mean (one per index, in the order of idx)          y_G - delta, the joint predictive mean of y_G from the rest;
+ *   cov (the n_g x n_g blocks one after another)       B^-1 y_std^2, rows and columns in the order of idx;
+ *   chi2 (ngroups)     alpha_G^T delta = (y_G - mean)^T cov^-1 (y_G - mean), n_g degrees of freedom;
+ *   logpdf (ngroups)   log N(y_G; mean, cov), the density in units of y: -chi2 / 2 + log det B / 2 - n_g (log(2 pi) / 2 + log y_std);
+ *   info (ngroups)     0, or the 1-based pivot (indices ascending) at which B was not positive definite: that group's
+ *                      outputs are NaN, the call and the other groups are not affected.
+ *   Every group's indices are sorted on the host and its outputs handed back in the caller's order: a group's results
+ *   are the same bits whatever the order of its indices (up to that permutation), whatever other groups share the call
+ *   and wherever it stands in the list.  All output pointers may be NULL.
+ * Both refuse (-1, with gpry_last_error) when the context holds no valid factor; gpry_leave_out also an empty group, one
+ * of more than 64 points, an index outside [0, N) and an index twice in a group.  Both work on the factor grown by
+ * gpry_append_rows, stop the resident predict kernel first, and read V, alpha_, y_ and the noise vector only: the state of
+ * gpry_predict, of a sweep, of a Kriging-believer session and of the samplers is untouched.  Stage timers "loo" and
+ * "leave_out" (gpry_timing_get).  device_ms (nullable): device time of the call, copies included. */
+int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* seq_mean, double* seq_var_y,
+             double* device_ms);
+int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, int64_t ngroups, double* mean, double* cov,
+                   double* chi2, double* logpdf, int* info, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
