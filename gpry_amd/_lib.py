@@ -108,6 +108,9 @@ SIGNATURES = {
     "gpry_kb_reset": (C.c_int, [_vp]),
     "gpry_kb_register": (C.c_int, [_vp, _vp, C.c_int64, _P(C.c_int64), _vp]),
     "gpry_kb_gram": (C.c_int, [_vp, C.c_int64, _vp, _vp, _P(C.c_int64)]),
+    "gpry_kb_gram_rows": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _P(C.c_int64)]),
+    "gpry_kb_rank": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
+                               C.c_int64, _vp, _vp, _vp, _vp, _vp, _P(C.c_int64), _P(C.c_int64), _vp]),
     "gpry_comm_unique_id": (C.c_int, [_vp]),
     "gpry_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _P(_vp)]),
     "gpry_comm_destroy": (C.c_int, [_vp]),
@@ -942,6 +945,42 @@ class Device:
         if nn.value != n:
             raise GpryHipError(f"kb_gram: device holds {nn.value} candidates, host expected {n}")
         return G, kv
+
+    def kb_gram_rows(self, p, n):
+        """Gram rows of the registered candidates ``p`` from one launch: ``(G, kv)``, one row per entry of ``p``."""
+        p = np.ascontiguousarray(p, dtype=np.int64)
+        G, kv = np.empty((len(p), n)), np.empty((len(p), n))
+        nn = C.c_int64(0)
+        self._check(self._lib.gpry_kb_gram_rows(self._h, _ptr(p), len(p), _ptr(G), _ptr(kv), C.byref(nn)),
+                    "gpry_kb_gram_rows")
+        if nn.value != n:
+            raise GpryHipError(f"kb_gram_rows: device holds {nn.value} candidates, host expected {n}")
+        return G, kv
+
+    def kb_rank(self, X_new, var0, idx, y, sigma, acq, order, params, slots):
+        """``gpry_kb_rank``: registers ``X_new`` (their ``var0`` is written behind the session's), then ranks the offer into
+        the pool ``slots = (idx, y, sigma, acq, acq_cond)`` (int64 / float64 arrays of n_points + 1, updated in place).
+        Returns ``(cache_models, info, stats)``: models built, 0 or t + 1 of a non-positive-definite border, and
+        (launches, rows, extra requests)."""
+        m_new = 0 if X_new is None else len(X_new)
+        X_new = None if m_new == 0 else _f64(X_new)
+        params = _f64(params)
+        counter, info = C.c_int64(0), C.c_int64(0)
+        stats = np.zeros(3, dtype=np.int64)
+        s_idx, s_y, s_sigma, s_acq, s_cond = slots
+        for a, t in ((var0, np.float64), (idx, np.int64), (y, np.float64), (sigma, np.float64), (acq, np.float64),
+                     (order, np.int64), (s_idx, np.int64), (s_y, np.float64), (s_sigma, np.float64),
+                     (s_acq, np.float64), (s_cond, np.float64)):
+            if a.dtype != t or not a.flags.c_contiguous:
+                raise ValueError("kb_rank: arrays must be contiguous int64 / float64")
+        if not (len(y) == len(sigma) == len(acq) == len(idx)) or len(params) != 5 or \
+                not (len(s_idx) == len(s_y) == len(s_sigma) == len(s_acq) == len(s_cond)):
+            raise ValueError("kb_rank: array lengths do not match")
+        self._check(self._lib.gpry_kb_rank(self._h, _ptr(X_new), m_new, _ptr(var0), len(var0), _ptr(idx), _ptr(y),
+                                           _ptr(sigma), _ptr(acq), len(idx), _ptr(order), len(order), _ptr(params),
+                                           len(s_idx) - 1, _ptr(s_idx), _ptr(s_y), _ptr(s_sigma), _ptr(s_acq),
+                                           _ptr(s_cond), C.byref(counter), C.byref(info), _ptr(stats)), "gpry_kb_rank")
+        return counter.value, info.value, stats
 
     # -- measurement ----------------------------------------------------------------
     def timing_reset(self):

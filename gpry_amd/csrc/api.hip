@@ -1,6 +1,7 @@
 // C-ABI entry points of the GP hot path (include/gpry_hip.h): factor, LML, predict, gates and Kriging-believer support
 // (the NORA sweep: sweep.hip; its shortlist selection: sweep_topk.hip).
 #include "sweep.h"
+#include "kb_gram.h"
 #include <algorithm>
 
 int require_model(gpry_ctx* ctx, bool need_factor) {
@@ -996,32 +997,14 @@ __global__ void scale_rows_kernel(const double* __restrict__ X, int64_t m, int d
     }
     out[idx] = v;
 }
-// one wave per row x: out_dot[x] = U[x].U[p] ; out_k[x] = C k(|xs_x - xs_p|)
-__device__ __forceinline__ double kb_corr(int kid, double r2) {
-    switch (kid) {
-        case GPRY_RBF: return exp(-0.5 * r2);
-        case GPRY_MATERN12: return exp(-sqrt(r2));
-        case GPRY_MATERN32: { double t = sqrt(r2) * 1.7320508075688772; return (1.0 + t) * exp(-t); }
-        default: { double t = sqrt(r2) * 2.23606797749979; return (1.0 + t + t * t / 3.0) * exp(-t); }
-    }
-}
+// one wave per row x: out_dot[x] = U[x].U[p] ; out_k[x] = C k(|xs_x - xs_p|)  (kb_gram.h)
 __global__ __launch_bounds__(256) void kb_gram_kernel(const double* __restrict__ U, int64_t ldu, int64_t n, int64_t p,
                                                       int64_t Np, const double* __restrict__ Xkb, int dpad,
                                                       int kid, double C, double* __restrict__ out_dot,
                                                       double* __restrict__ out_k) {
-    const int lane = threadIdx.x & 63;
     const int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (x >= n) return;
-    const double* ux = U + x * ldu; const double* up = U + p * ldu;
-    double s = 0.0;
-    for (int64_t i = lane; i < Np; i += 64) s = fma(ux[i], up[i], s);
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) {
-        out_dot[x] = s;
-        double r2 = 0.0;
-        for (int k = 0; k < dpad; k++) { double df = Xkb[x * dpad + k] - Xkb[p * dpad + k]; r2 = fma(df, df, r2); }
-        out_k[x] = C * kb_corr(kid, r2);
-    }
+    kb_gram_entry(U, ldu, x, p, Np, Xkb, dpad, kid, C, out_dot, out_k);
 }
 __global__ __launch_bounds__(256) void kb_var0_kernel(const double* __restrict__ U, int64_t ldu, int64_t first,
                                                       int64_t m, int64_t Np, double C, double* __restrict__ out) {

@@ -199,6 +199,7 @@ struct gpry_ctx {
     const double* up_X = nullptr;      // host pool of the sweep in flight whose chunks are still to be uploaded (sweep.hip: run_sweep)
     const double* up_y = nullptr;      // ... and the caller's y of a sweep with given y (gpry_sweep_logexp_given), beside them
     int up_gates = 0;                  // ... and the device gates are evaluated chunk by chunk behind each upload
+    int opt_kb_rank = 1;               // 1: RankedPool.add ranks an offer through gpry_kb_rank (kb_rank.hip); 0: the Python path (the comparator)
     int opt_predict_gates = 0;         // 1: gpry_predict ORs the device gates (gpry_set_gates) into the caller's mask, as the sweep does
     // pruned sweep (option "sweep_prune", sweep.hip / sweep_topk.hip): gpry_sweep_logexp with no arrays wanted leaves y and a per-candidate upper
     // bound of the acquisition; gpry_sweep_topk contracts only the candidates whose bound can reach the shortlist

@@ -321,6 +321,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("predict_serve", opt_predict_serve, 0, 1, (void)0),
     OPT_INT("serve_idle_us", opt_serve_idle_us, 10, 1000000, (void)0),
     OPT_INT("mcmc_mapped", opt_mcmc_mapped, 0, 1, (void)0),
+    OPT_INT("kb_rank", opt_kb_rank, 0, 1, (void)0),
 };
 #undef OPT_INT
 const OptionSpec* find_option(const char* key) {

@@ -885,7 +885,7 @@ class NORA(GenericGPAcquisition):
                     break
                 K *= 4
         self.stats.update(shortlist=fed, cache_models=self.pool.cache_counter,
-                          rank_s=time() - t_rank)
+                          rank_s=time() - t_rank, rank_native=self.pool.rank_native)
         pruned_on = getattr(self, "_pruned_on", [])
         if pruned_on:
             self.stats["prune"] = [t.sweep_prune_info() for t in pruned_on]
@@ -899,6 +899,23 @@ class NORA(GenericGPAcquisition):
         self.pool.reset_cache()
         self.log(f"({(time() - t_rank):.2g} sec) Ranked pool of candidates.", level=2)
         return X_pool, y_pool, acq_pool
+
+
+class _LazyModels(list):
+    """``RankedPool.gpr_cond`` after a native ``add``: the conditioned model of slots ``0..i`` is built from the returned
+    order when somebody asks for it."""
+
+    def __init__(self, session, slot_idx, n_filled):
+        super().__init__([None] * len(slot_idx))
+        self._session, self._slot_idx, self._n_filled = session, [int(i) for i in slot_idx], n_filled
+
+    def __getitem__(self, i):
+        model = super().__getitem__(i)
+        if model is None and isinstance(i, (int, np.integer)) and 0 <= i < self._n_filled:
+            from gpry_amd.kriging import ConditionedGPR
+            model = ConditionedGPR(self._session, self._slot_idx[:i + 1])
+            self[i] = model
+        return model
 
 
 class RankedPool:
@@ -921,6 +938,7 @@ class RankedPool:
         self.acq = np.zeros(size + 1)
         self.reset_cache()
         self.cache_counter = 0
+        self.rank_native = False        # the last add() went through gpry_kb_rank
 
     def __len__(self):
         return len(self.y) - 1
@@ -969,6 +987,9 @@ class RankedPool:
         if acq is None:
             acq = self._acq_func(y, sigma)
         m = method.lower()
+        self.rank_native = self._add_native(X, y, sigma, acq) if m == "single sort acq" else False
+        if self.rank_native:
+            return
         if hasattr(self._gpr, "kb_session") and 0 < len(X) <= 16384:
             # one device pass computes u(x) = V k*(x) for the whole offer; conditioned
             # standard deviations are then look-ups (gpry_amd/kriging.py)
@@ -989,6 +1010,57 @@ class RankedPool:
                 # first test (:1432) without touching the pool
                 break
             self.add_one(X[i], y[i], sigma[i], acq[i])
+
+    def _native_params(self):
+        """The LogExp parameters of the pool's acquisition function, or None if it is not ``LogExp.f`` with a scalar
+        noise level (what ``gpry_kb_rank`` evaluates)."""
+        f = self._acq_func
+        if not isinstance(f, partial) or f.func is not gpryacqfuncs.LogExp.f or f.args:
+            return None
+        kw = f.keywords
+        if set(kw) != {"baseline", "noise_level", "zeta"} or np.iterable(kw["noise_level"]):
+            return None
+        return {"sigma_n": float(kw["noise_level"]), "baseline": float(kw["baseline"]), "zeta": float(kw["zeta"])}
+
+    def _add_native(self, X, y, sigma, acq):
+        """``add(method="single sort acq")`` in one library call (``gpry_kb_rank``: registration of the offer, batched
+        Gram rows, the slot logic in C++).  False where the call does not apply -- no ``kb_rank`` on the device or option
+        ``kb_rank`` = 0, a classifier, a per-point noise level, another acquisition function, more than 16384 rows, a NaN
+        -- and the Python path below runs.  The pool's arrays are left as that path leaves them; only the rounding
+        inside ``acq_cond`` may differ (numpy's dot sums in BLAS order, the library in index order)."""
+        gpr = self._gpr
+        dev = getattr(gpr, "device", None)
+        if dev is None or not hasattr(dev, "kb_rank") or not hasattr(gpr, "kb_session"):
+            return False
+        if gpr.infinities_classifier is not None or np.iterable(gpr.noise_level) or not 0 < len(X) <= 16384:
+            return False
+        params = self._native_params()
+        if params is None or not dev.get_option("kb_rank"):
+            return False
+        y, sigma, acq = (np.ascontiguousarray(a, dtype=np.float64) for a in (y, sigma, acq))
+        if np.isnan(acq).any():
+            return False
+        sess = gpr.kb_session()
+        filled = self.acq_cond > -np.inf
+        s_idx = np.array([sess._index.get(np.ascontiguousarray(row, dtype=float).tobytes(), -1) for row in self.X],
+                         dtype=np.int64)
+        if np.any(s_idx[filled] < 0):
+            return False            # (a pool filled under another session)
+        order = np.ascontiguousarray(np.argsort(acq)[::-1], dtype=np.int64)
+        slots = (s_idx, self.y, self.sigma, self.acq, self.acq_cond)
+        _, (models, info, stats) = sess.rank(X, y, sigma, acq, order, params, slots)
+        self.cache_counter += models
+        held = s_idx >= 0
+        self.X[held] = sess.X[s_idx[held]]
+        self.X[~held] = 0.0
+        self.gpr_cond = _LazyModels(sess, s_idx, int(np.count_nonzero(self.acq_cond[:-1] > -np.inf)))
+        self.rank_stats = tuple(int(v) for v in stats)
+        if info:
+            raise np.linalg.LinAlgError(
+                f"{info}-th appended point makes the augmented kernel matrix non positive "
+                "definite. Try gradually increasing the 'noise_level' parameter of your "
+                "GaussianProcessRegressor estimator.")
+        return True
 
     def add_bulk(self, X, y, sigma, acq, i_start=0):
         """Fill slot after slot from the whole batch (gp_acquisition.py:1337-1390)."""

@@ -47,11 +47,11 @@ class KBSession:
     def n(self):
         return len(self.var0)
 
-    def register(self, X):
-        """Session indices of the rows of ``X`` (new rows are sent to the device)."""
+    def _assign(self, X):
+        """Session indices of the rows of ``X``, and the rows the device does not hold yet (``None`` if it has all)."""
         X = np.ascontiguousarray(np.atleast_2d(X), dtype=float)
         idx = np.empty(len(X), dtype=np.int64)
-        new_rows, new_pos = [], []
+        new_rows = []
         for i, row in enumerate(X):
             key = row.tobytes()
             j = self._index.get(key)
@@ -59,23 +59,48 @@ class KBSession:
                 j = self.n + len(new_rows)
                 self._index[key] = j
                 new_rows.append(row)
-                new_pos.append(i)
             idx[i] = j
-        if new_rows:
-            Xn = np.array(new_rows)
+        return idx, (np.array(new_rows) if new_rows else None)
+
+    def _commit(self, Xn, var0):
+        """The rows ``Xn`` are on the device, with these ``var0``."""
+        self.X = np.vstack([self.X, Xn])
+        self.var0 = np.append(self.var0, var0)
+        clf = self.gpr.infinities_classifier
+        if clf is None:
+            m = np.zeros(len(Xn), bool)
+        else:
+            Xn_ = np.ascontiguousarray(self.gpr.preprocessing_X.transform(Xn))
+            m = np.logical_not(clf.predict(Xn_, validate=False))
+        self.masked = np.append(self.masked, m)
+
+    def register(self, X):
+        """Session indices of the rows of ``X`` (new rows are sent to the device)."""
+        idx, Xn = self._assign(X)
+        if Xn is not None:
             first, var0 = self.dev.kb_register(Xn)
             if first != self.n:
                 raise _lib.GpryHipError("KB session out of sync with the device")
-            self.X = np.vstack([self.X, Xn])
-            self.var0 = np.append(self.var0, var0)
-            clf = self.gpr.infinities_classifier
-            if clf is None:
-                m = np.zeros(len(Xn), bool)
-            else:
-                Xn_ = np.ascontiguousarray(self.gpr.preprocessing_X.transform(Xn))
-                m = np.logical_not(clf.predict(Xn_, validate=False))
-            self.masked = np.append(self.masked, m)
+            self._commit(Xn, var0)
         return idx
+
+    def rank(self, X, y, sigma, acq, order, params, slots):
+        """``gpry_kb_rank``: register the offer ``X`` and rank it into the pool ``slots`` (session indices and values per
+        slot, updated in place) in one library call.  Returns the offer's session indices and the call's
+        ``(cache_models, info, stats)``."""
+        idx, Xn = self._assign(X)
+        m_new = 0 if Xn is None else len(Xn)
+        var0 = np.concatenate([self.var0, np.empty(m_new)])
+        try:
+            out = self.dev.kb_rank(Xn, var0, idx, y, sigma, acq, order,
+                                   [params["sigma_n"], self.noise_alpha(), params["baseline"], params["zeta"],
+                                    self.std_y], slots)
+        except Exception:
+            self.gpr._kb = None      # host and device may disagree on what is registered: the next user starts afresh
+            raise
+        if m_new:
+            self._commit(Xn, var0[len(var0) - m_new:])
+        return idx, out
 
     def gram(self, p):
         """(u(p).u(x), k(p, x)) for all registered x; recomputed when the session has grown."""

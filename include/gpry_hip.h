@@ -158,6 +158,9 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *                             computed from it, agree to rounding
  *     "chol_stacked_dense" 0/1  1: that schedule without use of the zero structure of the appended rows (every row block in
  *                             every step, every panel applied to every tile: three times the work; the comparator, same bits)
+ *     "kb_rank" 0/1           1 (default): the Python mirror ranks an offer of the Kriging-believer pool through gpry_kb_rank
+ *                             (one call: registration, batched Gram rows, the slot logic in C++); 0: its own loop over
+ *                             gpry_kb_gram, one call per accepted point (the comparator; same picks, acq_cond to rounding)
  *     "predict_gates" 0/1     gpry_predict applies the gates of gpry_set_gates itself (default 0; the Python mirror sets 1)
  *     "predict_serve" 0/1     mean-only gpry_predict of <= 8 points is answered by a RESIDENT kernel (no launch per call;
  *                             default 1); "serve_idle_us" = how long that kernel waits for the next request before it
@@ -709,6 +712,31 @@ int gpry_kb_register(gpry_ctx* ctx, const double* X, int64_t m, int64_t* first,
 /* For registered candidate p: G[x] = u(p).u(x) and kvec[x] = kernel_(x_p, x) for every
  * registered x (n = number registered so far; both arrays length n). */
 int gpry_kb_gram(gpry_ctx* ctx, int64_t p, double* G, double* kvec, int64_t* n);
+/* The same for n_rows registered candidates p[] in ONE launch: row j of G / kvec (n_rows x n, row-major) is what
+ * gpry_kb_gram(p[j]) returns, bit for bit, whatever shares the launch. */
+int gpry_kb_gram_rows(gpry_ctx* ctx, const int64_t* p, int64_t n_rows, double* G, double* kvec, int64_t* n);
+/* The Kriging-believer ranking of an offer in one call: RankedPool.add(method="single sort acq") with add_one,
+ * _position_for, sort, cache_model and the conditioned models' predict_std (gpry/gp_acquisition.py:1290-1335, 1392-1520,
+ * 1522-1555, 1598-1670), for a model without infinities classifier and with a scalar noise level.  The slot logic runs on
+ * the host (csrc/kb_rank_core.h, which writes down the order of operations); the Gram rows it needs come from batched
+ * launches, the first of them speculative (the pool's slots and the first 2 n_points offers in walking order).
+ *   X_new (m_new x d): the offer's rows that the session does not hold yet; they are registered first (gpry_kb_register)
+ *     and get the session indices [n_session - m_new, n_session).  var0 (n_session): C - |u|^2 of every session candidate;
+ *     the last m_new entries are written here.
+ *   idx, y, sigma, acq (n_offer): session index and sweep values of each offered row; order (n_order): the walk,
+ *     np.argsort(acq)[::-1] of the caller.  params: sigma_n, alpha (noise on the border diagonal, transformed units),
+ *     baseline, zeta, y_std.
+ *   slot_* (n_points + 1 each, in/out) and *cache_counter (in/out): the pool; slot_idx -1 = never filled, slot_acq_cond
+ *     -inf = empty.  A second call continues the pool.
+ *   *info: 0, or t + 1 when the t-th appended point makes the augmented kernel matrix non positive definite (the pool is
+ *     then left as it stood at that point).  stats (nullable, 3 values): Gram launches, rows fetched, requests of the core
+ *     beyond the speculative one.
+ * Against the Python path only the rounding inside slot_acq_cond may differ (numpy's dot sums in BLAS order). */
+int gpry_kb_rank(gpry_ctx* ctx, const double* X_new, int64_t m_new, double* var0, int64_t n_session,
+                 const int64_t* idx, const double* y, const double* sigma, const double* acq, int64_t n_offer,
+                 const int64_t* order, int64_t n_order, const double* params, int64_t n_points,
+                 int64_t* slot_idx, double* slot_y, double* slot_sigma, double* slot_acq, double* slot_acq_cond,
+                 int64_t* cache_counter, int64_t* info, int64_t* stats);
 
 /* ---- a16: multi-GPU (one process per GPU, RCCL over xGMI) -------------------------- */
 /* 128-byte RCCL unique id, made on rank 0 and distributed by the caller. */

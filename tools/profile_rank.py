@@ -39,4 +39,5 @@ for _ in range(5):
     X_new, _, _ = acq.multi_add(gpr, n_points=d, rng=rng)
 pr.disable()
 print("stats", acq.stats)
+print("rank_native", acq.stats.get("rank_native"), "rank_ms", acq.stats["rank_s"] * 1e3)
 pstats.Stats(pr).sort_stats("cumulative").print_stats(45)
