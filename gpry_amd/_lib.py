@@ -4,6 +4,7 @@ There is deliberately no CPU fallback: if the shared library is missing, or a de
 call is made on a machine without a GPU, the error is raised to the caller.
 """
 import ctypes as C
+import ctypes as _ct     # for svm_fit, whose parameter C is the classifier's
 import os
 
 import numpy as np
@@ -92,6 +93,8 @@ SIGNATURES = {
     "gpry_sample_joint": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp, _vp,
                                     _P(C.c_int), _P(C.c_double), _P(C.c_double)]),
     "gpry_loo": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_svm_fit": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int64, _vp,
+                               _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int64), _P(C.c_int), _P(C.c_double)]),
     "gpry_leave_out": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
@@ -773,6 +776,31 @@ class Device:
         self._check(self._lib.gpry_loo(self._h, *[_ptr(out[k]) for k in self.LOO_OUTPUTS], C.byref(ms)), "gpry_loo")
         out["device_ms"] = ms.value
         return out
+
+    # -- training of the infinities classifier (gpry_amd/svm.py: SVM(trainer="device")) -------------------------------
+    def svm_fit(self, X, finite, C, gamma, eps=1e-3, max_iter=None):
+        """The C-SVC dual of the two classes ``finite`` / not, RBF kernel ``exp(-gamma |a - b|^2)``, solved on the device
+        (gpry_svm_fit: libsvm's SMO without shrinking).  X: (N, d) in the coordinates the classifier is evaluated in.
+        Returns ``alpha`` (N,), ``rho`` (decision(x) = sum_t y_t alpha_t k(x_t, x) - rho with y = +1 for finite),
+        ``objective``, ``violation`` (G_max - G_min of the last stop test), ``n_iter``, ``status`` (0 converged, 1 the
+        budget of ``max_iter`` updates -- default 100 N + 10000 -- ran out; alpha is feasible either way) and
+        ``device_ms``.  The model, sweep, gates and sessions of the context are not touched."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("svm_fit: X must be (N, d)")
+        N, d = X.shape
+        finite = np.ascontiguousarray(np.asarray(finite).astype(bool), dtype=np.uint8)
+        if finite.shape != (N,):
+            raise ValueError("svm_fit: finite must be (N,)")
+        max_iter = 100 * N + 10000 if max_iter is None else int(max_iter)
+        alpha = np.empty(N)
+        rho, obj, viol, ms = _ct.c_double(0.0), _ct.c_double(0.0), _ct.c_double(0.0), _ct.c_double(0.0)
+        nit, status = _ct.c_int64(0), _ct.c_int(0)
+        self._check(self._lib.gpry_svm_fit(self._h, _ptr(X), _ptr(finite), N, d, float(C), float(gamma), float(eps), max_iter,
+                                           _ptr(alpha), _ct.byref(rho), _ct.byref(obj), _ct.byref(viol), _ct.byref(nit),
+                                           _ct.byref(status), _ct.byref(ms)), "gpry_svm_fit")
+        return dict(alpha=alpha, rho=rho.value, objective=obj.value, violation=viol.value, n_iter=int(nit.value),
+                    status=int(status.value), device_ms=ms.value)
 
     def leave_out(self, groups):
         """Joint predictive of every group of training targets from the points outside it (gpry_leave_out).  ``groups``: a

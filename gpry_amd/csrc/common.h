@@ -250,6 +250,10 @@ struct gpry_ctx {
     uint8_t* dloo = nullptr;           // gpry_loo / gpry_leave_out: partial sums of the pass over V, partial Grams, outputs (bytes)
     int64_t loo_cap = 0;
     void* hloo = nullptr; int64_t hloo_cap = 0;    // gpry_loo: pinned landing place of its five output rows (bytes)
+    uint8_t* dsvm = nullptr;           // gpry_svm_fit: coordinate-major training set, alpha, gradient, labels, status block (bytes)
+    int64_t svm_cap = 0;
+    void* hsvm = nullptr; int64_t hsvm_cap = 0;    // gpry_svm_fit: pinned image of its upload (bytes)
+    int64_t opt_svm_iters = 4096;      // gpry_svm_fit: steps of one launch of the solver (the result does not depend on it)
 
     // host pinned staging
     void* hpin = nullptr; void* hpin_dev = nullptr; int64_t hpin_cap = 0;   // host / device view of the same buffer

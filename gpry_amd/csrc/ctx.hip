@@ -248,10 +248,11 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
                     ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc, ctx->dknn,
-                    ctx->dph, ctx->djoint, ctx->dloo};
+                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hloo) (void)hipHostFree(ctx->hloo);
+    if (ctx->hsvm) (void)hipHostFree(ctx->hsvm);
     if (ctx->hbres) (void)hipHostFree(ctx->hbres);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -322,6 +323,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("serve_idle_us", opt_serve_idle_us, 10, 1000000, (void)0),
     OPT_INT("mcmc_mapped", opt_mcmc_mapped, 0, 1, (void)0),
     OPT_INT("kb_rank", opt_kb_rank, 0, 1, (void)0),
+    OPT_INT("svm_iters_per_launch", opt_svm_iters, 1, BIG, (void)0),
 };
 #undef OPT_INT
 const OptionSpec* find_option(const char* key) {

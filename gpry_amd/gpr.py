@@ -580,6 +580,8 @@ class GaussianProcessRegressor(_RM, _BE):
         else:
             if fit_classifier:
                 thr_ = self.preprocessing_y.transform_scale(thr_keep)
+                if getattr(clf, "wants_device", False):      # SVM(trainer="device") trains through the model's context
+                    clf.bind(self.device)
                 pred = clf.fit(self.X_train_all_, self.y_train_all_, thr_)
                 assert np.array_equal(is_finite_all, pred), \
                     "Infinities classifier miss-classified at least 1 point."

@@ -161,6 +161,8 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *     "kb_rank" 0/1           1 (default): the Python mirror ranks an offer of the Kriging-believer pool through gpry_kb_rank
  *                             (one call: registration, batched Gram rows, the slot logic in C++); 0: its own loop over
  *                             gpry_kb_gram, one call per accepted point (the comparator; same picks, acq_cond to rounding)
+ *     "svm_iters_per_launch"  gpry_svm_fit: updates one launch of its solver makes at most (default 4096; the result does
+ *                             not depend on it)
  *     "predict_gates" 0/1     gpry_predict applies the gates of gpry_set_gates itself (default 0; the Python mirror sets 1)
  *     "predict_serve" 0/1     mean-only gpry_predict of <= 8 points is answered by a RESIDENT kernel (no launch per call;
  *                             default 1); "serve_idle_us" = how long that kernel waits for the next request before it
@@ -635,6 +637,42 @@ int gpry_predict_point(gpry_ctx* ctx, const double* x, int mask_bits, int want_k
  * kernel evaluates decision function and trust box next to the mean). */
 int gpry_set_gates(gpry_ctx* ctx, const double* sv, const double* coef, int64_t n_sv, double gamma,
                    double intercept, int positive_is_finite, const double* trust_bounds);
+
+/* ---- f4: training of that classifier on the device (svm_fit.hip) -------------------- */
+/* What gpry/svm.py:227 leaves to sklearn's SVC, i.e. to libsvm (svm.cpp: Solver::Solve, select_working_set,
+ * calculate_rho): the C-SVC dual of two classes with the RBF kernel k(a, b) = exp(-gamma |a - b|^2),
+ *   minimise 1/2 alpha^T Q alpha - sum alpha,  0 <= alpha_t <= C,  sum y_t alpha_t = 0,  Q_ts = y_t y_s k(x_t, x_s),
+ * y_t = +1 where finite[t] != 0 ("finite") and -1 elsewhere, by sequential minimal optimisation.  X: N x d row-major, in
+ * the coordinates the classifier is evaluated in (the TRANSFORMED ones of gpry_set_gates).  The gradient G = Q alpha - e is
+ * kept incrementally.  Per iteration, as libsvm's second-order rule (WSS 2):
+ *   i = argmax of -y_t G_t over I_up = {y_t = +1, alpha_t < C} U {y_t = -1, alpha_t > 0}, G_max its value;
+ *   j = argmin of -b^2 / a over t in I_low = {y_t = +1, alpha_t > 0} U {y_t = -1, alpha_t < C} with b = G_max + y_t G_t > 0,
+ *       a = 2 - 2 k(x_i, x_t), a non-positive a replaced by tau = 1e-12; G_min = min of -y_t G_t over I_low;
+ *   stop when G_max - G_min < eps; else libsvm's two-variable update of (alpha_i, alpha_j) with its four clipping branches
+ *   and G_t += Q_ti d alpha_i + Q_tj d alpha_j.
+ * Not libsvm's: no shrinking; a TIE in either selection goes to the SMALLEST index (libsvm's scan keeps the last one);
+ * and convergence is declared on a gradient without the rounding of the steps: when the stop test passes, G is recomputed
+ * from alpha (per point the rows with alpha > 0 in ascending index order) and the test repeated on it; if it fails there
+ * the iteration goes on from the recomputed gradient.  r^2 is the sum of the squared coordinate differences in coordinate
+ * order and the exponential is the routine of the device's gates, so the trained function and its evaluation by
+ * gpry_set_gates see the same kernel values.
+ * Outputs: alpha (N); *rho as calculate_rho (the mean of y_t G_t over the free variables 0 < alpha_t < C, the midpoint of
+ * the two bounds when there is none): decision(x) = sum_t y_t alpha_t k(x_t, x) - rho, finite <=> decision > 0, i.e.
+ * gpry_set_gates(sv = the rows with alpha > 0, coef = y alpha, intercept = -rho, positive_is_finite = 1); *objective =
+ * 1/2 sum alpha_t (G_t - 1); *violation = G_max - G_min of the last stop test; *n_iter the updates made; *status 0 =
+ * converged, 1 = max_iter updates were made first (alpha is feasible all the same; not an error).  rho, objective,
+ * violation, n_iter, status and device_ms may be NULL.
+ * One workgroup runs the solve (the method is serial), at most "svm_iters_per_launch" updates per launch (option, default
+ * 4096; a launch is finite, the state -- alpha, G, a status block -- stays in device memory between launches); kernel rows
+ * are kept in an on-demand cache of up to 32 MB in device memory (a cached row is the computed row bit for bit).  The bits
+ * of every output depend on (X, finite, C, gamma, eps, max_iter) alone: not on the context, on that option, or on what
+ * else the context holds.  Refuses (-1, gpry_last_error) N < 2, N > 8192, d > GPRY_MAX_DIM, labels of one class,
+ * non-finite X, and C, gamma or eps that are not positive and finite.  Stops the resident predict kernel first and
+ * touches nothing else: model, factor, sweep, gates, Kriging-believer session and samplers stay as they are.  Stage timer
+ * "svm_fit"; device_ms: device time of the call, copies included. */
+int gpry_svm_fit(gpry_ctx* ctx, const double* X, const uint8_t* finite, int64_t N, int64_t d, double C, double gamma,
+                 double eps, int64_t max_iter, double* alpha, double* rho, double* objective, double* violation,
+                 int64_t* n_iter, int* status, double* device_ms);
 
 /* ---- a8-a13: fused NORA sweep ----------------------------------------------------- */
 /* For all M candidates: mean, std (as gpry_predict), acq = LogExp.f(mean, std,
