@@ -359,6 +359,9 @@ int gpry_set_train(gpry_ctx* ctx, const double* X_, const double* y_, const doub
     if (d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "set_train: d=%d > GPRY_MAX_DIM=%d is not supported by this build", d, GPRY_MAX_DIM);
     if (!X_ || !y_ || !alpha) return gpry_fail(ctx, -1, "set_train: X_, y_ and alpha must not be NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // a candidate pool of rows of another width is not a resident pool of this model: a sweep with X == NULL would read
+    // it with the new stride
+    if (d != ctx->d) { ctx->sw_M = 0; ctx->sw_pruned = 0; }
     GPRY_TRY(ensure_capacity(ctx, N, d));
     hipStream_t st = ctx->stream;
     for (int k = 0; k < d; k++) {       // centre of the MFMA panel build (kernel_build.hip: cross_build_mfma_kernel)
@@ -427,6 +430,9 @@ int gpry_timing_get(gpry_ctx* ctx, const char* name, double* total_ms, int64_t* 
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_timing_get: ctx is NULL");
     // (not a timer: how often a batched objective halved its chunk after an out-of-memory answer since the context was created)
     if (name && !strcmp(name, "lml_batch_shrinks")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->batch_shrinks; return 0; }
+    // (not timers either: what ensure_capacity has allocated, in training rows and in padded columns)
+    if (name && !strcmp(name, "capacity_rows")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->cap; return 0; }
+    if (name && !strcmp(name, "capacity_cols")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->dp_cap; return 0; }
     timers_collect(ctx);
     auto it = ctx->timers.find(name);
     if (it == ctx->timers.end()) { if (total_ms) *total_ms = 0.0; if (count) *count = 0; return -1; }

@@ -271,7 +271,11 @@ static int srv_launch(gpry_ctx* ctx, SrvHost* s) {
     a.res = reinterpret_cast<SrvUnit*>(s->d + SrvHost::RES);
     a.state = reinterpret_cast<SrvUnit*>(s->d + SrvHost::STATE);
     a.dseq = s->dflags; a.dhdr = s->dflags + 1; a.dexit = s->dflags + 2; a.dx = s->dx;
+    // the kernel runs on a stream of its own: the launch on ctx->stream that puts the prediction factor's scaled
+    // coordinates back has to be through before it reads them (it used to meet a half-restored dXs now and then)
+    const bool restore = ctx->xs_foreign;
     GPRY_TRY(ensure_pred_xs(ctx));
+    if (restore) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     a.Xs = ctx->dXs; a.alpha_ = ctx->dalpha_;
     a.gen = ++s->gen;
     a.seq0 = s->seq - 1;

@@ -178,7 +178,9 @@ int gpry_ctx_get_option(gpry_ctx* ctx, const char* key, int64_t* value);
 
 /* ---- model state ------------------------------------------------------------------ */
 /* X_train_, y_train_, alpha = noise_^2 in the TRANSFORMED space, as assembled by
- * append_to_data (gpry/gpr.py:743-747).  X_ is N x d row-major. */
+ * append_to_data (gpry/gpr.py:743-747).  X_ is N x d row-major.  The factor and any Kriging-believer session are dropped;
+ * the resident candidate pool of gpry_sweep_logexp stays for a sweep with X == NULL under the new model unless d changes
+ * (rows of another width are no pool of this model: such a sweep is refused). */
 int gpry_set_train(gpry_ctx* ctx, const double* X_, const double* y_,
                    const double* alpha, int64_t N, int d);
 /* kernel_.theta = [log C, log l_1..l_d] (sklearn:kernels.py:734-747) */
@@ -849,7 +851,9 @@ int gpry_group_lml_batch(gpry_group* group, const double* thetas, int n_theta, i
  * ctx stream).  Known names: "kernel_build", "potrf", "trtri", "lauum", "lml_traces",
  * "cross_build", "sweep_gemm", "sweep_finish", "topk".  Returns <0 if unknown.
  * *count = launches accumulated since gpry_timing_reset.  "lml_batch_shrinks" is a counter, not a timer: *count = the times a
- * batched objective of this context halved its chunk after an out-of-memory answer (any other failure is returned to the caller). */
+ * batched objective of this context halved its chunk after an out-of-memory answer (any other failure is returned to the caller).
+ * "capacity_rows" / "capacity_cols" are sizes, not timers: *count = the training rows / padded columns the context's buffers hold
+ * (they grow with the largest model the context has seen and never shrink). */
 int gpry_timing_reset(gpry_ctx* ctx);
 int gpry_timing_get(gpry_ctx* ctx, const char* name, double* total_ms, int64_t* count);
 /* Raw micro-benchmarks used by bench.py to quote measured peaks beside the spec:
