@@ -17,6 +17,7 @@ MASK_CLASSIFIED_INF = 1
 MASK_OUTSIDE_TRUST = 2
 
 KERNEL_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3}
+KERNEL_WHITE = 0x10    # GPRY_KERNEL_WHITE: or-ed into a kernel id, theta gains log w as its last entry
 
 
 class GpryAffine(C.Structure):
@@ -308,9 +309,17 @@ class Device:
         self.N, self.d = N, d
 
     def set_theta(self, kernel_id, theta):
-        theta = _f64(theta, (self.d + 1,))
+        """``kernel_id``: 0..3, or-ed with ``KERNEL_WHITE`` for a model with a fitted white term; ``theta`` is then
+        ``[log C, log l_1 .. l_d, log w]``, and so is every theta / gradient of ``lml`` and ``lml_batch``."""
+        white = bool(int(kernel_id) & KERNEL_WHITE)
+        theta = _f64(theta, (self.d + 1 + white,))
         self._check(self._lib.gpry_set_theta(self._h, int(kernel_id), _ptr(theta)),
                     "gpry_set_theta")
+        self.white = white
+
+    @property
+    def n_theta(self):
+        return self.d + 1 + int(getattr(self, "white", False))
 
     def set_affine(self, x_lo=None, x_span=None, y_mean=0.0, y_std=1.0, clip_hi=np.inf):
         tf = make_affine(x_lo, x_span, y_mean, y_std, clip_hi)
@@ -366,8 +375,8 @@ class Device:
         # persistent argument buffers: at small N an evaluation takes 30-60 us, of which building two arrays and four
         # ctypes pointers per call used to be 3-4
         buf = getattr(self, "_lml_buf", None)
-        if buf is None or len(buf[0]) != self.d + 1:
-            th, gr = np.zeros(self.d + 1), np.zeros(self.d + 1)
+        if buf is None or len(buf[0]) != self.n_theta:
+            th, gr = np.zeros(self.n_theta), np.zeros(self.n_theta)
             val, info = C.c_double(0.0), C.c_int(0)
             buf = self._lml_buf = (th, gr, C.c_void_p(th.ctypes.data), C.c_void_p(gr.ctypes.data), val, info,
                                    C.byref(val), C.byref(info))
@@ -385,8 +394,8 @@ class Device:
         without gradients).  N <= 128, d <= 16: one launch, one workgroup per theta, the bits of single ``lml`` calls."""
         thetas = _f64(np.atleast_2d(thetas))
         B, w = thetas.shape
-        if w != self.d + 1:
-            raise ValueError(f"expected {self.d + 1} columns, got {w}")
+        if w != self.n_theta:
+            raise ValueError(f"expected {self.n_theta} columns, got {w}")
         lml = np.empty(B)
         grad = np.zeros((B, w)) if eval_gradient else None
         info = np.zeros(B, dtype=np.int32)
@@ -1108,6 +1117,8 @@ class DeviceGroup:
         N, d = X_.shape
         y_ = _f64(y_, (N,))
         alpha = _f64(np.broadcast_to(alpha, (N,)))
+        if int(kernel_id) & KERNEL_WHITE:
+            raise NotImplementedError("a device group does not carry the white term (WhiteKernel) of the kernel yet")
         theta = _f64(theta, (d + 1,))
         tf = make_affine(*affine) if affine is not None else None
         info = C.c_int(0)

@@ -100,7 +100,7 @@ static int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* inf
 // evaluation (gpry_ctx::bn), at the bn thetas whose [C, l...] rows sit in the arena: covariance build, factor, V = L^-1,
 // alpha, log-det and quadratic form, and with want_grad K^-1 = V^T V and the traces.  The last kernel writes results and
 // factorisation status into `dres` (device view of pinned host memory; theta tb at row tb of GPRY_BRES_STRIDE doubles).
-constexpr int RES_INFO = 2 + 1 + GPRY_MAX_DIM;      // [logdet/2, quad, grad (1 + d) ..., info0, info1]
+constexpr int RES_INFO = 2 + GPRY_THETA_MAX;      // [logdet/2, quad, grad (1 + d, + 1 with a white term) ..., info0, info1]
 static_assert(RES_INFO + 3 <= GPRY_BRES_STRIDE, "result row too short");
 static int lml_chain(gpry_ctx* ctx, int want_grad, double* dres) {
     GPRY_TRY(build_factor(ctx, ctx->dW, ctx->dW2, ctx->dW3, nullptr));
@@ -137,7 +137,7 @@ static int batch_layout(gpry_ctx* ctx, BatchLayout* L) {
     GPRY_TRY(factor_chain_slices(ctx, Np, &slices));
     const int DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
     const int64_t nb = Np / 64, ntile = nb * (nb + 1) / 2;
-    const int64_t p1 = ((Np + 255) / 256) * Np, p2 = ntile * (DPsel + 1);       // solve_alpha, launch_lml_traces
+    const int64_t p1 = ((Np + 255) / 256) * Np, p2 = ntile * (DPsel + 2);       // solve_alpha, launch_lml_traces
     int64_t o = 0;
     auto take = [&](int64_t n) { const int64_t at = o; o += round_up(n, 32); return at; };      // 256-byte pieces
     L->w = take(nn); L->w2 = take(nn); L->w3 = take(nn);
@@ -145,7 +145,7 @@ static int batch_layout(gpry_ctx* ctx, BatchLayout* L) {
     L->vec = take(8 * Np + 4096);
     L->part_cap = p1 > p2 ? p1 : p2; L->part = take(L->part_cap);
     L->split_cap = (int64_t)slices * nn; L->split = take(L->split_cap > 0 ? L->split_cap : 1);
-    L->par = take(1 + GPRY_MAX_DIM);
+    L->par = take(GPRY_BPAR_ROW);
     L->info = take(8);                      // 16 status / arrival words
     L->stride = o + 32 * 9;                 // not a multiple of a large power of two: consecutive sets start on different channels
     return 0;
@@ -175,7 +175,7 @@ static bool lml_batch_usable(const gpry_ctx* ctx) {
     return ctx->N > 0 && ctx->Np > 128 && ctx->Np <= ctx->opt_lml_batch && ctx->d <= 32 && ctx->opt_chol == 0;
 }
 static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad, double* lml, double* grad, int* info) {
-    const int w = ctx->d + 1;
+    const int w = ctx_ntheta(ctx);
     for (int64_t i = 0; i < B * w; i++)
         if (!isfinite(thetas[i])) return gpry_fail(ctx, -1, "theta[%d] is not finite", (int)(i % w));
     GPRY_TRY(serve_stop(ctx));
@@ -185,7 +185,7 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
         gpry_ctx* c;
         double *dW, *dW2, *dW3, *dXs, *dvec, *dpart, *dsplit; int* dinfo; hipStream_t stream;
         int64_t part_cap, split_cap; bool xs_foreign, have_theta;
-        double theta[1 + GPRY_MAX_DIM];
+        double theta[GPRY_THETA_MAX];
         explicit Scope(gpry_ctx* ctx) : c(ctx), dW(ctx->dW), dW2(ctx->dW2), dW3(ctx->dW3), dXs(ctx->dXs), dvec(ctx->dvec), dpart(ctx->dpart),
                                         dsplit(ctx->dsplit), dinfo(ctx->dinfo), stream(ctx->stream), part_cap(ctx->part_cap), split_cap(ctx->split_cap),
                                         xs_foreign(ctx->xs_foreign), have_theta(ctx->have_theta) {
@@ -232,7 +232,7 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
     // a failed allocation (another context took the memory in between) halves the chunk; below `min_chunk` sets the thetas go
     // through one after another instead of the fit failing (latency schedule).  Only an out-of-memory answer is retried.
     for (;;) {
-        const int rc = ensure_batch_buffers(ctx, chunk * L.stride, (int64_t)sizeof(double) * chunk * (GPRY_BRES_STRIDE + 1 + GPRY_MAX_DIM));
+        const int rc = ensure_batch_buffers(ctx, chunk * L.stride, (int64_t)sizeof(double) * chunk * (GPRY_BRES_STRIDE + GPRY_BPAR_ROW));
         if (rc == 0) break;
         if (rc != 2) return rc;             // anything but "out of memory" is the caller's to see
         ctx->batch_shrinks++;
@@ -261,17 +261,18 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
         const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
         for (int64_t b = 0; b < nb; b++) {
             const double* th = thetas + (b0 + b) * w;
-            double* row = hpar + b * (1 + GPRY_MAX_DIM);
+            double* row = hpar + b * GPRY_BPAR_ROW;
             for (int k = 0; k <= GPRY_MAX_DIM; k++) row[k] = 1.0;
             row[0] = exp(th[0]);                                     // as make_kp / make_ap for one evaluation
             for (int k = 0; k < ctx->d; k++) row[1 + k] = exp(th[1 + k]);
+            row[GPRY_BPAR_WHITE] = ctx->white ? exp(th[1 + ctx->d]) : 0.0;
             hres[b * GPRY_BRES_STRIDE + RES_INFO] = -1.0; hres[b * GPRY_BRES_STRIDE + RES_INFO + 1] = -1.0;     // "not written"
         }
         for (int k = 0; k < w; k++) ctx->theta[k] = thetas[b0 * w + k];      // (the launchers read the sizes, not these, in a batch)
         // test hook ("panel_debug" bit 7): every scratch set starts as NaNs -- a result that depended on what a set held before shows
         if (ctx->opt_panel_debug & 128) HIP_TRY(ctx, hipMemsetAsync(a0, 0xFF, sizeof(double) * (size_t)(nb * L.stride), main_stream));
-        HIP_TRY(ctx, hipMemcpy2DAsync(a0 + L.par, sizeof(double) * L.stride, hpar, sizeof(double) * (1 + GPRY_MAX_DIM),
-                                      sizeof(double) * (1 + GPRY_MAX_DIM), (size_t)nb, hipMemcpyHostToDevice, main_stream));
+        HIP_TRY(ctx, hipMemcpy2DAsync(a0 + L.par, sizeof(double) * L.stride, hpar, sizeof(double) * GPRY_BPAR_ROW,
+                                      sizeof(double) * GPRY_BPAR_ROW, (size_t)nb, hipMemcpyHostToDevice, main_stream));
         // Stream groups (throughput schedule): the panel chain of the Cholesky is one workgroup's latency per step whatever the
         // number of thetas, and between two products of a group the GPU drains.  With the thetas dealt over G streams the host
         // queues group after group; the groups run out of step by themselves and one's panel steps sit underneath the others' GEMMs.
@@ -395,8 +396,8 @@ int gpry_factorize(gpry_ctx* ctx, int* info) {
     // The optimiser's last objective evaluation is normally at the theta it returns: its factor
     // (L in dW, V in dW2; same kernels, same inputs => the bits a fresh factorisation would give)
     // is adopted by swapping buffers instead of factorising again.
-    bool hit = ctx->opt_lml_cache && ctx->lml_cache && ctx->lml_kernel_id == ctx->kernel_id;
-    for (int k = 0; hit && k <= ctx->d; k++) hit = ctx->lml_theta[k] == ctx->theta[k];
+    bool hit = ctx->opt_lml_cache && ctx->lml_cache && ctx->lml_kernel_id == (ctx->kernel_id | (ctx->white ? GPRY_KERNEL_WHITE : 0));
+    for (int k = 0; hit && k < ctx_ntheta(ctx); k++) hit = ctx->lml_theta[k] == ctx->theta[k];
     ctx->lml_cache = false;
     if (hit) {
         std::swap(ctx->dA, ctx->dW);
@@ -443,14 +444,15 @@ int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, dou
     GPRY_TRY(serve_stop(ctx));
     if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
     if (!theta || !lml || (want_grad && !grad)) return gpry_fail(ctx, -1, "lml: theta, lml and (with want_grad) grad must not be NULL");
-    for (int k = 0; k <= ctx->d; k++)
+    const int nth = ctx_ntheta(ctx);      // 1 + d, one more (log w) for a model set with GPRY_KERNEL_WHITE
+    for (int k = 0; k < nth; k++)
         if (!isfinite(theta[k])) return gpry_fail(ctx, -1, "theta[%d] is not finite", k);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // evaluate at `theta` without disturbing the prediction factor (dA, dV, dalpha_)
-    double saved[1 + GPRY_MAX_DIM];
+    double saved[GPRY_THETA_MAX];
     bool had = ctx->have_theta;
     memcpy(saved, ctx->theta, sizeof(saved));
-    for (int k = 0; k <= ctx->d; k++) ctx->theta[k] = theta[k];
+    for (int k = 0; k < nth; k++) ctx->theta[k] = theta[k];
     ctx->have_theta = true;
     // One stream synchronisation per evaluation: the factorisation status is not waited for in the
     // middle (every kernel behind a failed factorisation either exits on *dinfo != 0 or works on
@@ -464,7 +466,7 @@ int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, dou
     // N <= 128, d <= 16: the whole evaluation in one launch of one workgroup (lml_small.hip); it leaves no factor in
     // dW / dW2 and does not touch the scaled coordinates of the prediction factor
     bool fused = false;
-    double fhost[2 + 1 + GPRY_MAX_DIM];
+    double fhost[2 + GPRY_THETA_MAX];
     int finfo = 0;
     if (rc == 0 && ctx->opt_lml_small && ctx->opt_chol == 0) {
         StageScope s(ctx, "lml_small");
@@ -479,10 +481,10 @@ int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, dou
     // the scaled training coordinates belong to the prediction factor: whoever needs them next restores them
     // (ensure_pred_xs; an optimiser's next evaluation does not)
     if (rescaled && had && ctx->factor_valid) ctx->xs_foreign = true;
-    double host[2 + 1 + GPRY_MAX_DIM];
+    double host[2 + GPRY_THETA_MAX];
     int hinfo[2] = {0, 0};
     if (rc == 0 && fused) {
-        memcpy(host, fhost, sizeof(double) * (2 + (want_grad ? ctx->d + 1 : 0)));
+        memcpy(host, fhost, sizeof(double) * (2 + (want_grad ? nth : 0)));
         hinfo[0] = finfo;
     } else if (rc == 0) {
         // (Polling the status word in the mapped buffer instead of waiting for the stream returns 15 us earlier and is
@@ -493,7 +495,7 @@ int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, dou
         if (e != hipSuccess) rc = gpry_fail(ctx, -2, "lml: %s", hipGetErrorString(e));
         else if (hres[RES_INFO] < 0.0) rc = gpry_fail(ctx, -2, "lml: the evaluation did not deliver its status");
         else {
-            memcpy(host, hres, sizeof(double) * (2 + (want_grad ? ctx->d + 1 : 0)));
+            memcpy(host, hres, sizeof(double) * (2 + (want_grad ? nth : 0)));
             hinfo[0] = (int)hres[RES_INFO]; hinfo[1] = (int)hres[RES_INFO + 1];
             if (panel_timed_out((int)hres[RES_INFO + 2])) rc = panel_timeout_error(ctx, (int)hres[RES_INFO + 2]);
         }
@@ -502,18 +504,18 @@ int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, dou
     ctx->lml_cache = (rc == 0 && inf == 0 && !fused);
     if (ctx->lml_cache) {
         memset(ctx->lml_theta, 0, sizeof(ctx->lml_theta));
-        for (int k = 0; k <= ctx->d; k++) ctx->lml_theta[k] = theta[k];
-        ctx->lml_kernel_id = ctx->kernel_id;
+        for (int k = 0; k < nth; k++) ctx->lml_theta[k] = theta[k];
+        ctx->lml_kernel_id = ctx->kernel_id | (ctx->white ? GPRY_KERNEL_WHITE : 0);
     }
     if (rc) return rc;
     if (info) *info = inf;
     if (inf != 0) {   // sklearn:_gpr.py:586-589
         *lml = -INFINITY;
-        if (want_grad && grad) for (int k = 0; k <= ctx->d; k++) grad[k] = 0.0;
+        if (want_grad && grad) for (int k = 0; k < nth; k++) grad[k] = 0.0;
         return 0;
     }
     *lml = -0.5 * host[1] - host[0] - 0.5 * (double)ctx->N * log(2.0 * M_PI);
-    if (want_grad && grad) for (int k = 0; k <= ctx->d; k++) grad[k] = host[2 + k];
+    if (want_grad && grad) for (int k = 0; k < nth; k++) grad[k] = host[2 + k];
     return 0;
 }
 
@@ -525,7 +527,7 @@ int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_lml_batch: ctx is NULL");
     if (B <= 0) return 0;
     if (!thetas || !lml || (want_grad && !grad)) return gpry_fail(ctx, -1, "lml_batch: thetas, lml and (with want_grad) grad must not be NULL");
-    const int w = ctx->d + 1;
+    const int w = ctx_ntheta(ctx);
     bool fused = ctx->N > 0 && ctx->opt_lml_small && ctx->opt_chol == 0 && ctx->Np == 128 && ctx->d <= 16 && B <= 256;
     for (int64_t i = 0; fused && i < B * w; i++) fused = isfinite(thetas[i]);
     // (throughput schedule: a single theta goes through the chain of the many as well -- its result must not depend on B)
@@ -543,11 +545,12 @@ int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad
     }
     GPRY_TRY(serve_stop(ctx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<double> par((size_t)B * 17, 1.0), out((size_t)B * (2 + 1 + GPRY_MAX_DIM), 0.0);
+    std::vector<double> par((size_t)B * 18, 1.0), out((size_t)B * (2 + 1 + GPRY_MAX_DIM), 0.0);
     std::vector<int> inf((size_t)B, 0);
     for (int64_t b = 0; b < B; b++) {
-        par[b * 17] = exp(thetas[b * w]);                                   // as make_kp / make_ap for one evaluation
-        for (int k = 0; k < ctx->d; k++) par[b * 17 + 1 + k] = exp(thetas[b * w + 1 + k]);
+        par[b * 18] = exp(thetas[b * w]);                                   // as make_kp / make_ap for one evaluation
+        for (int k = 0; k < ctx->d; k++) par[b * 18 + 1 + k] = exp(thetas[b * w + 1 + k]);
+        par[b * 18 + 17] = ctx->white ? exp(thetas[b * w + 1 + ctx->d]) : 0.0;
     }
     {
         StageScope s(ctx, "lml_small");
@@ -674,7 +677,7 @@ int gpry_predict(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* mask,
         GPRY_TRY(launch_predict_small_std(ctx, (const double*)hd, (int)M, ctx->dG, (double*)(hd + xb),
                                           (double*)(hd + xb) + M * nmb));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const double C = exp(ctx->theta[0]);
+        const double C = ctx_prior_var(ctx);       // C + w for a model with a white term
         for (int64_t m = 0; m < M; m++) {
             double mu_ = 0.0, ss = 0.0;
             for (int64_t b = 0; b < nmb; b++) mu_ += hm[m * nmb + b];
@@ -820,7 +823,7 @@ int gpry_predict_point(gpry_ctx* ctx, const double* x, int mask_bits, int want_k
     double y = fmin(mu_ * ctx->tf.y_std + ctx->tf.y_mean, ctx->tf.clip_hi);
     if (mask_bits) y = -INFINITY;
     *mean = y;
-    double var = exp(ctx->theta[0]) - ss;
+    double var = ctx_prior_var(ctx) - ss;
     if (var < 0.0) var = 0.0;
     double sd = sqrt(var) * ctx->tf.y_std;
     if (mask_bits & GPRY_MASK_CLASSIFIED_INF) sd = 0.0;
@@ -929,7 +932,7 @@ int gpry_predict_grad_batch(gpry_ctx* ctx, const double* X, int64_t m, int want_
         hm = hmv.data(); hs = hsv.data(); hg = hgv.data();
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    const double C = exp(ctx->theta[0]);
+    const double C = ctx_prior_var(ctx);
     for (int64_t i = 0; i < m; i++) {
         if (mean) {
             double mu_ = 0.0;
@@ -1102,7 +1105,7 @@ int gpry_kb_register(gpry_ctx* ctx, const double* X, int64_t m, int64_t* first, 
     GPRY_TRY(gemm_f64_launch(ctx, g, true, true, EPI_STORE));
     if (var0) {
         hipLaunchKernelGGL(kb_var0_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, ctx->dU, Np, ctx->kb_n, m,
-                           Np, exp(ctx->theta[0]), ctx->dkbout);
+                           Np, ctx_prior_var(ctx), ctx->dkbout);      // (C + w for a model with a white term)
         HIP_TRY(ctx, hipMemcpyAsync(var0, ctx->dkbout, sizeof(double) * m, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -11,6 +11,9 @@
 
 #include "../../include/gpry_hip.h"
 
+#define GPRY_THETA_MAX (2 + GPRY_MAX_DIM)      // [log C, log l_1 .. l_d, log w]
+#define GPRY_BPAR_ROW (2 + GPRY_MAX_DIM)       // parameter row of a batched evaluation: [C, l_1 .. l_32, w]
+#define GPRY_BPAR_WHITE (1 + GPRY_MAX_DIM)
 #define GPRY_TILE 128       // GEMM workgroup tile and padding quantum of N
 #define GPRY_NB 64          // Cholesky / trtri base block
 
@@ -48,14 +51,15 @@ struct gpry_ctx {
     // training set (transformed space)
     int64_t N = 0, Np = 0, cap = 0;  // cap: allocated padded size
     int d = 0, dpad = 0, dp_cap = 0;   // dp_cap: row width the X buffers were allocated for
-    int kernel_id = GPRY_RBF;
+    int kernel_id = GPRY_RBF;           // the stationary kernel alone (GPRY_KERNEL_WHITE is kept in `white`)
+    bool white = false;                 // the model has a fitted white term w: theta[1 + d] = log w (ctx_white below)
     bool have_theta = false, factor_valid = false;
-    double theta[1 + GPRY_MAX_DIM] = {0};
+    double theta[GPRY_THETA_MAX] = {0};
     gpry_affine tf;
     // factor of the last successful gpry_lml evaluation: still sitting in dW (L) / dW2 (V)
     bool lml_cache = false;
-    int lml_kernel_id = -1;
-    double lml_theta[1 + GPRY_MAX_DIM] = {0};
+    int lml_kernel_id = -1;             // (with the white flag)
+    double lml_theta[GPRY_THETA_MAX] = {0};
     int opt_lml_cache = 1;
     unsigned long long lml_seq = 0;     // stamp of the last single-launch evaluation
     int opt_lml_small = 1;       // N <= 128, d <= 16: LML + gradient in one launch of one workgroup (lml_small.hip)
@@ -67,7 +71,7 @@ struct gpry_ctx {
     // (bset below).  Outside a batched evaluation bn = 1, bstride = 0, bpar = NULL and nothing changes.
     int bn = 1;
     int64_t bstride = 0;
-    const double* bpar = nullptr;      // device, set 0: [C, l_1 .. l_d] as the host computes them for one evaluation
+    const double* bpar = nullptr;      // device, set 0: [C, l_1 .. l_d] as the host computes them for one evaluation, w at GPRY_BPAR_WHITE
     double* barena = nullptr; int64_t barena_cap = 0;     // doubles
     void* hbres = nullptr; void* hbres_dev = nullptr; int64_t hbres_cap = 0;   // results of a batch (pinned, device-mapped)
     int64_t opt_lml_batch = 4096;      // largest Np whose gpry_lml_batch runs as one chain (0: thetas one after another); measured
@@ -133,7 +137,7 @@ struct gpry_ctx {
     int opt_cross_mfma = 1;    // 1 (default): the sweep's cross-kernel panel takes its distances from the matrix pipe
     double alpha_l2 = -1.0;    // ||alpha_||_2 of the prediction factor (fetched when the panel form is chosen; < 0: not yet)
     double alpha_l1 = 0.0;     // ||alpha_||_1, fetched with it
-    double noise_min = 0.0;    // smallest entry of the noise vector `alpha` of the training rows (set_train, append_rows): lambda_min(K) >= it
+    double noise_min = 0.0;    // smallest entry of the noise vector `alpha` of the training rows (set_train, append_rows): lambda_min(K) >= it + w
     int panel_form = 0;        // cross-kernel panel of the last sweep / panel predict: 0 none yet, 1 matrix pipe, 2 difference form, 3 small-batch kernel, 4 hybrid (matrix pipe, near pairs from the coordinates)
     int opt_cross_hybrid = 1;  // 1: a model that fails the gate of the matrix-pipe form because of SHORT length scales takes the hybrid form instead of the difference form
     double panel_est[4] = {0, 0, 0, 2.5e-7};   // its error estimates: mean (l2, gated), mean (l1, worst case), variance / C (gated), the gate
@@ -228,7 +232,8 @@ struct gpry_ctx {
         int64_t v_cap = 0, a_cap = 0, xs_cap = 0, x_cap = 0;
         int64_t N = 0, Np = 0;
         int d = 0, dpad = 0, kernel_id = 0;
-        double theta[1 + GPRY_MAX_DIM] = {0};
+        bool white = false;
+        double theta[GPRY_THETA_MAX] = {0};
         gpry_affine tf;
         double xcenter[GPRY_MAX_DIM] = {0};
         bool xs_foreign = false;
@@ -263,7 +268,20 @@ struct gpry_ctx {
 
 extern thread_local char g_last_error[1024];
 
+// the white term of the model (GPRY_KERNEL_WHITE): w, the number of theta entries, the prior variance C + w of a new point
+static inline double ctx_white(const gpry_ctx* ctx) { return ctx->white ? exp(ctx->theta[1 + ctx->d]) : 0.0; }
+static inline int ctx_ntheta(const gpry_ctx* ctx) { return ctx->d + 1 + (ctx->white ? 1 : 0); }
+static inline double ctx_prior_var(const gpry_ctx* ctx) {
+    const double C = exp(ctx->theta[0]);
+    return ctx->white ? C + exp(ctx->theta[1 + ctx->d]) : C;
+}
+
 int gpry_fail(gpry_ctx* ctx, int code, const char* fmt, ...);
+// entry points that do not carry the white term yet: an error that names it, never a silently wrong variance
+static inline int refuse_white(gpry_ctx* ctx, const char* who) {
+    if (!ctx->white) return 0;
+    return gpry_fail(ctx, -1, "%s: a model with a white term (WhiteKernel, GPRY_KERNEL_WHITE) is not supported by this entry point", who);
+}
 
 #define HIP_TRY(ctx, expr)                                                          \
     do {                                                                            \

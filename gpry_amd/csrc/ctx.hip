@@ -395,14 +395,18 @@ int gpry_set_train(gpry_ctx* ctx, const double* X_, const double* y_, const doub
 int gpry_set_theta(gpry_ctx* ctx, int kernel_id, const double* theta) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_set_theta: ctx is NULL");
     GPRY_TRY(serve_stop(ctx));
-    if (kernel_id < 0 || kernel_id > 3) return gpry_fail(ctx, -1, "unknown kernel id %d", kernel_id);
+    const bool white = (kernel_id & GPRY_KERNEL_WHITE) != 0;
+    const int kid = kernel_id & ~GPRY_KERNEL_WHITE;
+    if (kernel_id < 0 || kid > 3) return gpry_fail(ctx, -1, "unknown kernel id %d", kernel_id);
     if (ctx->d <= 0) return gpry_fail(ctx, -1, "set_theta before set_train");
     if (!theta) return gpry_fail(ctx, -1, "set_theta: theta is NULL");
-    ctx->kernel_id = kernel_id;
-    for (int k = 0; k <= ctx->d; k++) {
+    const int nth = ctx->d + 1 + (white ? 1 : 0);
+    for (int k = 0; k < nth; k++)
         if (!isfinite(theta[k])) return gpry_fail(ctx, -1, "theta[%d] is not finite", k);
-        ctx->theta[k] = theta[k];
-    }
+    ctx->kernel_id = kid;
+    ctx->white = white;
+    for (int k = 0; k < nth; k++) ctx->theta[k] = theta[k];
+    if (!white) ctx->theta[1 + ctx->d] = 0.0;
     ctx->have_theta = true;
     ctx->factor_valid = false;
     ctx->kb_n = 0;

@@ -157,6 +157,8 @@ const char* gpry_group_last_error(gpry_group* g) { return g ? g->err : g_last_er
 int gpry_group_set_model(gpry_group* g, const double* X_, const double* y_, const double* alpha, int64_t N, int d,
                          int kernel_id, const double* theta, const gpry_affine* tf, int* info) {
     if (!g) return group_fail(nullptr, -1, "gpry_group_set_model: group is NULL");
+    if (kernel_id & GPRY_KERNEL_WHITE)
+        return group_fail(g, -1, "gpry_group_set_model: a model with a white term (WhiteKernel, GPRY_KERNEL_WHITE) is not supported by the device group");
     if (info) *info = 0;
     std::vector<int> infos(g->members.size(), 0);
     GPRY_TRY(for_members(g, [&](int i) -> int {

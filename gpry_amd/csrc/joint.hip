@@ -275,6 +275,7 @@ int gpry_predict_cov(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* m
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_predict_cov: ctx is NULL");
     GPRY_TRY(serve_stop(ctx));
     GPRY_TRY(require_model(ctx, true));
+    GPRY_TRY(refuse_white(ctx, "gpry_predict_cov"));
     if (!cov) return gpry_fail(ctx, -1, "gpry_predict_cov: cov is NULL");
     GPRY_TRY(joint_check(ctx, "gpry_predict_cov", X, m));
     NsTimer tm;
@@ -302,6 +303,7 @@ int gpry_sample_joint(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* 
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_sample_joint: ctx is NULL");
     GPRY_TRY(serve_stop(ctx));
     GPRY_TRY(require_model(ctx, true));
+    GPRY_TRY(refuse_white(ctx, "gpry_sample_joint"));
     if (!Y) return gpry_fail(ctx, -1, "gpry_sample_joint: Y is NULL");
     if (S < 1 || S > JOINT_MAX_S) return gpry_fail(ctx, -1, "gpry_sample_joint: S = %lld, need 1 <= S <= %d", (long long)S, JOINT_MAX_S);
     if (jitter != jitter || jitter == INFINITY) return gpry_fail(ctx, -1, "gpry_sample_joint: jitter = %g", jitter);

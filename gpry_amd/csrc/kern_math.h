@@ -8,6 +8,8 @@ struct KernParams {
     double C;
     int d, dpad, has_aff;
     int64_t N;
+    double white;       // w of a model with GPRY_KERNEL_WHITE (on the diagonal of the training matrix: C + (noise + w))
+    int white_on;       // 0: no white term -- the diagonal keeps the expression it had, C + noise
 };
 struct AffParams {
     double ls[GPRY_MAX_DIM];     // length scales (unused slots = 1)
@@ -142,6 +144,7 @@ static KernParams make_kp(gpry_ctx* ctx) {
     kp.C = exp(ctx->theta[0]);
     kp.d = ctx->d; kp.dpad = ctx->dpad;
     kp.has_aff = ctx->tf.has_x_affine; kp.N = ctx->N;
+    kp.white = ctx_white(ctx); kp.white_on = ctx->white ? 1 : 0;
     return kp;
 }
 static AffParams make_ap(gpry_ctx* ctx, bool use_affine) {

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256, 6) void kernel_train_q_kernel(
     // batched launch (gpry_ctx::bn): theta blockIdx.z builds its own K from its own scaled coordinates and constant
     const double* __restrict__ Xs = bset(Xs_, (int)blockIdx.z, bstride);
     double* __restrict__ K = bset(K_, (int)blockIdx.z, bstride);
-    if (bpar) kp.C = bset(bpar, (int)blockIdx.z, bstride)[0];
+    if (bpar) { const double* bp = bset(bpar, (int)blockIdx.z, bstride); kp.C = bp[0]; kp.white = bp[GPRY_BPAR_WHITE]; }
     // Coordinates of the 64 rows and the 64 columns, row-major as they lie in memory, row stride dp + 2 doubles: staged with
     // 16-byte loads and stores (whole 128-byte lines in, no bank conflicts), read back as double2 over k -- the rows of the
     // eight `ly` (columns of the eight `lx`) are 288 bytes apart = 8 banks, a conflict-free ds_read_b128.  (Round 3 staged
@@ -159,7 +159,12 @@ __global__ __launch_bounds__(256, 6) void kernel_train_q_kernel(
                 if (special) {
                     const int64_t i = (int64_t)bi * TS + r0 + 16 * ap + a2;
                     const int64_t j = (int64_t)bj * TS + c0 + 16 * (b >> 1) + (b & 1);
-                    if (i == j) x = kp.C + (add_noise ? noise[i < kp.N ? i : 0] : 0.0);
+                    if (i == j) {
+                        // (a white term w sits on the diagonal with or without alpha: kernel_(X) has it; in that association,
+                        // so that the matrix is to the bit that of the model whose alpha is alpha + w)
+                        if (kp.white_on) x = kp.C + ((add_noise ? noise[i < kp.N ? i : 0] : 0.0) + kp.white);
+                        else x = kp.C + (add_noise ? noise[i < kp.N ? i : 0] : 0.0);
+                    }
                     if (i >= kp.N || j >= kp.N) x = (i == j) ? 1.0 : 0.0;   // identity padding
                 }
                 v[a2][b] = x;
@@ -217,7 +222,7 @@ __global__ __launch_bounds__(256) void kernel_rows_kernel(const double* __restri
         double r2 = 0.0;
         for (int c = 0; c < kp.dpad; c++) { const double df = xa[c] - xj[c]; r2 = fma(df, df, r2); }
         v = kp.C * corr_r2<KID>(r2);            // the arithmetic of the training build (kernel_train_q_kernel)
-        if (j == row0 + a) v = kp.C + noise[j];
+        if (j == row0 + a) v = kp.white_on ? kp.C + (noise[j] + kp.white) : kp.C + noise[j];
         if (j >= row0) { Cb[a * 64 + (int)(j - row0)] = v; v = 0.0; }
     }
     Bk[idx] = v;
@@ -727,6 +732,7 @@ __global__ __launch_bounds__(256) void lml_traces_kernel(
     const double* __restrict__ alpha = bset(alpha_, (int)blockIdx.z, bstride);
     double* __restrict__ part = bset(part_, (int)blockIdx.z, bstride);
     if (bpar) kp.C = bset(bpar, (int)blockIdx.z, bstride)[0];
+    // (the white entry needs no w here: the tiles leave sum_i W_ii, reduce_traces_kernel multiplies)
     // coordinates of the 64 rows and the 64 columns, [k][row] with a row stride of 66 doubles: with 64 the sixteen k of a row --
     // neighbouring lanes of the staging loop -- fell into ONE pair of LDS banks (a 16-way conflict on every write, in a prologue
     // that all resident workgroups run at the same time); 66 spreads them over 32 banks and keeps the 16-byte reads aligned
@@ -854,7 +860,20 @@ __global__ __launch_bounds__(256) void lml_traces_kernel(
     if (t <= DP) {
         double s = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
         if (bi != bj) s *= 2.0;
-        part[(int64_t)blockIdx.x * (DP + 1) + t] = s;
+        part[(int64_t)blockIdx.x * (DP + 2) + t] = s;
+    }
+    // A model with a white term: d K / d log w = w I, its entry needs tr W = sum_i (alpha_i^2 - K^-1_ii).  The diagonal tiles
+    // form their 64 terms here, behind the pair loops (nothing more lives through those), and add them in a fixed butterfly;
+    // off the diagonal the column is 0 (without a white term nobody reads it).  reduce_traces_kernel multiplies by w / 2.
+    if (kp.white_on && wave == 1) {
+        double v = 0.0;
+        if (bi == bj) {
+            const int64_t i = (int64_t)bi * 64 + lane;
+            if (i < kp.N) v = ai[lane] * ai[lane] - Kinv[i * ld + i];
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) part[(int64_t)blockIdx.x * (DP + 2) + DP + 1] = v;
     }
 }
 
@@ -862,17 +881,22 @@ __global__ __launch_bounds__(256) void lml_traces_kernel(
 __global__ __launch_bounds__(256) void reduce_traces_kernel(const double* __restrict__ part_, int64_t ntile,
                                                             int stride, double* __restrict__ out_,
                                                             const int* __restrict__ info_, const double* __restrict__ lq_,
-                                                            double* __restrict__ host_res, int info_at, int64_t bstride) {
+                                                            double* __restrict__ host_res, int info_at, int64_t bstride,
+                                                            int nplain, int white_col, double white, const double* __restrict__ bpar) {
     __shared__ double red[256];
     const int tb = (int)blockIdx.z;             // theta of a batched launch: its results go to their own row of host_res
+    if (bpar) white = bset(bpar, tb, bstride)[GPRY_BPAR_WHITE];
     const double* __restrict__ part = bset(part_, tb, bstride);
     double* __restrict__ out = bset(out_, tb, bstride);
     const int* __restrict__ info = bset(info_, tb, bstride);
     const double* __restrict__ lq = bset(lq_, tb, bstride);
     if (host_res) host_res += (int64_t)tb * GPRY_BRES_STRIDE;
+    // workgroups 0 .. nplain - 1: log C and the length scales; workgroup nplain (a model with a white term): log w, whose
+    // partial sums sit in column white_col -- 1/2 w tr(alpha alpha^T - K^-1)
     const int k = blockIdx.x, t = threadIdx.x;
+    const int col = k < nplain ? k : white_col;
     double s = 0.0;
-    for (int64_t i = t; i < ntile; i += 256) s += part[i * stride + k];
+    for (int64_t i = t; i < ntile; i += 256) s += part[i * stride + col];
     red[t] = s;
     __syncthreads();
     for (int w = 128; w >= 1; w >>= 1) {
@@ -880,6 +904,7 @@ __global__ __launch_bounds__(256) void reduce_traces_kernel(const double* __rest
         __syncthreads();
     }
     if (t == 0) {
+        if (k >= nplain) red[0] *= white;
         out[k] = 0.5 * red[0];
         // last kernel of an evaluation with gradient: results and factorisation status also go straight into the
         // mapped host buffer (read by the host after the stream wait: no copy-out operations)
@@ -901,7 +926,7 @@ int launch_lml_traces(gpry_ctx* ctx, const double* Kinv, const double* alpha, do
     int64_t ntile = nb * (nb + 1) / 2;
     if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
     int DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
-    int64_t need = ntile * (DPsel + 1);
+    int64_t need = ntile * (DPsel + 2);
     if (need > ctx->part_cap && ctx->bpar) return gpry_fail(ctx, -1, "batched chain: partial sums exceed the arena");
     if (need > ctx->part_cap) {
         if (ctx->dpart) dev_free(ctx, ctx->dpart);
@@ -916,8 +941,9 @@ int launch_lml_traces(gpry_ctx* ctx, const double* Kinv, const double* alpha, do
 #undef LT4
 #undef LT2
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(reduce_traces_kernel, dim3((unsigned)(ctx->d + 1), 1, (unsigned)ctx->bn), dim3(256), 0, ctx->stream,
-                       ctx->dpart, ntile, DPsel + 1, grad_out_dev, ctx->dinfo, lq_dev, host_res, info_at, ctx->bstride);
+    hipLaunchKernelGGL(reduce_traces_kernel, dim3((unsigned)ctx_ntheta(ctx), 1, (unsigned)ctx->bn), dim3(256), 0, ctx->stream,
+                       ctx->dpart, ntile, DPsel + 2, grad_out_dev, ctx->dinfo, lq_dev, host_res, info_at, ctx->bstride,
+                       ctx->d + 1, DPsel + 1, kp.white, ctx->bpar);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

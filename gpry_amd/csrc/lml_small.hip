@@ -47,21 +47,23 @@ struct LmlSmallArgs {
     const double* X;        // N x d transformed training rows (ctx->dX)
     const double* y;        // Np (zero padded)
     const double* noise;    // Np
-    LsUnit* host_res;       // mapped host memory, 16-byte units {value, stamp}: [0] sum log L_ii, [1] quad, [2 .. 2 + d] gradient,
+    LsUnit* host_res;       // mapped host memory, 16-byte units {value, stamp}: [0] sum log L_ii, [1] quad, [2 .. 2 + d] gradient
+                            // ([3 + d]: the entry of log w of a model with a white term),
                             // [LS_INFO_UNIT] factorisation status (0 or the 1-based failing column, as a double)
     unsigned long long seq; // stamp of this evaluation
     int want_grad;
-    const double* batch;       // nullable: several thetas in ONE launch, workgroup b evaluates [C, l_1 .. l_16] = batch[17 b ..] (the values
+    const double* batch;       // nullable: several thetas in ONE launch, workgroup b evaluates [C, l_1 .. l_16, w] = batch[LS_PAR b ..] (the values
                                // the host computes for a single evaluation: same bits) and reports into host_res + LS_UNITS * b
 };
 #define LS_UNITS (LS_INFO_UNIT + 1)
+#define LS_PAR 18
 
 template <int DP, int KID>
 __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernParams kp, AffParams ap) {
     __shared__ __attribute__((aligned(16))) double M[LS_NP * LS_LD];
     __shared__ __attribute__((aligned(16))) double xs[DP * LS_NP];      // k-major: xs[k * 128 + row]
     __shared__ double sy[LS_NP], sz[LS_NP], sal[LS_NP], srd[LS_NP], slog[LS_NP];
-    __shared__ double red[LS_NB][DP + 2];
+    __shared__ double red[LS_NB][DP + 3];       // [..][0 .. DP]: traces, [0 / 1][DP + 1]: log-det and quad, [..][DP + 2]: tr W (white term)
     __shared__ double red2[4][LS_NP];
     __shared__ int s_flag[16];
     __shared__ int s_bad;
@@ -69,8 +71,9 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
     const int r = lane & 15, g = lane >> 4;
     const int N = (int)kp.N;
     if (a.batch != nullptr) {      // this workgroup's theta and result units (the restarts of a fit evaluated side by side)
-        const double* bp = a.batch + 17 * (int64_t)blockIdx.x;
+        const double* bp = a.batch + LS_PAR * (int64_t)blockIdx.x;
         kp.C = bp[0];
+        kp.white = bp[LS_PAR - 1];
 #pragma unroll
         for (int k = 0; k < DP; k++) ap.ls[k] = bp[1 + k];
         a.host_res += LS_UNITS * (int64_t)blockIdx.x;
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
         for (int q = 0; q < 4; q++) {
             const int i = 16 * bi + g + 4 * q;
             double v = kp.C * corr_r2<KID>(r2[q]);               // libm exp / sqrt, as the training build of the general path
-            if (i == j) v = kp.C + (i < N ? a.noise[i] : 0.0);
+            if (i == j) v = kp.white_on ? kp.C + ((i < N ? a.noise[i] : 0.0) + kp.white) : kp.C + (i < N ? a.noise[i] : 0.0);
             if (i >= N || j >= N) v = (i == j) ? 1.0 : 0.0;      // identity padding
             M[i * LS_LD + j] = v;
         }
@@ -266,6 +269,7 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
     double gacc[DP + 1];
 #pragma unroll
     for (int k = 0; k <= DP; k++) gacc[k] = 0.0;
+    double gw = 0.0;            // tr W = sum_i (alpha_i^2 - K^-1_ii): d K / d log w = w I (model with a white term)
     const int ntile = nb * (nb + 1) / 2;
     for (int q8 = 0; q8 * LS_NB < ntile; q8++) {
         const int tl = q8 * LS_NB + ((q8 & 1) ? LS_NB - 1 - w : w);      // snake over the waves: long tiles come first
@@ -294,6 +298,7 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
             const double h = corr_and_h<KID>(r2[q], &kv);
             if (i == j) kv = 1.0;
             if (i >= N || j >= N) wv = 0.0;
+            if (kp.white_on && i == j) gw += wv;
             gacc[0] = fma(wv, kp.C * kv, gacc[0]);
             wh[q] = wv * kp.C * h;
         }
@@ -313,6 +318,10 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
         for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) red[w][k] = v;
     }
+    if (kp.white_on) {
+        for (int off = 32; off >= 1; off >>= 1) gw += __shfl_xor(gw, off);
+        if (lane == 0) red[w][DP + 2] = gw;
+    }
     __syncthreads();
     // ---- I: results
     if (t <= kp.d) {
@@ -320,6 +329,12 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
 #pragma unroll
         for (int q = 0; q < LS_NB; q++) s += red[q][t];
         ls_store_unit(a.host_res + 2 + t, 0.5 * s, a.seq);
+    }
+    if (kp.white_on && t == 64) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < LS_NB; q++) s += red[q][DP + 2];
+        ls_store_unit(a.host_res + 3 + kp.d, 0.5 * (s * kp.white), a.seq);
     }
     if (t == 0) {
         const double sl = red[0][DP + 1], sq = red[1][DP + 1];
@@ -330,7 +345,7 @@ __global__ __launch_bounds__(LS_NT) void lml_small_kernel(LmlSmallArgs a, KernPa
 }
 
 // N <= 128, d <= 16: the single-launch evaluation, for B thetas at once (B workgroups of one launch; B = 1: gpry_lml).
-// params: B x 17 doubles [C, l_1 .. l_16] as the host computes them for a single evaluation (nullptr with B = 1: the
+// params: B x 18 doubles [C, l_1 .. l_16, w] as the host computes them for a single evaluation (nullptr with B = 1: the
 // context's theta); out: B x (2 + 33) doubles [sum log L_ii, quad, grad (1 + d) ...] per theta, info[B]: 0 or the failing
 // column.  The results are picked up from the stamped units as they land (see LsUnit); the stream is only queried now and
 // then, to notice a launch that failed.  Returns 1 if the model does not fit this kernel (the caller takes the general
@@ -341,12 +356,13 @@ int launch_lml_small_batch(gpry_ctx* ctx, int B, const double* params, int want_
     if (B < 1 || (B > 1 && !params)) return gpry_fail(ctx, -1, "lml_small: bad batch");
     KernParams kp;
     kp.C = exp(ctx->theta[0]); kp.d = ctx->d; kp.dpad = ctx->dpad; kp.has_aff = 0; kp.N = ctx->N;
+    kp.white = ctx_white(ctx); kp.white_on = ctx->white ? 1 : 0;
     AffParams ap = make_ap(ctx, false);
     // the units live behind the first KiB of the staging buffer (the general chain writes plain doubles into that), the
     // parameter rows of a batch behind the units
     const int64_t unit_bytes = (int64_t)sizeof(LsUnit) * LS_UNITS * B;
     const int64_t par_off = round_up(1024 + unit_bytes, 256);
-    GPRY_TRY(ensure_pinned(ctx, par_off + (int64_t)sizeof(double) * 17 * B + 256));
+    GPRY_TRY(ensure_pinned(ctx, par_off + (int64_t)sizeof(double) * LS_PAR * B + 256));
     LsUnit* hu = reinterpret_cast<LsUnit*>(static_cast<char*>(ctx->hpin) + 1024);
     LmlSmallArgs a;
     a.X = ctx->dX; a.y = ctx->dy; a.noise = ctx->dnoise;
@@ -355,7 +371,7 @@ int launch_lml_small_batch(gpry_ctx* ctx, int B, const double* params, int want_
     a.want_grad = want_grad;
     a.batch = nullptr;
     if (params) {
-        memcpy(static_cast<char*>(ctx->hpin) + par_off, params, sizeof(double) * 17 * B);
+        memcpy(static_cast<char*>(ctx->hpin) + par_off, params, sizeof(double) * LS_PAR * B);
         a.batch = reinterpret_cast<const double*>(static_cast<char*>(ctx->hpin_dev) + par_off);
     }
 #define LS2(DP, KID) hipLaunchKernelGGL((lml_small_kernel<DP, KID>), dim3((unsigned)B), dim3(LS_NT), 0, ctx->stream, a, kp, ap)
@@ -365,7 +381,7 @@ int launch_lml_small_batch(gpry_ctx* ctx, int B, const double* params, int want_
 #undef LS2
     HIP_TRY(ctx, hipGetLastError());
     const unsigned long long seq = a.seq;
-    const int need = 2 + (want_grad ? ctx->d + 1 : 0);
+    const int need = 2 + (want_grad ? ctx_ntheta(ctx) : 0);
     long long spins = 0;
     bool finished = false;         // the stream has drained: whatever has not landed by now never will
     int done = 0;                  // thetas 0 .. done - 1 have been picked up

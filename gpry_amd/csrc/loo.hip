@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void loo_pass_kernel(const double* __restrict_
 __global__ __launch_bounds__(64) void loo_finish_kernel(const double* __restrict__ V, int64_t Np, int64_t N, int nt,
                                                          const double* __restrict__ qpart, const double* __restrict__ wpart,
                                                          const double* __restrict__ y, const double* __restrict__ alpha_,
-                                                         const double* __restrict__ noise, double y_mean, double y_std,
+                                                         const double* __restrict__ noise, double white, int white_on, double y_mean, double y_std,
                                                          double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * LOO_T + threadIdx.x;      // one wave per tile of 64 points: N / 64 workgroups
     if (i >= N) return;
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(64) void loo_finish_kernel(const double* __restrict
     const double vkk = V[i * (Np + 1)], ys2 = y_std * y_std, yi = y[i], rq = 1.0 / q;
     out[i] = ns_rn((yi - alpha_[i] * rq) * y_std) + y_mean;
     out[N + i] = ys2 * rq;
-    out[2 * N + i] = fmax(rq - noise[i], 0.0) * ys2;
+    out[2 * N + i] = fmax(rq - (white_on ? noise[i] + white : noise[i]), 0.0) * ys2;      // var_f: without alpha_i + w
     out[3 * N + i] = ns_rn((yi - w / vkk) * y_std) + y_mean;
     out[4 * N + i] = ys2 / (vkk * vkk);
 }
@@ -295,7 +295,7 @@ int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* 
         hipLaunchKernelGGL(loo_pass_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, ctx->dV, Np, N, ctx->dy,
                            qpart, wpart);
         hipLaunchKernelGGL(loo_finish_kernel, dim3((unsigned)nt), dim3(LOO_T), 0, st, ctx->dV, Np, N, nt, qpart, wpart, ctx->dy,
-                           ctx->dalpha_, ctx->dnoise, ctx->tf.y_mean, ctx->tf.y_std, out);
+                           ctx->dalpha_, ctx->dnoise, ctx_white(ctx), ctx->white ? 1 : 0, ctx->tf.y_mean, ctx->tf.y_std, out);
         HIP_TRY(ctx, hipGetLastError());
         // one copy of the five rows into pinned memory of the call's own, handed out below
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hloo, out, sz[2], hipMemcpyDeviceToHost, st));

@@ -251,6 +251,7 @@ int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const d
     if (!isfinite(zeta) || !isfinite(baseline))
         return gpry_fail(ctx, -1, "gpry_maximize_acq: zeta = %g, baseline = %g", zeta, baseline);
     GPRY_TRY(require_model(ctx, true));
+    GPRY_TRY(refuse_white(ctx, "gpry_maximize_acq"));
     if (ctx->Np > MAXACQ_NP_MAX)
         return gpry_fail(ctx, -1, "gpry_maximize_acq: the model has %lld padded rows, more than %d", (long long)ctx->Np,
                          MAXACQ_NP_MAX);

@@ -261,6 +261,7 @@ static void srv_post(SrvHost* s, unsigned long long cmd, const double* X, int M,
 static int srv_launch(gpry_ctx* ctx, SrvHost* s) {
     KernParams kp;
     kp.C = exp(ctx->theta[0]); kp.d = ctx->d; kp.dpad = ctx->dpad; kp.has_aff = ctx->tf.has_x_affine; kp.N = ctx->N;
+    kp.white = ctx_white(ctx); kp.white_on = ctx->white ? 1 : 0;      // (the mean needs neither)
     AffParams ap = make_ap(ctx, kp.has_aff);
     int nsplit = (int)(ctx->N / 1024);            // the slices of the one-launch path (api.hip: gpry_predict)
     if (nsplit < 1) nsplit = 1;

@@ -288,7 +288,8 @@ static int choose_panel_form(gpry_ctx* ctx, bool small_build) {
     const double e = 4.0 * 2.220446049250313e-16 * C * (1.0 + 6.0 * R2);
     ctx->panel_est[0] = e * ctx->alpha_l2;
     ctx->panel_est[1] = e * ctx->alpha_l1;
-    ctx->panel_est[2] = ctx->noise_min > 0.0 ? 2.0 * e / (sqrt(ctx->noise_min) * sqrt(C)) : INFINITY;
+    const double lam_min = ctx->noise_min + ctx_white(ctx);      // lambda_min(K) >= min(alpha) + w
+    ctx->panel_est[2] = lam_min > 0.0 ? 2.0 * e / (sqrt(lam_min) * sqrt(C)) : INFINITY;
     if (!(ctx->panel_est[0] <= ctx->panel_est[3]) || !(ctx->panel_est[2] <= ctx->panel_est[3])) fast_panel = false;
     if (ctx->opt_panel_debug & 32) fast_panel = true;       // test hook: the matrix-pipe form whatever the estimates say
     if (fast_panel) ctx->panel_form = 1;
@@ -405,7 +406,9 @@ static int contract_splitk(gpry_ctx* ctx, const double* Kst, int64_t ncols, int 
 // the post-processing of the context's model for a request
 static FinishParams finish_params(const gpry_ctx* ctx, const SweepRequest& rq) {
     FinishParams fp;
-    fp.C = exp(ctx->theta[0]); fp.y_mean = ctx->tf.y_mean; fp.y_std = ctx->tf.y_std;
+    // (fp.C is the prior VARIANCE of a new point, C + w for a model with a white term: the finishes form var = fp.C - |V k*|^2
+    // from it and the bound kernels of the pruned sweep their prior sigma, finish_sd(0, ..) -- acq_math.h)
+    fp.C = ctx_prior_var(ctx); fp.y_mean = ctx->tf.y_mean; fp.y_std = ctx->tf.y_std;
     fp.clip_hi = ctx->tf.clip_hi; fp.zeta = rq.zeta; fp.baseline = rq.baseline; fp.sigma_n = rq.sigma_n;
     fp.want_std = rq.kind != SWEEP_PREDICT || rq.want_std; fp.want_acq = rq.kind != SWEEP_PREDICT;
     return fp;
@@ -618,7 +621,7 @@ static int prune_snapshot(gpry_ctx* ctx) {
     HIP_TRY(ctx, hipMemcpyAsync(m.dalpha_, ctx->dalpha_, sizeof(double) * Np, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(m.dXs, ctx->dXs, sizeof(double) * Np * ctx->dpad, hipMemcpyDeviceToDevice, ctx->stream));
     if (N > 0) HIP_TRY(ctx, hipMemcpyAsync(m.dX, ctx->dX, sizeof(double) * N * ctx->d, hipMemcpyDeviceToDevice, ctx->stream));
-    m.N = N; m.Np = Np; m.d = ctx->d; m.dpad = ctx->dpad; m.kernel_id = ctx->kernel_id;
+    m.N = N; m.Np = Np; m.d = ctx->d; m.dpad = ctx->dpad; m.kernel_id = ctx->kernel_id; m.white = ctx->white;
     memcpy(m.theta, ctx->theta, sizeof(m.theta));
     m.tf = ctx->tf;
     memcpy(m.xcenter, ctx->xcenter, sizeof(m.xcenter));
@@ -635,7 +638,7 @@ struct SnapSwap {
         gpry_ctx::ModelSnap& m = c->snap;
         std::swap(c->dV, m.dV); std::swap(c->dalpha_, m.dalpha_); std::swap(c->dXs, m.dXs); std::swap(c->dX, m.dX);
         std::swap(c->N, m.N); std::swap(c->Np, m.Np); std::swap(c->d, m.d); std::swap(c->dpad, m.dpad);
-        std::swap(c->kernel_id, m.kernel_id); std::swap(c->theta, m.theta); std::swap(c->tf, m.tf);
+        std::swap(c->kernel_id, m.kernel_id); std::swap(c->white, m.white); std::swap(c->theta, m.theta); std::swap(c->tf, m.tf);
         std::swap(c->xcenter, m.xcenter); std::swap(c->xs_foreign, m.xs_foreign);
     }
 };

@@ -288,6 +288,14 @@ class BatchOptimizer(GenericGPAcquisition):
         if not (isinstance(n_points, int) and n_points > 0):
             raise ValueError(f"n_points should be int > 0, got {n_points}")
         rng = get_random_generator(rng)
+        if isinstance(self.acq_optimizer, str) and self.acq_optimizer == "device" and getattr(gpr, "has_white_term", False):
+            # gpry_maximize_acq does not carry a fitted white term (WhiteKernel) yet: this call's runs are L-BFGS-B runs,
+            # side by side where they can be
+            self.acq_optimizer = "fmin_l_bfgs_b"
+            try:
+                return self.multi_add(gpr, n_points=n_points, bounds=bounds, rng=rng, force_resample=force_resample)
+            finally:
+                self.acq_optimizer = "device"
         use_bounds = self.bounds_ if bounds is None else bounds
         X_opts, y_lies, acq_vals = np.empty((n_points, gpr.d)), np.empty(n_points), np.empty(n_points)
         gpr_ = deepcopy(gpr)                    # the lies go into a copy

@@ -389,6 +389,16 @@ class GaussianProcessRegressor(_RM, _BE):
     def _device_theta(self, kernel=None):
         return (kernel or self.kernel_).device_spec(self.d)
 
+    @property
+    def has_white_term(self):
+        """Does the kernel carry a ``WhiteKernel`` whose noise level is part of the model (and of theta)?"""
+        kernel = self.kernel_ if self.kernel_ is not None else self.kernel
+        return bool(kernel.device_spec(self.d)[0] & _lib.KERNEL_WHITE)
+
+    def _refuse_white(self, who):
+        if self.has_white_term:
+            raise NotImplementedError(f"{who} does not carry the white term (WhiteKernel) of the kernel yet")
+
     def _ensure_factor(self):
         """Bring the device factor up to date with (kernel_, training set)."""
         if self._dev_factor_ok:
@@ -475,7 +485,8 @@ class GaussianProcessRegressor(_RM, _BE):
     @property
     def scales(self):
         """(output scale, length scales) in the units of the caller."""
-        amplitude, lengths = np.sqrt(self.kernel_.k1.constant_value), np.atleast_1d(self.kernel_.k2.length_scale)
+        prod = self.kernel_._parts()[0] if self.has_white_term else self.kernel_      # (C * k of C * k + WhiteKernel)
+        amplitude, lengths = np.sqrt(prod.k1.constant_value), np.atleast_1d(prod.k2.length_scale)
         return (self.preprocessing_y.inverse_transform_scale(amplitude),
                 tuple(self.preprocessing_X.inverse_transform_scale(lengths)))
 
@@ -908,10 +919,7 @@ class GaussianProcessRegressor(_RM, _BE):
             # theta = [log C, log l_1 .. log l_d] (the automatic kernel): the device vector is log(exp(theta)) row by row --
             # what ``device_spec`` returns after ``kernel.theta = theta`` -- and the gradient needs no chain rule.  Going
             # through the kernel object cost 15 us per theta, more than the device's share of a round below ~300 points.
-            plain = False
-            if fast:
-                _, _, n_c, n_l, _, const_first = kern._layout()
-                plain = n_c == 1 and n_l == d and const_first
+            plain = fast and kern.plain_theta(d)        # (with a white term: one more column, log w last)
 
             def fg(Thetas):
                 if plain:
@@ -922,7 +930,7 @@ class GaussianProcessRegressor(_RM, _BE):
                     lml, grad_full, _ = dv.lml_batch(fulls, True)
                     counts[g] += len(T)
                     bad = ~np.isfinite(lml)
-                    F, G = -lml, -grad_full[:, :d + 1]
+                    F, G = -lml, -grad_full[:, :T.shape[1]]
                     if bad.any():
                         F[bad] = np.inf
                         G[bad] = 0.0
@@ -1262,6 +1270,7 @@ class GaussianProcessRegressor(_RM, _BE):
             if self.trust_bounds is not None and not ignore_trust_region:
                 y_mean[~is_in_bounds(X, self.trust_bounds)] = self.minus_inf_value
             return y_mean, self.kernel(X)
+        self._refuse_white("predict(return_cov=True)")
         self._ensure_factor()
         self._push_affine()
         res = self.device.predict_cov(X, mask=self._joint_mask(X, validate, ignore_trust_region))
@@ -1293,6 +1302,7 @@ class GaussianProcessRegressor(_RM, _BE):
             seed = int(random_state)
         if self.X_train_ is None:
             raise ValueError("sample_y needs a model with training data")
+        self._refuse_white("sample_y")
         self._ensure_factor()
         self._push_affine()
         res = self.device.sample_joint(X, n_samples, seed, jitter=jitter,

@@ -7,13 +7,16 @@ of the scikit-learn kernels those derive from (``theta`` layout: sklearn:kernels
 All arithmetic -- ``k(X, Y)``, ``diag`` and the theta-gradient traces used by the
 marginal likelihood -- runs on the GPU through ``gpry_amd._lib``; only
 ``ConstantKernel * RBF`` and ``ConstantKernel * Matern(nu in {0.5, 1.5, 2.5})``, the
-kernels the reference's auto-constructor builds (gpry/gpr.py:343-363), are supported.
+kernels the reference's auto-constructor builds (gpry/gpr.py:343-363), are supported -- and either of them plus a
+``WhiteKernel`` (``WhiteKernel`` :612, ``Sum`` :671), whose noise level the fit then learns with the other entries of theta.
 """
 import copy
 import warnings
 from collections import namedtuple
 
 import numpy as np
+
+KERNEL_WHITE = 0x10     # include/gpry_hip.h GPRY_KERNEL_WHITE: flag bit of a kernel id, the model has a fitted white term
 
 
 class Hyperparameter(namedtuple("Hyperparameter", ("name", "value_type", "bounds", "max_length",
@@ -113,6 +116,12 @@ class Kernel:
         return c
 
     # -- operators ----------------------------------------------------------------------
+    def __add__(self, b):
+        return Sum(self, b if isinstance(b, Kernel) else ConstantKernel(b))
+
+    def __radd__(self, b):
+        return Sum(b if isinstance(b, Kernel) else ConstantKernel(b), self)
+
     def __mul__(self, b):
         return Product(self, b if isinstance(b, Kernel) else ConstantKernel(b))
 
@@ -121,7 +130,8 @@ class Kernel:
 
     # -- evaluation (device) --------------------------------------------------------------
     def device_spec(self, d):
-        """(kernel_id, full theta [log C, log l_1..l_d]) for libgpry_hip.so."""
+        """(kernel_id, full theta [log C, log l_1..l_d]) for libgpry_hip.so; a sum with a ``WhiteKernel``: the id with
+        ``KERNEL_WHITE`` set and ``log noise_level`` as one more entry."""
         raise NotImplementedError(
             f"{self!r}: only ConstantKernel * RBF / Matern(nu=0.5|1.5|2.5) run on the device")
 
@@ -356,6 +366,11 @@ class Product(Kernel):
             return np.array(grad_full[:d + 1], dtype=float)
         return self.grad_from_full(grad_full, d)
 
+    def plain_theta(self, d):
+        """Is theta the device's own vector ``[log C, log l_1 .. log l_d]``, entry by entry?"""
+        _, _, n_c, n_l, _, const_first = self._layout()
+        return n_c == 1 and n_l == d and const_first
+
     def clone_with_theta(self, theta):
         # shallow copies of the two factors: the setter replaces the values it touches by new objects, bounds and
         # prior boxes are never modified in place (a deepcopy cost 45 us per objective evaluation)
@@ -388,6 +403,120 @@ class Product(Kernel):
 
     def __repr__(self):
         return f"{self.k1!r} * {self.k2!r}"
+
+
+class WhiteKernel(Kernel):
+    """White noise of variance ``noise_level`` (transformed-y units) on the diagonal of ``k(X, X)``
+    (gpry/kernels.py:612, sklearn:kernels.py WhiteKernel).  Runs on the device as a term of a ``Sum`` only."""
+
+    def __init__(self, noise_level=1.0, noise_level_bounds=(1e-5, 1e5)):
+        self.noise_level = noise_level
+        self.noise_level_bounds = noise_level_bounds
+
+    def get_params(self, deep=True):
+        return {"noise_level": self.noise_level, "noise_level_bounds": self.noise_level_bounds}
+
+    @property
+    def hyperparameter_noise_level(self):
+        return Hyperparameter("noise_level", "numeric", self.noise_level_bounds, None)
+
+    def gradient_x(self, x, X_train):
+        return np.zeros_like(np.atleast_2d(np.asarray(X_train, dtype=float)))
+
+    def diag(self, X):
+        return np.full(np.atleast_2d(X).shape[0], self.noise_level, dtype=float)
+
+    def __repr__(self):
+        return "{0}(noise_level={1:.3g})".format(type(self).__name__, self.noise_level)
+
+
+class Sum(Kernel):
+    """``k1 + k2`` (gpry/kernels.py:671).  On the device: ``(ConstantKernel * RBF | Matern) + WhiteKernel`` in either
+    order -- kernel id with ``KERNEL_WHITE``, theta ``[log C, log l_1..l_d, log noise_level]``."""
+
+    def __init__(self, k1, k2):
+        self.k1, self.k2 = k1, k2
+
+    get_params = Product.get_params
+    hyperparameters = Product.hyperparameters
+    theta = Product.theta
+    bounds = Product.bounds
+
+    def _parts(self):
+        if isinstance(self.k1, Product) and isinstance(self.k2, WhiteKernel):
+            return self.k1, self.k2
+        if isinstance(self.k2, Product) and isinstance(self.k1, WhiteKernel):
+            return self.k2, self.k1
+        return Kernel.device_spec(self, None)       # raises
+
+    def device_spec(self, d):
+        prod, white = self._parts()
+        kid, full = prod.device_spec(d)
+        return kid | KERNEL_WHITE, np.append(full, np.log(float(white.noise_level)))
+
+    # -- the objective's fast paths, as on Product
+    def _layout(self):
+        prod, white = self._parts()
+        wb = white.noise_level_bounds
+        n_w = 0 if (isinstance(wb, str) and wb == "fixed") else 1
+        _, _, n_c, n_l, _, _ = prod._layout()
+        return prod, white, n_c + n_l, n_w, prod is self.k1
+
+    def _split(self, theta):
+        prod, white, n_p, n_w, prod_first = self._layout()
+        theta = np.asarray(theta, dtype=float)
+        if theta.shape != (n_p + n_w,):
+            raise ValueError(f"theta has not the correct number of entries. Should be {n_p + n_w}; "
+                             f"given are {len(theta)}")
+        tp, tw = (theta[:n_p], theta[n_p:]) if prod_first else (theta[n_w:], theta[:n_w])
+        return prod, white, tp, tw
+
+    def set_theta_and_full(self, theta, d):
+        """``self.theta = theta`` followed by ``self.device_spec(d)`` in one pass."""
+        prod, white, tp, tw = self._split(theta)
+        if len(tw):
+            white.noise_level = float(np.exp(tw[0]))
+        kid, full = prod.set_theta_and_full(tp, d)
+        return kid | KERNEL_WHITE, np.append(full, np.log(float(white.noise_level)))
+
+    def grad_from_full(self, grad_full, d):
+        """Chain rule from d lml / d [log C, log l_1..l_d, log w] to the free entries of theta."""
+        prod, white, n_p, n_w, prod_first = self._layout()
+        gp = prod.grad_from_full(grad_full[:d + 1], d)
+        gw = np.array(grad_full[d + 1:d + 2], dtype=float) if n_w else np.array([])
+        return np.append(gp, gw) if prod_first else np.append(gw, gp)
+
+    def grad_from_full_fast(self, grad_full, d):
+        if self.plain_theta(d):
+            return np.array(grad_full[:d + 2], dtype=float)
+        return self.grad_from_full(grad_full, d)
+
+    def plain_theta(self, d):
+        prod, _, _, n_w, prod_first = self._layout()
+        return prod.plain_theta(d) and n_w == 1 and prod_first
+
+    def clone_with_theta(self, theta):
+        prod, white, tp, tw = self._split(theta)
+        w = copy.copy(white)
+        if len(tw):
+            w.noise_level = float(np.exp(tw[0]))
+        p = prod.clone_with_theta(tp)
+        return Sum(p, w) if prod is self.k1 else Sum(w, p)
+
+    def theta_to_full(self, theta, d):
+        k = copy.deepcopy(self)
+        k.theta = theta
+        return k.device_spec(d)[1]
+
+    def gradient_x(self, x, X_train):
+        prod, _ = self._parts()
+        return prod.gradient_x(x, X_train)
+
+    def diag(self, X):
+        return self.k1.diag(X) + self.k2.diag(X)
+
+    def __repr__(self):
+        return f"{self.k1!r} + {self.k2!r}"
 
 
 def clone(kernel):

@@ -40,7 +40,11 @@ class KBSession:
         self._index = {}
         self._gram = {}
         self._last_cond = None           # most recent conditioned model (prefix re-use)
-        self.C = float(np.exp(gpr._device_theta()[1][0]))
+        kid, full = gpr._device_theta()
+        self.C = float(np.exp(full[0]))
+        # a fitted white term w (WhiteKernel) sits on the diagonal of every appended point beside its alpha; the device's
+        # var0 is C + w - |u|^2
+        self.white = float(np.exp(full[-1])) if kid & _lib.KERNEL_WHITE else None
         self.std_y = gpr._y_affine()[1]
 
     @property
@@ -117,7 +121,8 @@ class KBSession:
         if np.iterable(nl):
             raise ValueError("Need to pass non-null noise_level (scalar or array) because concrete "
                              "values were given earlier for the training points.")
-        return float(self.gpr.preprocessing_y.transform_scale(nl)) ** 2
+        alpha = float(self.gpr.preprocessing_y.transform_scale(nl)) ** 2
+        return alpha if self.white is None else alpha + self.white
 
     def conditioned(self, Xp, yp):
         gpr = self.gpr

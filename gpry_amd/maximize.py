@@ -101,7 +101,7 @@ def _refuse_matern12(gpr, d, who):
     """A Matern-1/2 mean has a kink at every training row: no Hessian.  (The stand-ins of the tests carry a ``kernel_id``.)"""
     kernel = getattr(gpr, "kernel_", None)
     kid = kernel.device_spec(d)[0] if hasattr(kernel, "device_spec") else getattr(gpr, "kernel_id", None)
-    if kid == 1:
+    if kid is not None and (kid & 0xF) == 1:      # (the white-term flag is not part of the family)
         raise ValueError(f"{who}: the mean of a Matern-1/2 model is not differentiable at the training rows; it has no "
                          "Hessian")
 
@@ -424,7 +424,10 @@ def acq_h0(gpr, covmat, lo, hi):
     kernel = getattr(gpr, "kernel_", None)
     if kernel is None:
         return np.eye(d)
-    ls = np.broadcast_to(np.exp(np.asarray(kernel.theta, dtype=float)[1:]), (d,)).copy()
+    theta = np.asarray(kernel.theta, dtype=float)
+    if getattr(gpr, "has_white_term", False):       # C * k + WhiteKernel: the length scales of k, wherever log w sits in theta
+        theta = np.asarray(kernel._parts()[0].theta, dtype=float)
+    ls = np.broadcast_to(np.exp(theta[1:]), (d,)).copy()
     px = getattr(gpr, "preprocessing_X", None)
     if px is not None and hasattr(px, "transform_bounds"):
         tb = np.asarray(px.transform_bounds(np.stack([lo, hi], axis=1)), dtype=float)

@@ -30,6 +30,15 @@ typedef struct gpry_group gpry_group;
 
 /* kernel ids: Product(ConstantKernel, RBF | Matern(nu)) -- gpry/kernels.py:213,281,601,681 */
 enum { GPRY_RBF = 0, GPRY_MATERN12 = 1, GPRY_MATERN32 = 2, GPRY_MATERN52 = 3 };
+/* Flag bit or-ed into a kernel id: Sum(Product(...), WhiteKernel(w)) -- gpry/kernels.py WhiteKernel / Sum.  The noise
+ * level w (a variance, transformed-y units) is a hyperparameter of the model: the training matrix is
+ * C k(X, X) + diag(alpha + w), the prior variance of a new point C + w, and while the flag is set EVERY theta / grad array
+ * of gpry_set_theta, gpry_lml and gpry_lml_batch has 2 + d entries, the last being log w resp. d lml / d log w.
+ * Without the flag nothing changes.  Entry points that do not carry the term yet refuse such a model with an error that
+ * names the white term (-1, gpry_last_error) and leave the context as it was: gpry_maximize_acq, gpry_predict_cov,
+ * gpry_sample_joint, gpry_group_*.  (The Kriging-believer session carries it: var0 = C + w - |u|^2, and the caller adds w
+ * to the alpha of the points it appends.) */
+#define GPRY_KERNEL_WHITE 0x10
 
 /* Largest dimension of the parameter space: ABI size of the per-dimension arrays in gpry_affine AND the
  * limit gpry_set_train enforces (the kernels of this build are instantiated for d <= 32; GPry's design
@@ -183,7 +192,8 @@ int gpry_ctx_get_option(gpry_ctx* ctx, const char* key, int64_t* value);
  * (rows of another width are no pool of this model: such a sweep is refused). */
 int gpry_set_train(gpry_ctx* ctx, const double* X_, const double* y_,
                    const double* alpha, int64_t N, int d);
-/* kernel_.theta = [log C, log l_1..l_d] (sklearn:kernels.py:734-747) */
+/* kernel_.theta = [log C, log l_1..l_d] (sklearn:kernels.py:734-747); with kernel_id | GPRY_KERNEL_WHITE:
+ * [log C, log l_1..l_d, log w], 2 + d entries */
 int gpry_set_theta(gpry_ctx* ctx, int kernel_id, const double* theta);
 int gpry_set_affine(gpry_ctx* ctx, const gpry_affine* tf);
 
@@ -218,12 +228,14 @@ int gpry_append_rows(gpry_ctx* ctx, const double* Xnew_, const double* ynew_, co
 /* ---- a4/a5: log marginal likelihood (+ gradient) ---------------------------------- */
 /* sklearn:_gpr.py:574-652 via gpry/gpr.py:876-881.  Non-PD: returns 0 with
  * *lml = -inf, grad = 0, *info > 0 (sklearn:_gpr.py:586-589).  Does not disturb the
- * factor held for prediction.  grad has 1+d entries (ignored if want_grad == 0). */
+ * factor held for prediction.  grad has 1+d entries (ignored if want_grad == 0).  For a model set with GPRY_KERNEL_WHITE
+ * theta and grad have 2+d entries: theta[1+d] = log w, grad[1+d] = 1/2 w (alpha^T alpha - tr K^-1); the other entries are,
+ * to the bit, those of the model without the flag whose alpha is alpha + w. */
 int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml,
              double* grad, int* info);
 
 /* B evaluations of the same objective in one call (thetas: B x (1 + d), lml: B, grad: B x (1 + d) or NULL, info: B or NULL,
- * each as gpry_lml).  The optimiser runs of a multi-restart fit (gpry/gpr.py:883-994, one after another there) stepped side
+ * each as gpry_lml; rows of 2 + d entries, every theta with its own log w, for a model set with GPRY_KERNEL_WHITE).  The optimiser runs of a multi-restart fit (gpry/gpr.py:883-994, one after another there) stepped side
  * by side hand over one theta per run and round.  N <= 128, d <= 16: one launch, one workgroup per theta; larger training
  * sets up to option "lml_batch" padded rows (default 4096): ONE chain of launches in which every kernel (covariance build,
  * Cholesky panel steps, V = L^-1 levels, K^-1 = V^T V, traces) carries all thetas, each with its own scratch set; either way
