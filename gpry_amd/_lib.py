@@ -61,6 +61,7 @@ SIGNATURES = {
     "gpry_append_rows": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _P(C.c_int)]),
     "gpry_lml": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_double), _vp, _P(C.c_int)]),
     "gpry_lml_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "gpry_loo_objective": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_double), _vp, _P(C.c_int)]),
     "gpry_predict": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_debug_serve_stats": (C.c_int, [_vp, _P(C.c_int64), _P(C.c_int64)]),
     "gpry_ns_prior": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int64, _vp, _vp, _P(C.c_double)]),
@@ -387,6 +388,21 @@ class Device:
             self._check(rc, "gpry_lml")
         if eval_gradient:
             return val.value, gr.copy(), info.value
+        return val.value, info.value
+
+    def loo_objective(self, theta, eval_gradient=False):
+        """The leave-one-out log predictive density of the training targets at ``theta`` (gpry_loo_objective), transformed
+        units like ``lml``: ``(value, info)`` or ``(value, grad, info)``; ``(-inf, zeros, info > 0)`` where the matrix
+        is not positive definite.  The factor held for prediction is not disturbed."""
+        theta = _f64(np.asarray(theta, dtype=np.float64).ravel())
+        if theta.shape[0] != self.n_theta:
+            raise ValueError(f"expected {self.n_theta} entries, got {theta.shape[0]}")
+        grad = np.zeros(self.n_theta)
+        val, info = C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gpry_loo_objective(self._h, _ptr(theta), 1 if eval_gradient else 0, C.byref(val), _ptr(grad),
+                                                 C.byref(info)), "gpry_loo_objective")
+        if eval_gradient:
+            return val.value, grad, info.value
         return val.value, info.value
 
     def lml_batch(self, thetas, eval_gradient=True):

@@ -29,11 +29,11 @@ static int copy_out_matrix(gpry_ctx* ctx, const double* dsrc, int64_t ld, int64_
 // A panel step whose bounded waits ran out (chol_panel.hip: PANEL_SPIN_CAP) reports a failing column like a matrix that is
 // not positive definite and leaves a marker in the fourth status word.  That is a scheduling failure, not a property of the
 // matrix: the caller gets an error, never the -inf of sklearn's non-PD convention (an optimiser would go on with a wrong objective).
-static bool panel_timed_out(int marker) { return (marker & 0xFF00) == 0x5A00; }
-static int panel_timeout_error(gpry_ctx* ctx, int marker) {
+bool panel_timed_out(int marker) { return (marker & 0xFF00) == 0x5A00; }
+int panel_timeout_error(gpry_ctx* ctx, int marker) {
     return gpry_fail(ctx, -2, "Cholesky panel step timed out (wait %d; the GPU is shared with work that starves the step?)", marker & 0xFF);
 }
-static int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* info_host) {
+int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* info_host) {
     // A <- K + diag(alpha); A <- chol(A) (lower); V <- A^-1
     GPRY_TRY(launch_scale_train(ctx));      // X / l (N x d, microseconds)
     // (where V comes out of the Cholesky launches -- potrf_stacked below -- T starts as the identity: written by the same kernel)

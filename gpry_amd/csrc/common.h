@@ -496,5 +496,13 @@ void serve_stats(gpry_ctx* ctx, int64_t* launches, int64_t* requests);
 int serve_predict_mean(gpry_ctx* ctx, const double* X, int64_t M, double* part, int* nsplit_out, unsigned* gate_bits);
 #define GPRY_SERVE_MAXM 8
 
+// ---- api.hip: the factor chain of one objective evaluation, shared with loo_fit.hip ------
+// A <- chol(K + diag(alpha)), V <- A^-1 at the theta the context holds (T: scratch); info_host NULL: the caller reads dinfo itself
+int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* info_host);
+bool panel_timed_out(int marker);                       // fourth status word: a bounded wait of a panel step ran out
+int panel_timeout_error(gpry_ctx* ctx, int marker);
+// loo.hip: gpry_loo's pass over an inverse factor V (partial sums per 64 x 64 tile; ceil(N / 64) x Np doubles each)
+int loo_pass_launch(gpry_ctx* ctx, const double* V, double* qpart, double* wpart);
+
 int ensure_capacity(gpry_ctx* ctx, int64_t N, int d);
 int ensure_pinned(gpry_ctx* ctx, int64_t bytes);

@@ -267,6 +267,16 @@ int loo_require(gpry_ctx* ctx, const char* who) {
 
 }  // namespace
 
+// the pass of gpry_loo over another inverse factor (loo_fit.hip: the V of an objective evaluation): the same launch, so
+// the partial sums -- and q_i once they are added ascending -- are the bits gpry_loo forms for the same model
+int loo_pass_launch(gpry_ctx* ctx, const double* V, double* qpart, double* wpart) {
+    const int nt = (int)((ctx->N + LOO_T - 1) / LOO_T);
+    hipLaunchKernelGGL(loo_pass_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, ctx->stream, V, ctx->Np, ctx->N, ctx->dy,
+                       qpart, wpart);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* seq_mean, double* seq_var_y,

@@ -304,6 +304,7 @@ class GaussianProcessRegressor(_RM, _BE):
         self.noise_level_ = None
         self.kernel_ = None
         self.log_marginal_likelihood_value_ = None
+        self.loo_value_ = None          # leave-one-out log predictive density at the fitted theta (objective="loo")
         self._init_device_state()
 
     # ---- device state ---------------------------------------------------------------
@@ -731,11 +732,61 @@ class GaussianProcessRegressor(_RM, _BE):
         lml, _ = dev.lml(theta_full, False)
         return lml if np.isfinite(lml) else -np.inf
 
+    def loo_log_predictive(self, theta=None, eval_gradient=False, clone_kernel=True):
+        """The leave-one-out log predictive density of the training targets (Rasmussen & Williams 5.4.2), transformed
+        units, on the device (``gpry_loo_objective``): the twin of ``log_marginal_likelihood`` -- same kernel handling,
+        same mapping of theta and gradient (a ``WhiteKernel`` in either operand order), ``(-inf, zeros)`` where the
+        matrix is not positive definite.  ``theta=None``: the value at the fitted theta, ``loo_value_``."""
+        self.n_eval_loglike += 1
+        if theta is None:
+            if eval_gradient:
+                raise ValueError("Gradient can only be evaluated for theta!=None")
+            return self.loo_value_
+        theta = np.asarray(theta, dtype=float)
+        kernel = self.kernel_ if self.kernel_ is not None else clone(self.kernel)
+        fast = hasattr(kernel, "set_theta_and_full")
+        if clone_kernel:
+            kernel = kernel.clone_with_theta(theta)
+            kid, theta_full = kernel.device_spec(self.d)
+        else:
+            if self.kernel_ is None:
+                self.kernel_ = kernel
+            if fast:                      # same side effect as the reference: kernel_.theta = theta
+                kid, theta_full = kernel.set_theta_and_full(theta, self.d)
+            else:
+                kernel.theta = theta
+                kid, theta_full = kernel.device_spec(self.d)
+            self._dev_factor_ok = False
+            self._host_factor = {}
+            self._kb = None
+        if not self._dev_train_ok:
+            self._upload_train()
+        dev = self._dev if self._dev is not None else self.device
+        if dev.N != len(self.y_train_):
+            raise RuntimeError("device training set out of sync")
+        if eval_gradient:
+            val, grad_full, _ = dev.loo_objective(theta_full, True)
+            if not np.isfinite(val):
+                return -np.inf, np.zeros_like(theta)
+            return val, (kernel.grad_from_full_fast(grad_full, self.d) if fast else kernel.grad_from_full(grad_full, self.d))
+        val, _ = dev.loo_objective(theta_full, False)
+        return val if np.isfinite(val) else -np.inf
+
     def fit_gpr_hyperparameters(self, simple=False, start_from_current=True, n_restarts=None,
-                                hyperparameter_bounds=None):
+                                hyperparameter_bounds=None, objective=None):
         """Maximise the marginal likelihood over theta (gpry/gpr.py:883-994): same restart
         schedule, RNG order (:969-978) and optimiser (scipy L-BFGS-B with jac) as the
-        reference; the objective and its gradient are evaluated on the device."""
+        reference; the objective and its gradient are evaluated on the device.
+
+        ``objective``: ``"lml"``, the log marginal likelihood, or ``"loo"``, the leave-one-out log predictive density
+        (``loo_log_predictive``; more robust where the kernel family is misspecified, R&W 5.4.2); ``None`` reads the
+        attribute ``fit_objective`` (default ``"lml"``).  A ``"loo"`` fit runs its restarts one after another, picks
+        the best by the leave-one-out value (``loo_value_``) and sets ``log_marginal_likelihood_value_`` to the LML at
+        the chosen theta."""
+        if objective is None:
+            objective = getattr(self, "fit_objective", "lml")
+        if objective not in ("lml", "loo"):
+            raise ValueError(f"objective: 'lml' or 'loo' (got {objective!r})")
         if simple:
             start_from_current, n_restarts = True, 1
         if not self._fitted:
@@ -755,15 +806,18 @@ class GaussianProcessRegressor(_RM, _BE):
             warnings.warn(f"Hyper-parameters not (re)fit. Reason(s): {'; '.join(reasons)}.")
             self.log_marginal_likelihood_value_ = self.log_marginal_likelihood(
                 self.kernel_.theta, clone_kernel=False)
+            if objective == "loo":
+                self.loo_value_ = self.loo_log_predictive(self.kernel_.theta, clone_kernel=False)
             self._update_model()
             return self
 
+        evaluate = self.loo_log_predictive if objective == "loo" else self.log_marginal_likelihood
+
         def obj_func(theta, eval_gradient=True):
             if eval_gradient:
-                lml, grad = self.log_marginal_likelihood(theta, eval_gradient=True,
-                                                         clone_kernel=False)
+                lml, grad = evaluate(theta, eval_gradient=True, clone_kernel=False)
                 return -lml, -grad
-            return -self.log_marginal_likelihood(theta, clone_kernel=False)
+            return -evaluate(theta, clone_kernel=False)
 
         if hyperparameter_bounds is None:
             hyperparameter_bounds = self.kernel_.bounds
@@ -775,10 +829,13 @@ class GaussianProcessRegressor(_RM, _BE):
                     "bounds are finite. You can pass some finite bounds manually using "
                     "``hyperparameter_bounds``.")
         self._rng = check_random_state(self.random_state)
+        # (the leave-one-out objective has one evaluation per call and lives on the model's own context: no farm, no lock-step)
         ctx_devs = (fit_context_devices(getattr(self.device, "device", 0), n_restarts, getattr(self, "fit_devices", None))
-                    if self.optimizer == "fmin_l_bfgs_b" else [0])
+                    if self.optimizer == "fmin_l_bfgs_b" and objective == "lml" else [0])
         self._side_by_side_why = ""
-        side_by_side = n_restarts > 1 and self._can_step_restarts_together()
+        side_by_side = objective == "lml" and n_restarts > 1 and self._can_step_restarts_together()
+        if objective == "loo" and n_restarts > 1:
+            self._side_by_side_why = "the leave-one-out objective has no batched evaluation: the restarts run one after another"
         if side_by_side or len(ctx_devs) > 1:
             # the optimiser never touches the RNG: drawing the start points up front gives the reference's
             # sequence (gpry/gpr.py:969-978)
@@ -791,7 +848,7 @@ class GaussianProcessRegressor(_RM, _BE):
             # The sequential loop evaluates with single gpry_lml calls (the latency schedule).  ``GPRY_HIP_FIT_SCHEDULE=throughput``
             # makes it the comparator of a throughput-schedule fit instead: every evaluation through the chain of the many with
             # one theta -- the side-by-side fit under that schedule then equals this loop bit for bit
-            seq_tp = (n_restarts > 1 and os.environ.get("GPRY_HIP_FIT_SCHEDULE", "").lower() == "throughput"
+            seq_tp = (objective == "lml" and n_restarts > 1 and os.environ.get("GPRY_HIP_FIT_SCHEDULE", "").lower() == "throughput"
                       and hasattr(self.device, "set_option") and 128 < self.n <= int(getattr(self.device, "lml_batch_max", 128)))
             optima = []
             try:
@@ -817,9 +874,16 @@ class GaussianProcessRegressor(_RM, _BE):
         self.fit_stats["side_by_side"] = bool(side_by_side)
         self.fit_stats["why"] = "" if side_by_side else (self._side_by_side_why or
                                                          ("one restart" if n_restarts <= 1 else "not applicable to this model / optimizer"))
+        self.fit_stats["objective"] = objective
         values = [o[1] for o in optima]
-        self.log_marginal_likelihood_value_ = -np.min(values)
         self.kernel_.theta = optima[int(np.argmin(values))][0]
+        if objective == "loo":
+            # the best run by the leave-one-out value; everything downstream that reads the LML gets it at that theta
+            self.loo_value_ = -np.min(values)
+            self.log_marginal_likelihood_value_ = self.log_marginal_likelihood(self.kernel_.theta, clone_kernel=False)
+        else:
+            self.log_marginal_likelihood_value_ = -np.min(values)
+            self.loo_value_ = None          # (of an earlier "loo" fit: another theta)
         self._invalidate()
         self._update_model()
         self._fitted = True
@@ -1431,7 +1495,7 @@ class GaussianProcessRegressor(_RM, _BE):
             bounds=self.bounds, random_state=self.random_state, account_for_inf=None)
         for name in ("n_eval", "n_eval_loglike", "noise_level_", "alpha", "n_last_appended",
                      "n_last_appended_finite", "newly_appended_for_inv", "_fitted",
-                     "log_marginal_likelihood_value_"):
+                     "log_marginal_likelihood_value_", "loo_value_", "fit_objective"):
             if hasattr(self, name):
                 setattr(c, name, getattr(self, name))
         for name in ("X_train", "y_train", "X_train_", "y_train_", "X_train_all", "y_train_all",

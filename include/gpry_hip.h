@@ -605,6 +605,23 @@ int gpry_sample_joint(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* 
  * "leave_out" (gpry_timing_get).  device_ms (nullable): device time of the call, copies included. */
 int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* seq_mean, double* seq_var_y,
              double* device_ms);
+
+/* ---- The leave-one-out log predictive density as a fit objective (loo_fit.hip; gpry_amd/gpr.py: loo_log_predictive,
+ * fit_gpr_hyperparameters(objective="loo")).  Rasmussen & Williams section 5.4.2, in transformed units like the LML:
+ *   L(theta) = sum_i [ 1/2 log q_i - alpha_i^2 / (2 q_i) ] - N/2 log 2 pi,   q_i = (K^-1)_ii, alpha = K^-1 y_
+ * i.e. the sum of gpry_loo's Gaussian log densities of y_i under (mean, var_y), plus N log y_std.  The gradient is ONE set
+ * of traces: with c_i = -1/2 (1 + alpha_i^2 / q_i) / q_i, b = K^-1 (alpha / q) and H = diag(sqrt(-c)) K^-1,
+ *   dL / d theta_j = sum_kl [ 1/2 (b alpha^T + alpha b^T) - H^T H ]_kl (dK / d theta_j)_kl       for every j at once:
+ * on top of gpry_lml with gradient one lower-only N^3 product on the matrix pipe, one matrix-vector product and
+ * gpry_loo's pass over V (q has the bits gpry_loo gives for the same model).
+ * theta / grad as gpry_lml (1 + d entries, 2 + d with GPRY_KERNEL_WHITE).  Non-PD: returns 0 with *value = -inf, grad = 0,
+ * *info > 0.  Does not disturb the factor held for prediction, a Kriging-believer session, the resident pool or the
+ * buffers of gpry_loo; it clears the factor cache of gpry_lml (option "lml_cache"), whose scratch it overwrites.  The
+ * entry checks are gpry_lml's (training set present, theta finite, d <= 32; the resident predict kernel is stopped).  Any
+ * size goes through the general chain (N <= 128 at 128 padded rows); one evaluation per call.  A result's bits depend on
+ * (training set, theta, kernel id) alone, and the value's not on want_grad.  Stage timers: those of the factor chain,
+ * "solve_alpha", "loo_q", "lauum", "loo_mirror", "loo_gram", "loo_traces". */
+int gpry_loo_objective(gpry_ctx* ctx, const double* theta, int want_grad, double* value, double* grad, int* info);
 int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, int64_t ngroups, double* mean, double* cov,
                    double* chi2, double* logpdf, int* info, double* device_ms);
 
