@@ -108,6 +108,7 @@ SIGNATURES = {
                                           C.c_double, _vp, _vp, _vp, _P(C.c_int64)]),
     "gpry_sweep_fetch": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_sweep_prune_info": (C.c_int, [_vp, _vp, _vp]),
+    "gpry_sweep_screen_info": (C.c_int, [_vp, _vp]),
     "gpry_sweep_topk": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _P(C.c_int64),
                                   _P(C.c_double)]),
     "gpry_kb_reset": (C.c_int, [_vp]),
@@ -963,6 +964,13 @@ class Device:
         out["tau"] = float(dinfo[0])
         out["stage_ms"] = dict(zip(("sweep_mean", "sweep_prune_select", "sweep_compact", "sweep_prune_gemm"), dinfo[1:].tolist()))
         return out
+
+    def sweep_screen_info(self):
+        """The FP32 screen of the bound pass in the last pruned sweep (option ``sweep_screen``, ``gpry_sweep_screen_info``):
+        blocks it certified, and blocks the pass saw."""
+        out = np.zeros(2, dtype=np.int64)
+        self._check(self._lib.gpry_sweep_screen_info(self._h, _ptr(out)), "gpry_sweep_screen_info")
+        return {"certified": int(out[0]), "blocks": int(out[1])}
 
     def sweep_topk(self, Kp, exclude=None):
         Kp = int(Kp)

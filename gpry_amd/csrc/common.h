@@ -168,6 +168,7 @@ struct gpry_ctx {
            DSEL_SURV = 6,      // candidates whose bound is not below tau (prune_survivors)
            DSEL_GIDX = 7,      // indices written to dgidx
            DSEL_LIVE = 8,      // live blocks of the bound pass
+           DSEL_FALL = 9,      // ... and, with its FP32 screen on, the blocks only the FP64 test skipped (the kernel takes DSEL_LIVE + 1)
            DSEL_WORDS = 64 };
 
     // Kriging-believer session
@@ -211,6 +212,9 @@ struct gpry_ctx {
     // 1 (default): in the hybrid panel form, stage A of a pruned sweep bounds y instead of computing it (the bound pass,
     // sweep.hip: mean_bound_setup); exact y only for the candidates that are contracted
     int opt_sweep_mean_bound = 1;
+    // 1 (default): the bound pass certifies far blocks with an FP32 screen in front of its FP64 test (kernel_build.hip: THE
+    // SCREEN); 0: the FP64 test alone (the comparator: same skipped blocks, same outputs)
+    int opt_sweep_screen = 1;
     int sw_pruned = 0;                 // 1: the resident sweep is pruned (acq_all holds exact values or bounds, see sweep_topk.hip)
     struct PruneState {
         int have_mask = 0;
@@ -224,6 +228,7 @@ struct gpry_ctx {
         int64_t survivors = -1;
         int ybound = 0;                // stage A bounded y (the bound pass): every contraction computes y as well
         int64_t live_blocks = 0, blocks = 0;    // blocks of 16 training rows x 32 candidates the bound pass evaluated / saw
+        int64_t cert_blocks = 0;                // ... and those its FP32 screen certified (gpry_sweep_screen_info)
     } prune;
     // the prediction state the pruned sweep was made with, copied at its end (sweep.hip: prune_snapshot): a later contraction
     // round or completion evaluates THAT model, whatever gpry_set_train / set_theta / factorize / append_rows did meanwhile

@@ -313,6 +313,7 @@ const OptionSpec OPTIONS[] = {
     OPT_INT("sweep_overlap", opt_sweep_overlap, 0, 1, (void)0),
     OPT_INT("sweep_prune", opt_sweep_prune, 0, 1, (void)0),
     OPT_INT("sweep_mean_bound", opt_sweep_mean_bound, 0, 1, (void)0),
+    OPT_INT("sweep_screen", opt_sweep_screen, 0, 1, (void)0),
     OPT_INT("sweep_small_map", opt_sweep_small_map, 0, 1, (void)0),
     OPT_INT("select_fused", opt_select_fused, 0, 1, (void)0),
     OPT_INT("prune_one_select", opt_prune_one_select, 0, 1, (void)0),

@@ -364,23 +364,30 @@ __global__ __launch_bounds__(256) void cross_build_kernel(
 // wave-uniform branch); any other block goes through the code of the exact pass unchanged, so that each of its terms
 // alpha_j v_j is the exact pass's to the bit.  mean_part then holds the partial sums over the live terms and sabs_part the
 // sums of |alpha_j v_j| over them; live_cnt counts the live blocks.  The caller (sweep.hip: mean_bound_setup) bounds what was left out.
+// screen != 0: an FP32 test in front of that one certifies most far blocks at half the matrix-pipe time (THE SCREEN, below);
+// live_cnt[1] counts the blocks it did not certify and the FP64 test then skipped (the certified ones are the rest).  The skipped set, and with it every output, is the same with and without it.
 template <int DP, int KID, bool HYB, bool BND = false>
 __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
     const double* __restrict__ Xcs, int64_t ldm, int64_t mc,
     const double* __restrict__ Ycs, const double* __restrict__ alpha_,
     double* __restrict__ Kst, int64_t ldk, double* __restrict__ mean_part, KernParams kp, double ucut,
     double ubnd = 0.0, double uhi = 0.0, double* __restrict__ sabs_part = nullptr,
-    unsigned long long* __restrict__ live_cnt = nullptr) {
+    unsigned long long* __restrict__ live_cnt = nullptr, int screen = 0) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
     constexpr int S = DP + 2, KS = DP / 4;
     constexpr double SC = corr_scale<KID>();
     __shared__ __attribute__((aligned(16))) double Yl[128 * S];
     __shared__ double yn[128], al[128];
+    constexpr int SF = DP + 1;      // (BND: the FP32 image of the training rows for the screen; odd stride: no bank conflicts at DP >= 16)
+    __shared__ float Yf[BND ? 128 * SF : 1];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, r = lane & 15, g = lane >> 4;
     const int jc = blockIdx.y;
     const int64_t mb = (int64_t)blockIdx.x * 256 + 64 * w;      // first candidate of this wave (local index in the chunk)
     for (int e = t; e < 128 * (DP / 2); e += 256) {
         const int row = e / (DP / 2), k2 = (e - row * (DP / 2)) * 2;
-        *reinterpret_cast<double2*>(Yl + row * S + k2) = *reinterpret_cast<const double2*>(Ycs + ((int64_t)jc * 128 + row) * DP + k2);
+        const double2 v = *reinterpret_cast<const double2*>(Ycs + ((int64_t)jc * 128 + row) * DP + k2);
+        *reinterpret_cast<double2*>(Yl + row * S + k2) = v;
+        if (BND) { Yf[row * SF + k2] = (float)v.x; Yf[row * SF + k2 + 1] = (float)v.y; }
     }
     if (t < 128) al[t] = alpha_ ? alpha_[jc * 128 + t] : 0.0;
     // B operands: coordinate 4 kk + g of the candidate of lane r in block tl; |x - c|^2 of that candidate.  The blocks come in
@@ -390,6 +397,7 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
     // blocks and 8-byte stores: the kernel ran at 3.9 TB/s of panel writes whatever its instruction count, the rate of 8-byte
     // stores on this part -- MI355X_MICROARCH.md: 0.54-0.70 of the 16-byte rate.)
     double xb[4][KS], xn[4];
+    float xbf[4][KS];       // (BND: the FP32 images of xb for the screen)
 #pragma unroll
     for (int tp = 0; tp < 2; tp++) {
         double s0 = 0.0, s1 = 0.0;
@@ -397,6 +405,7 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
         for (int kk = 0; kk < KS; kk++) {
             const double2 v = *reinterpret_cast<const double2*>(Xcs + (int64_t)(4 * kk + g) * ldm + mb + 32 * tp + 2 * r);
             xb[2 * tp][kk] = v.x; xb[2 * tp + 1][kk] = v.y;
+            if (BND) { xbf[2 * tp][kk] = (float)v.x; xbf[2 * tp + 1][kk] = (float)v.y; }
             s0 = fma(v.x, v.x, s0); s1 = fma(v.y, v.y, s1);
         }
         s0 += __shfl_xor(s0, 16); s0 += __shfl_xor(s0, 32);
@@ -415,16 +424,78 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
     const int nvalid = left >= 128 ? 128 : (left > 0 ? (int)left : 0);      // training rows of this chunk (the rest: zero padding)
     double macc[4] = {0.0, 0.0, 0.0, 0.0};
     double sacc[4] = {0.0, 0.0, 0.0, 0.0};
-    unsigned nlive = 0;
+    unsigned nlive = 0, nfall = 0;
+    // THE SCREEN (BND, option "sweep_screen"): u of the block's 512 pairs once more in FP32, u32 = fmaf(-2 SC, dot32,
+    // fl32(xn + yn)) with dot32 from v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain) on the FP32 images of the operands.  With
+    // |u32 - u| <= delta for the u of the FP64 test below (sweep.hip: THE BOUND PASS derives delta), a block whose every u32
+    // lies in [ubnd + delta, uhi - delta] is one that test skips, and is skipped here: half the matrix-pipe time, and none of
+    // it on the FP64 datapath.  Every other block goes on to the FP64 test as before.  delta = 2^-24 (d + 8) SC (max |y'| +
+    // max |x'|)^2 over the workgroup's rows and the wave's candidates: one pair of thresholds per wave, rounded inwards.  A
+    // wave with a norm that is not finite, or so large that an FP32 image or u32 could overflow, does not screen: v_min3 /
+    // v_max3 drop NaNs, so the loop could not tell.
+    bool scr = false;
+    float lo32 = 0.0f, hi32 = 0.0f;
+    if (BND && screen) {
+        const double y0 = yn[lane], y1 = yn[lane + 64];
+        bool bad = !(y0 <= 1e36) || !(y1 <= 1e36);
+        double ym = fmax(y0, y1), xm = fmax(fmax(xn[0], xn[1]), fmax(xn[2], xn[3]));
+#pragma unroll
+        for (int tl = 0; tl < 4; tl++) bad = bad || !(xn[tl] <= 1e36);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { ym = fmax(ym, __shfl_xor(ym, o)); xm = fmax(xm, __shfl_xor(xm, o)); }
+        const double rs = sqrt(ym) + sqrt(xm);      // (yn and xn carry the factor SC)
+        const double delta = 5.9604644775390625e-08 * (double)(kp.d + 8) * rs * rs;
+        const double lo = ubnd + delta, hi = uhi - delta;
+        lo32 = (float)lo;
+        if ((double)lo32 < lo) lo32 = __uint_as_float(__float_as_uint(lo32) + 1u);       // (lo > 0: the next float up)
+        hi32 = (float)hi;
+        if ((double)hi32 > hi) hi32 = __uint_as_float(__float_as_uint(hi32) - 1u);       // (taken only for hi > 0, below: the next float down)
+        // (wave-uniform by construction; said so that the branch, the thresholds and the counter live in scalar registers)
+        scr = !__any(bad || !(hi > 0.0) || !(lo32 <= hi32));
+        lo32 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lo32)));
+        hi32 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(hi32)));
+    }
 #pragma unroll 1
     for (int j0 = 0; j0 < 128; j0 += 16) {
         double a[KS], ynq[4], alq[4];
+        if (!BND) {
 #pragma unroll
-        for (int kk = 0; kk < KS; kk++) a[kk] = Yl[(j0 + r) * S + 4 * kk + g];
+            for (int kk = 0; kk < KS; kk++) a[kk] = Yl[(j0 + r) * S + 4 * kk + g];
 #pragma unroll
-        for (int q = 0; q < 4; q++) { ynq[q] = yn[j0 + g + 4 * q]; alq[q] = al[j0 + g + 4 * q]; }
+            for (int q = 0; q < 4; q++) { ynq[q] = yn[j0 + g + 4 * q]; alq[q] = al[j0 + g + 4 * q]; }
+        }
 #pragma unroll
         for (int tp = 0; tp < 2; tp++) {
+            if (BND && scr) {
+                // (operands read per block and not kept over the FP64 code below: held for the second block they cost the
+                // kernel a wave per SIMD at DP = 16)
+                float af[KS];
+                double yns[4];      // (the FP32 instruction leaves rows 4 g + i with a lane, not g + 4 q)
+#pragma unroll
+                for (int kk = 0; kk < KS; kk++) af[kk] = Yf[(j0 + r) * SF + 4 * kk + g];
+#pragma unroll
+                for (int i = 0; i < 4; i++) yns[i] = yn[j0 + 4 * g + i];
+                v4f c0 = {0.0f, 0.0f, 0.0f, 0.0f}, c1 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int kk = 0; kk < KS; kk++) {       // (two chains side by side: the dependent latency is 40 cycles, the issue interval 32)
+                    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[kk], xbf[2 * tp][kk], c0, 0, 0, 0);
+                    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[kk], xbf[2 * tp + 1][kk], c1, 0, 0, 0);
+                }
+                float mn = __builtin_inff(), mx = -__builtin_inff();
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const float w0 = fmaf(-2.0f * (float)SC, c0[i], (float)(xn[2 * tp] + yns[i]));
+                    const float w1 = fmaf(-2.0f * (float)SC, c1[i], (float)(xn[2 * tp + 1] + yns[i]));
+                    mn = fminf(mn, fminf(w0, w1)); mx = fmaxf(mx, fmaxf(w0, w1));
+                }
+                if (!__any(!(mn >= lo32 && mx <= hi32))) continue;
+            }
+            if (BND) {      // (the bound pass reads its FP64 operands per live block: most blocks never need them)
+#pragma unroll
+                for (int kk = 0; kk < KS; kk++) a[kk] = Yl[(j0 + r) * S + 4 * kk + g];
+#pragma unroll
+                for (int q = 0; q < 4; q++) { ynq[q] = yn[j0 + g + 4 * q]; alq[q] = al[j0 + g + 4 * q]; }
+            }
             v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int kk = 0; kk < KS; kk++) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[2 * tp][kk], acc0, 0, 0, 0);
@@ -442,7 +513,7 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
                 if (BND) live = live || !(ue0[q] >= ubnd && ue0[q] <= uhi) || !(ue1[q] >= ubnd && ue1[q] <= uhi);
             }
             if (BND) {
-                if (!__any(live)) continue;
+                if (!__any(live)) { if (screen) nfall++; continue; }
                 nlive++;
             }
 #pragma unroll
@@ -493,6 +564,9 @@ __global__ __launch_bounds__(256) void cross_build_mfma_kernel(
         }
     }
     if (BND && lane == 0 && nlive) atomicAdd(live_cnt, (unsigned long long)nlive);
+    // (the blocks the screen left to the FP64 test, which skipped them: few.  Counting the certified ones instead is one atomic
+    // per wave on one address, 16384 a launch: that alone took longer than the kernel)
+    if (BND && lane == 0 && nfall) atomicAdd(live_cnt + 1, (unsigned long long)nfall);      // (DSEL_FALL follows DSEL_LIVE)
 }
 // centred scaled training rows for cross_build_mfma_kernel: Ycs[i][k] = (X[i][k] - c_k) / l_k, zero rows / columns as padding
 __global__ __launch_bounds__(256) void center_train_kernel(const double* __restrict__ X, double* __restrict__ Ycs, int64_t N, int64_t Np, int d,
@@ -583,9 +657,11 @@ int launch_cross_build_mfma(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t
 }
 
 // The bound pass of a pruned sweep (cross_build_mfma_kernel<.., HYB, BND>): mean partials over the live blocks, their sums of
-// |alpha_j v_j| (sabs_part, same layout) and the live-block count (added to *live_cnt).  After launch_cross_prepare.
+// |alpha_j v_j| (sabs_part, same layout) and the live-block count (added to live_cnt[0]; with the FP32 screen, option
+// "sweep_screen", the blocks it left to the FP64 test and that test skipped to live_cnt[1]).  After launch_cross_prepare.
 int launch_cross_mean_bound(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, double* mean_part, double* sabs_part,
                             double ubnd, double uhi, unsigned long long* live_cnt) {
+    const int screen = ctx->opt_sweep_screen;
     hipStream_t st = ctx->stream;
     KernParams kp;
     int dsel = 0;
@@ -593,7 +669,7 @@ int launch_cross_mean_bound(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t
     GPRY_TRY(center_cands(ctx, Xc, m0, mc, 1, &kp, &dsel, &ldm));
     dim3 grid((unsigned)((mc + 255) / 256), (unsigned)(ctx->Np / 128));
 #define CB2(DP, KID) hipLaunchKernelGGL((cross_build_mfma_kernel<DP, KID, true, true>), grid, dim3(256), 0, st, ctx->dXcs, ldm, mc, ctx->dYcs, \
-                                        ctx->dalpha_, nullptr, mc, mean_part, kp, 100.0 * corr_scale<KID>(), ubnd, uhi, sabs_part, live_cnt)
+                                        ctx->dalpha_, nullptr, mc, mean_part, kp, 100.0 * corr_scale<KID>(), ubnd, uhi, sabs_part, live_cnt, screen)
 #define CB4(KID) { if (dsel == 4) CB2(4, KID); else if (dsel == 8) CB2(8, KID); else if (dsel == 16) CB2(16, KID); \
                    else if (dsel == 24) CB2(24, KID); else CB2(32, KID); }
     DISPATCH_KID(ctx->kernel_id, CB4)

@@ -324,6 +324,22 @@ static int choose_panel_form(gpry_ctx* ctx, bool small_build) {
 //     <= y_part + (1 + 2 gamma) D + 3 gamma S -- the slack, added and rounded up (sweep_mean_bound_kernel).
 // A bound only moves the candidate up the ranking (more survivors); it never changes a record.  Not taken for a model
 // whose weights or scales are not finite, y_std <= 0 or zeta < 0 (the acquisition would not be monotone in y).
+// THE SCREEN (option "sweep_screen", kernel_build.hip) skips a block before that test where u32 = fmaf(-2 s, dot32,
+// fl32(xn + yn)) of every pair lies in [ubnd + delta, uhi - delta]; it certifies only blocks the FP64 test would skip, so the
+// skipped set is a subset of the one above and nothing in this proof changes.  delta bounds |u32 - u| for the u of the FP64
+// test, with e = 2^-24, a = |x'|, b = |y'| (centred scaled, a b <= (a + b)^2 / 4, a^2 + b^2 <= (a + b)^2):
+//   * the FP32 images move each coordinate by a factor 1 + e at most: the exact dot product of the images is within
+//     (2 e + e^2) a b of x'.y', which is <= 4.1 e s a b in -2 s x'.y', i.e. <= 1.03 e s (a + b)^2;
+//   * dot32 is a fmaf chain over the d coordinates that are not padding (zero products round nothing): within
+//     gamma_d sum |x~ y~| <= 1.01 d e a b of that exact product, <= 0.51 d e s (a + b)^2 after the factor 2 s;
+//   * fl32(xn + yn) rounds the FP64 sum once, <= e s (a^2 + b^2) (1 + 2^-50) <= 1.01 e s (a + b)^2; the last fmaf rounds once,
+//     <= e |u32| <= 1.01 e s (a + b)^2 (|u32| <= s (a + b)^2 (1 + d e));
+//   * the FP64 u itself is within 4 * 2^-53 s (a^2 + b^2) of the exact value (kernel_build.hip), 1e-8 of the terms above.
+// In all <= (d / 2 + 3.1) e s (a + b)^2; delta = e (d + 8) s (max b + max a)^2, the maxima over the workgroup's rows and
+// the wave's candidates, has more than twice that, which also covers the FP64 roundings of delta and the two thresholds
+// themselves (these are then rounded inwards to FP32), and FP32 underflow: at most 2^-149 per operation, times a + b, where a
+// certified block has s (a + b)^2 >= ubnd >= 50 and so delta > 2e-5.  No FP32 value overflows: the screen is off for a wave whose norms
+// exceed 1e36 or are not finite.
 struct MeanBound { bool on = false; double ubnd = 0.0, uhi = 0.0, D1 = 0.0, g3 = 0.0; };
 static MeanBound mean_bound_setup(const gpry_ctx* ctx, const SweepRequest& rq, const FinishParams& fp, int nt) {
     MeanBound b;
@@ -443,11 +459,11 @@ int run_sweep(gpry_ctx* ctx, int64_t M, const SweepRequest& rq) {
     if (stage_a) ctx->prune.form = form;
     const MeanBound mb = mean_bound_setup(ctx, rq, fp, nt);
     unsigned long long* live_cnt = nullptr;
-    if (stage_a) { ctx->prune.ybound = mb.on ? 1 : 0; ctx->prune.live_blocks = 0; ctx->prune.blocks = 0; }
+    if (stage_a) { ctx->prune.ybound = mb.on ? 1 : 0; ctx->prune.live_blocks = 0; ctx->prune.blocks = 0; ctx->prune.cert_blocks = 0; }
     if (mb.on) {
         if (!ctx->dsel) GPRY_TRY(dev_alloc(ctx, &ctx->dsel, gpry_ctx::DSEL_WORDS));
         live_cnt = ctx->dsel + gpry_ctx::DSEL_LIVE;
-        HIP_TRY(ctx, hipMemsetAsync(live_cnt, 0, 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(live_cnt, 0, 16, ctx->stream));       // (DSEL_LIVE and DSEL_FALL)
         if (getenv("GPRY_HIP_DEBUG_PANEL"))
             fprintf(stderr, "gpry: bound pass: u in [%.6g, %.3g] skipped, D %.3g, gamma %.3g\n", mb.ubnd, mb.uhi, mb.D1, mb.g3 / 3.0);
     }
@@ -492,6 +508,9 @@ int run_sweep(gpry_ctx* ctx, int64_t M, const SweepRequest& rq) {
         if (stage_a) Kst = nullptr;         // (the kernels store the mean partials only)
         if (y_given) mean_part = nullptr;   // (... or the panel only)
         if (mb.on) {                        // (bound partials, the sums of |terms| in the place of the sigma partials)
+            // The blocks cross_build_mfma_kernel<.., BND> walks in this launch: grid.x workgroups of 4 waves, nt row chunks, and per
+            // wave 8 steps of 16 rows x 2 blocks of 32 candidates.  sweep_impl derives the certified blocks from this count (all -
+            // live - skipped by the FP64 test), so it has to follow the kernel's loop and launch_cross_mean_bound's grid.
             ctx->prune.blocks += (int64_t)((mcp + 255) / 256) * 4 * nt * 16;
             return launch_cross_mean_bound(ctx, ctx->dXc, m0, mcp, mean_part, mean_part + (int64_t)nt_mean * chunk, mb.ubnd, mb.uhi, live_cnt);
         }
@@ -701,7 +720,7 @@ int prune_complete(gpry_ctx* ctx) {
 }
 
 // The tail of a sweep entry point: the NaNs of nan_src counted into *nn (nan_src NULL: not counted), the live blocks of the
-// bound pass into *live (NULL: not fetched), the arrays the caller wants copied out, one synchronisation.
+// bound pass and the blocks only its FP64 test skipped into live[0] and live[1] (NULL: not fetched), the arrays the caller wants copied out, one synchronisation.
 static int sweep_copy_out(gpry_ctx* ctx, int64_t M, const double* nan_src, unsigned long long* nn, unsigned long long* live,
                           double* y_all, double* sigma_all, double* acq_all) {
     if (nan_src) {
@@ -711,7 +730,7 @@ static int sweep_copy_out(gpry_ctx* ctx, int64_t M, const double* nan_src, unsig
         hipLaunchKernelGGL(count_nan_kernel, dim3(1024), dim3(256), 0, ctx->stream, nan_src, M, dnan);
         HIP_TRY(ctx, hipMemcpyAsync(nn, dnan, 8, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (live) HIP_TRY(ctx, hipMemcpyAsync(live, ctx->dsel + gpry_ctx::DSEL_LIVE, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (live) HIP_TRY(ctx, hipMemcpyAsync(live, ctx->dsel + gpry_ctx::DSEL_LIVE, 16, hipMemcpyDeviceToHost, ctx->stream));
     if (y_all) HIP_TRY(ctx, hipMemcpyAsync(y_all, ctx->dy_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (sigma_all) HIP_TRY(ctx, hipMemcpyAsync(sigma_all, ctx->dsig_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
     if (acq_all) HIP_TRY(ctx, hipMemcpyAsync(acq_all, ctx->dacq_all, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
@@ -766,8 +785,8 @@ static int sweep_impl(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
     // NaN per-tile sum needs a NaN in V or in the candidate's panel column, and either one reaches y -- alpha_ = V^T V y
     // picks up every entry of V in alpha_[0], and a NaN panel entry enters the mean partial through fma(alpha_j, k, .), NaN
     // for any alpha_j.  The rest of the finish keeps var in [0, C]: the acquisition is finite or -inf.)
-    unsigned long long nn = 0, live = 0;
-    GPRY_TRY(sweep_copy_out(ctx, M, prune ? ctx->dub : ctx->dacq_all, &nn, prune && ctx->prune.ybound ? &live : nullptr,
+    unsigned long long nn = 0, live[2] = {0, 0};
+    GPRY_TRY(sweep_copy_out(ctx, M, prune ? ctx->dub : ctx->dacq_all, &nn, prune && ctx->prune.ybound ? live : nullptr,
                             y_all, sigma_all, acq_all));
     upload_scope.done = true;
     if (n_nan) *n_nan = (int64_t)nn;
@@ -777,7 +796,9 @@ static int sweep_impl(gpry_ctx* ctx, const double* X, int64_t M, const uint8_t* 
         ctx->prune = gpry_ctx::PruneState();
         ctx->prune.form = form;
         ctx->prune.ybound = ybound;
-        ctx->prune.live_blocks = ybound ? (int64_t)live : 0;
+        ctx->prune.live_blocks = ybound ? (int64_t)live[0] : 0;
+        // (every block is certified by the screen, skipped by the FP64 test or live)
+        ctx->prune.cert_blocks = ybound && ctx->opt_sweep_screen ? blocks - (int64_t)live[0] - (int64_t)live[1] : 0;
         ctx->prune.blocks = ybound ? blocks : 0;
         ctx->prune.have_mask = rq.have_mask ? 1 : 0;
         ctx->prune.fp = finish_params(ctx, rq);

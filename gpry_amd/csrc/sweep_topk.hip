@@ -553,3 +553,11 @@ extern "C" int gpry_sweep_prune_info(gpry_ctx* ctx, int64_t* info, double* dinfo
     }
     return 0;
 }
+
+extern "C" int gpry_sweep_screen_info(gpry_ctx* ctx, int64_t out[2]) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_sweep_screen_info: ctx is NULL");
+    if (!out) return gpry_fail(ctx, -1, "sweep_screen_info: out must not be NULL");
+    out[0] = ctx->prune.cert_blocks;
+    out[1] = ctx->prune.blocks;
+    return 0;
+}

@@ -897,6 +897,11 @@ class NORA(GenericGPAcquisition):
         pruned_on = getattr(self, "_pruned_on", [])
         if pruned_on:
             self.stats["prune"] = [t.sweep_prune_info() for t in pruned_on]
+            for t, st in zip(pruned_on, self.stats["prune"]):
+                # blocks the FP32 screen of the bound pass certified.  (_prune_targets takes any object with sweep_prune_info:
+                # the stand-in devices of tests/test_sweep_prune_cpu.py have that method and not this one)
+                if hasattr(t, "sweep_screen_info"):
+                    st["certified"] = t.sweep_screen_info()["certified"]
         else:
             self.stats.pop("prune", None)
         merged = self.pool.copy(drop_empty=True)

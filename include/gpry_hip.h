@@ -151,6 +151,9 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *                             adds a rigorous slack for them and for rounding, and computes y exactly only for the candidates it
  *                             contracts (same records and, after gpry_sweep_fetch, the same arrays bit for bit).  0: y exactly for
  *                             every candidate in the mean pass
+ *     "sweep_screen" 0/1      1 (default): that mean pass certifies far blocks with an exact FP32 matrix product and a rigorous
+ *                             margin in front of its FP64 test (gpry_sweep_screen_info); 0: the FP64 test alone (the comparator:
+ *                             the same blocks are skipped, every array is the same bit for bit)
  *     "sweep_small_map" 0/1   1 (default): a one-pass contraction of at most 512 tiles of 128 x 128 (the compact batches of a pruned
  *                             sweep) launches one workgroup per tile, longest row tile first, consecutive candidate tiles on
  *                             different XCDs; 0: the super-tile map of the large launches (the comparator).  A row tile walks k in
@@ -769,6 +772,9 @@ int gpry_sweep_topk(gpry_ctx* ctx, int64_t Kp, const int64_t* exclude, int64_t n
  * completion use a copy of the model taken at the end of the sweep: a refit or refactorisation in between does not change
  * what they compute. */
 int gpry_sweep_prune_info(gpry_ctx* ctx, int64_t* info, double* dinfo);
+/* The FP32 screen of that mean pass (option "sweep_screen") in the last pruned sweep: out[0] blocks it certified as skipped
+ * without the FP64 test, out[1] blocks the pass saw ([10] above).  out[0] <= [10] - [9]; 0 where the pass did not bound y. */
+int gpry_sweep_screen_info(gpry_ctx* ctx, int64_t out[2]);
 
 /* ---- a14/a15: Kriging-believer support (bordered factor instead of deepcopy+refit) - */
 /* Start a session on the current factor; drops any registered candidates. */
