@@ -197,6 +197,17 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ptrs(arrays, *keys):
+    """The pointers of ``arrays[key]`` in the order of ``keys``, NULL for a key that is not there."""
+    return [_ptr(arrays.get(k)) for k in keys]
+
+
+# the output arguments that the chain entry points / the maximisers have in common, in the order of the C prototypes
+_CHAIN_OUT = ("X", "y", "X_last", "y_last", "naccept", "ncalls")
+_BFGS_OUT = ("iters", "ncalls", "ngrad", "status")
+_BFGS_TR = ("G_tr", "nhalv_tr", "reset_tr")
+
+
 def _f64(a, shape=None):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if shape is not None and a.shape != shape:
@@ -547,30 +558,59 @@ class Device:
                     "gpry_ns_knn")
         return nbr, ms.value
 
+    # -- what the chain and the maximiser wrappers below share ---------------------------------
+    def _starts(self, X0, what="start states", count="nchains"):
+        """``X0`` as a contiguous (count, d) float64 array."""
+        X0 = _f64(X0)
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise ValueError(f"expected {what} of shape ({count}, {self.d}), got {X0.shape}")
+        return X0
+
+    @staticmethod
+    def _chain_out(n, d, nsteps, thin, proposals, **own):
+        """The output dict of a chain call: the records, the last states and the counters, then the entry point's
+        ``own`` arrays, then (``proposals``) ``X_prop`` / ``y_prop``."""
+        nrec = nsteps // thin if thin > 0 else 0
+        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
+                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64), **own)
+        if proposals:
+            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)))
+        return out
+
+    def _bfgs_io(self, X0, fixed, H0, max_iter, hooks, values):
+        """Checked (X0, fixed, H0) of a maximiser call, its output dict -- ``X``, the ``values`` (nstart,), ``G``, the
+        counters and ``status`` -- and the trace dict (empty without ``hooks``; the value's trace is values[0] + "_tr")."""
+        X0 = self._starts(X0, "starts", "nstart")
+        n, d = X0.shape
+        H0 = _f64(H0, (d, d))
+        fixed = np.ascontiguousarray(fixed)
+        if fixed.shape != (d,) or fixed.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise ValueError(f"expected a boolean mask of shape ({d},), got {fixed.dtype} {fixed.shape}")
+        out = dict(X=np.empty((n, d)), **{v: np.empty(n) for v in values}, G=np.empty((n, d)), iters=np.zeros(n, np.int32),
+                   ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
+        tr = {}
+        if hooks:
+            m = max(max_iter, 0)
+            tr = {"U_tr": np.empty((n, m + 1, d)), values[0] + "_tr": np.empty((n, m + 1)), "G_tr": np.empty((n, m + 1, d)),
+                  "nhalv_tr": np.empty((n, m), np.int32), "reset_tr": np.empty((n, m), np.int32)}
+        return X0, fixed.astype(np.uint8), H0, out, tr
+
     # -- Metropolis MCMC of the mean (gpry_amd/mcmc.py drives this one) ---------------------
     def mcmc_chains(self, lo, hi, X0, y0, Lp, T, minus_inf_value, seed, batch, nsteps, thin, proposals=False):
         """``nsteps`` Metropolis steps of ``len(X0)`` chains from the states (X0, y0) (y0 NaN: evaluated first), proposal
         u' = u + Lp z in unit-cube coordinates: a dict with ``X`` (nchains, nsteps // thin, d) and ``y`` (nchains,
         nsteps // thin), the states after every thin-th step; ``X_last`` / ``y_last``, ``naccept`` / ``ncalls`` per chain;
         ``device_ms``; with ``proposals`` also ``X_prop`` (nchains, nsteps, d) and ``y_prop`` (NaN: not evaluated)."""
-        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
-        X0 = _f64(X0)
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise ValueError(f"expected start states of shape (nchains, {self.d}), got {X0.shape}")
+        lo, hi, X0 = _f64(lo, (self.d,)), _f64(hi, (self.d,)), self._starts(X0)
         n, d = X0.shape
         y0, Lp = _f64(y0, (n,)), _f64(Lp, (d, d))
         nsteps, thin = int(nsteps), int(thin)
-        nrec = nsteps // thin if thin > 0 else 0
-        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
-                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64))
-        if proposals:
-            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)))
+        out = self._chain_out(n, d, nsteps, thin, proposals)
         ms = C.c_double(0.0)
         self._check(self._lib.gpry_mcmc_chains(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(Lp), float(T),
                                                float(minus_inf_value), int(seed), int(batch), nsteps, thin,
-                                               _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]), _ptr(out["y_last"]),
-                                               _ptr(out["naccept"]), _ptr(out["ncalls"]), _ptr(out.get("X_prop")),
-                                               _ptr(out.get("y_prop")), C.byref(ms)), "gpry_mcmc_chains")
+                                               *_ptrs(out, *_CHAIN_OUT, "X_prop", "y_prop"), C.byref(ms)),
+                    "gpry_mcmc_chains")
         out["device_ms"] = ms.value
         return out
 
@@ -583,33 +623,25 @@ class Device:
         ``nswap_try`` / ``nswap_acc`` (nladders, nrungs - 1); with ``proposals`` also ``X_prop``, ``y_prop`` and
         ``swap_log`` (nladders, nsteps // swap_every, nrungs - 1): 1 accepted, 0 rejected, -1 not tried
         (gpry_mcmc_ladders)."""
-        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
-        X0 = _f64(X0)
+        lo, hi, X0 = _f64(lo, (self.d,)), _f64(hi, (self.d,)), self._starts(X0)
         nrungs = int(nrungs)
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise ValueError(f"expected start states of shape (nchains, {self.d}), got {X0.shape}")
         n, d = X0.shape
         if nrungs < 1 or n % nrungs:
             raise ValueError(f"{n} start states do not form ladders of nrungs = {nrungs}")
         nl = n // nrungs
         y0, Lp, T = _f64(y0, (n,)), _f64(Lp, (nrungs, d, d)), _f64(T, (nrungs,))
         nsteps, thin, swap_every = int(nsteps), int(thin), int(swap_every)
-        nrec = nsteps // thin if thin > 0 else 0
-        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
-                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64),
-                   nswap_try=np.zeros((nl, nrungs - 1), np.int64), nswap_acc=np.zeros((nl, nrungs - 1), np.int64))
+        out = self._chain_out(n, d, nsteps, thin, proposals, nswap_try=np.zeros((nl, nrungs - 1), np.int64),
+                              nswap_acc=np.zeros((nl, nrungs - 1), np.int64))
         log = None
         if proposals:
-            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)),
-                       swap_log=np.full((nl, nsteps // swap_every if swap_every > 0 else 0, nrungs - 1), -1, np.int8))
+            out["swap_log"] = np.full((nl, nsteps // swap_every if swap_every > 0 else 0, nrungs - 1), -1, np.int8)
             log = out["swap_log"] if swap_every > 0 else None
         ms = C.c_double(0.0)
         self._check(self._lib.gpry_mcmc_ladders(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), nl, nrungs, _ptr(Lp),
                                                 _ptr(T), float(minus_inf_value), int(seed), int(batch), nsteps, thin,
-                                                swap_every, _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]),
-                                                _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
-                                                _ptr(out["nswap_try"]), _ptr(out["nswap_acc"]), _ptr(out.get("X_prop")),
-                                                _ptr(out.get("y_prop")), _ptr(log), C.byref(ms)), "gpry_mcmc_ladders")
+                                                swap_every, *_ptrs(out, *_CHAIN_OUT, "nswap_try", "nswap_acc", "X_prop",
+                                                                   "y_prop"), _ptr(log), C.byref(ms)), "gpry_mcmc_ladders")
         out["device_ms"] = ms.value
         return out
 
@@ -624,19 +656,13 @@ class Device:
         ``reflect``: the drifts reflect at the walls of the box, at most ``max_reflect`` (1 .. 1024) times each, instead of
         rejecting the trajectory that leaves it, and the dict gains ``nreflect``, the reflections per chain
         (gpry_hmc_chains_reflect)."""
-        lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
-        X0 = _f64(X0)
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise ValueError(f"expected start states of shape (nchains, {self.d}), got {X0.shape}")
+        lo, hi, X0 = _f64(lo, (self.d,)), _f64(hi, (self.d,)), self._starts(X0)
         n, d = X0.shape
         y0, Lp = _f64(y0, (n,)), _f64(Lp, (d, d))
         nsteps, thin = int(nsteps), int(thin)
-        nrec = nsteps // thin if thin > 0 else 0
-        out = dict(X=np.empty((n, nrec, d)), y=np.empty((n, nrec)), X_last=np.empty((n, d)), y_last=np.empty(n),
-                   naccept=np.zeros(n, np.int64), ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64))
+        out = self._chain_out(n, d, nsteps, thin, hooks, ngrad=np.zeros(n, np.int64))
         if hooks:
-            out.update(X_prop=np.empty((n, nsteps, d)), y_prop=np.empty((n, nsteps)), dH_prop=np.empty((n, nsteps)),
-                       G0=np.empty((n, d)))
+            out.update(dH_prop=np.empty((n, nsteps)), G0=np.empty((n, d)))
         ms = C.c_double(0.0)
         name, own = "gpry_hmc_chains", []
         if reflect:
@@ -644,10 +670,8 @@ class Device:
             name, own = "gpry_hmc_chains_reflect", [1, int(max_reflect), _ptr(out["nreflect"])]
         self._check(getattr(self._lib, name)(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(Lp), float(eps),
                                              int(nleap), float(T), float(minus_inf_value), int(seed), int(batch), nsteps,
-                                             thin, _ptr(out["X"]), _ptr(out["y"]), _ptr(out["X_last"]),
-                                             _ptr(out["y_last"]), _ptr(out["naccept"]), _ptr(out["ncalls"]),
-                                             _ptr(out["ngrad"]), _ptr(out.get("X_prop")), _ptr(out.get("y_prop")),
-                                             _ptr(out.get("dH_prop")), _ptr(out.get("G0")), *own, C.byref(ms)), name)
+                                             thin, *_ptrs(out, *_CHAIN_OUT, "ngrad", "X_prop", "y_prop", "dH_prop", "G0"),
+                                             *own, C.byref(ms)), name)
         out["device_ms"] = ms.value
         return out
 
@@ -660,31 +684,14 @@ class Device:
         ``hooks`` also the traces ``U_tr`` (nstart, max_iter + 1, d), ``y_tr``, ``G_tr``, ``nhalv_tr`` and ``reset_tr``
         (nstart, max_iter), unused slots NaN / -1."""
         lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
-        X0 = _f64(X0)
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise ValueError(f"expected starts of shape (nstart, {self.d}), got {X0.shape}")
-        n, d = X0.shape
-        y0, H0 = _f64(y0, (n,)), _f64(H0, (d, d))
-        fixed = np.ascontiguousarray(fixed)
-        if fixed.shape != (d,) or fixed.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-            raise ValueError(f"expected a boolean mask of shape ({d},), got {fixed.dtype} {fixed.shape}")
-        fixed = fixed.astype(np.uint8)
         max_iter, max_halvings = int(max_iter), int(max_halvings)
-        out = dict(X=np.empty((n, d)), y=np.empty(n), G=np.empty((n, d)), iters=np.zeros(n, np.int32),
-                   ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
-        tr = {}
-        if hooks:
-            m = max(max_iter, 0)
-            tr = dict(U_tr=np.empty((n, m + 1, d)), y_tr=np.empty((n, m + 1)), G_tr=np.empty((n, m + 1, d)),
-                      nhalv_tr=np.empty((n, m), np.int32), reset_tr=np.empty((n, m), np.int32))
-        ms = C.c_double(0.0)
+        X0, fixed, H0, out, tr = self._bfgs_io(X0, fixed, H0, max_iter, hooks, ("y",))
+        n = len(X0)
+        y0, ms = _f64(y0, (n,)), C.c_double(0.0)
         self._check(self._lib.gpry_maximize_mean(self._h, _ptr(lo), _ptr(hi), _ptr(X0), _ptr(y0), n, _ptr(fixed), _ptr(H0),
                                                  max_iter, max_halvings, float(gtol), float(ftol), float(minus_inf_value),
-                                                 _ptr(out["X"]), _ptr(out["y"]), _ptr(out["G"]), _ptr(out["iters"]),
-                                                 _ptr(out["ncalls"]), _ptr(out["ngrad"]), _ptr(out["status"]),
-                                                 _ptr(tr.get("U_tr")), _ptr(tr.get("y_tr")), _ptr(tr.get("G_tr")),
-                                                 _ptr(tr.get("nhalv_tr")), _ptr(tr.get("reset_tr")), C.byref(ms)),
-                    "gpry_maximize_mean")
+                                                 *_ptrs(out, "X", "y", "G", *_BFGS_OUT),
+                                                 *_ptrs(tr, "U_tr", "y_tr", *_BFGS_TR), C.byref(ms)), "gpry_maximize_mean")
         out.update(tr)
         out["device_ms"] = ms.value
         return out
@@ -699,33 +706,14 @@ class Device:
         (``MAX_STATUS``) and ``device_ms``; with ``hooks`` also the traces ``U_tr`` (nstart, max_iter + 1, d), ``a_tr``,
         ``G_tr``, ``nhalv_tr`` and ``reset_tr`` (nstart, max_iter), unused slots NaN / -1."""
         lo, hi = _f64(lo, (self.d,)), _f64(hi, (self.d,))
-        X0 = _f64(X0)
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise ValueError(f"expected starts of shape (nstart, {self.d}), got {X0.shape}")
-        n, d = X0.shape
-        H0 = _f64(H0, (d, d))
-        fixed = np.ascontiguousarray(fixed)
-        if fixed.shape != (d,) or fixed.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-            raise ValueError(f"expected a boolean mask of shape ({d},), got {fixed.dtype} {fixed.shape}")
-        fixed = fixed.astype(np.uint8)
         max_iter, max_halvings = int(max_iter), int(max_halvings)
-        out = dict(X=np.empty((n, d)), a=np.empty(n), y=np.empty(n), sigma=np.empty(n), G=np.empty((n, d)),
-                   iters=np.zeros(n, np.int32), ncalls=np.zeros(n, np.int64), ngrad=np.zeros(n, np.int64),
-                   status=np.zeros(n, np.int32))
-        tr = {}
-        if hooks:
-            m = max(max_iter, 0)
-            tr = dict(U_tr=np.empty((n, m + 1, d)), a_tr=np.empty((n, m + 1)), G_tr=np.empty((n, m + 1, d)),
-                      nhalv_tr=np.empty((n, m), np.int32), reset_tr=np.empty((n, m), np.int32))
+        X0, fixed, H0, out, tr = self._bfgs_io(X0, fixed, H0, max_iter, hooks, ("a", "y", "sigma"))
         ms = C.c_double(0.0)
-        self._check(self._lib.gpry_maximize_acq(self._h, _ptr(lo), _ptr(hi), _ptr(X0), n, _ptr(fixed), _ptr(H0), float(zeta),
-                                                float(baseline), float(sigma_n), max_iter, max_halvings, float(gtol),
-                                                float(ftol), float(minus_inf_value), _ptr(out["X"]), _ptr(out["a"]),
-                                                _ptr(out["y"]), _ptr(out["sigma"]), _ptr(out["G"]), _ptr(out["iters"]),
-                                                _ptr(out["ncalls"]), _ptr(out["ngrad"]), _ptr(out["status"]),
-                                                _ptr(tr.get("U_tr")), _ptr(tr.get("a_tr")), _ptr(tr.get("G_tr")),
-                                                _ptr(tr.get("nhalv_tr")), _ptr(tr.get("reset_tr")), C.byref(ms)),
-                    "gpry_maximize_acq")
+        self._check(self._lib.gpry_maximize_acq(self._h, _ptr(lo), _ptr(hi), _ptr(X0), len(X0), _ptr(fixed), _ptr(H0),
+                                                float(zeta), float(baseline), float(sigma_n), max_iter, max_halvings,
+                                                float(gtol), float(ftol), float(minus_inf_value),
+                                                *_ptrs(out, "X", "a", "y", "sigma", "G", *_BFGS_OUT),
+                                                *_ptrs(tr, "U_tr", "a_tr", *_BFGS_TR), C.byref(ms)), "gpry_maximize_acq")
         out.update(tr)
         out["device_ms"] = ms.value
         return out

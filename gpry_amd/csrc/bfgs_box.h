@@ -290,3 +290,39 @@ __device__ __forceinline__ void bfgs_box_run(Obj& obj, const NsArgs& a, int d, c
         out.status[c] = status;
     }
 }
+
+// ---- host side -----------------------------------------------------------------------------------
+// What gpry_maximize_mean and gpry_maximize_acq check alike; `hk`: the caller's trace arrays (host pointers).
+static int bfgs_check(gpry_ctx* ctx, const char* who, int64_t nstart, const BfgsCtl& ctl, const double* H0, const BfgsHooks& hk) {
+    const bool hooks = hk.U_tr != nullptr;
+    if ((hk.v_tr != nullptr) != hooks || (hk.G_tr != nullptr) != hooks || (hk.nhalv_tr != nullptr) != hooks ||
+        (hk.reset_tr != nullptr) != hooks)
+        return gpry_fail(ctx, -1, "%s: the trace hooks are all NULL or all given", who);
+    if (nstart < 1 || nstart > 0x7fffffffll || ctl.max_iter < 0 || ctl.max_iter > 100000 || ctl.max_halvings < 0 ||
+        ctl.max_halvings > 1000)
+        return gpry_fail(ctx, -1, "%s: nstart = %lld, max_iter = %d, max_halvings = %d", who, (long long)nstart, ctl.max_iter,
+                         ctl.max_halvings);
+    if (!(ctl.gtol >= 0.0) || !isfinite(ctl.gtol)) return gpry_fail(ctx, -1, "%s: gtol = %g", who, ctl.gtol);
+    if (!(ctl.ftol >= 0.0) || !isfinite(ctl.ftol)) return gpry_fail(ctx, -1, "%s: ftol = %g", who, ctl.ftol);
+    for (int e = 0; e < ctx->d * ctx->d; e++)
+        if (!isfinite(H0[e])) return gpry_fail(ctx, -1, "%s: H0 has an entry that is not finite", who);
+    return 0;
+}
+
+// Declares bfgs_box_run's outputs (`out`: the caller's arrays) and, where given, its traces (`hk`, likewise) on `st`
+// behind what the caller has declared, begins the stage and hands back the same two structs with the device's pointers.
+// Unused trace slots start as 0xff bytes: NaN and -1.
+static int bfgs_begin(NsStage& st, int64_t n, int d, int max_iter, BfgsOut* out, BfgsHooks* hk) {
+    const int64_t m1 = max_iter + 1, m0 = max_iter;
+    const auto rX = st.out(out->X_out, n * d), rv = st.out(out->v_out, n), rG = st.out(out->G_out, n * d);
+    const auto rit = st.out(out->iters, n);
+    const auto rnc = st.out(out->ncalls, n), rgr = st.out(out->ngrad, n);
+    const auto rst = st.out(out->status, n);
+    const auto rU = st.out(hk->U_tr, n * m1 * d, 0xff), rvt = st.out(hk->v_tr, n * m1, 0xff);
+    const auto rGt = st.out(hk->G_tr, n * m1 * d, 0xff);
+    const auto rnh = st.out(hk->nhalv_tr, n * m0, 0xff), rrs = st.out(hk->reset_tr, n * m0, 0xff);
+    GPRY_TRY(st.begin());
+    *out = {st.dev(rX), st.dev(rv), st.dev(rG), st.dev(rit), st.dev(rnc), st.dev(rgr), st.dev(rst)};
+    *hk = {st.dev(rU), st.dev(rvt), st.dev(rGt), st.dev(rnh), st.dev(rrs)};
+    return 0;
+}

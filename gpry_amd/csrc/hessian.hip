@@ -176,29 +176,16 @@ int gpry_hessian_mean(gpry_ctx* ctx, const double* X, int64_t npts, double* y_ou
     for (int k = 0; k < GPRY_MAX_DIM; k++) { lo[k] = 0.0; hi[k] = 1.0; }
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "gpry_hessian_mean", lo, hi, 0, &a, &kp, &ap));
-    // one buffer: [X | y | g | H]
-    const int64_t sz[4] = {8 * n * d, 8 * n, 8 * n * d, 8 * n * d * d};
-    int64_t off[5];
-    ns_layout(sz, off);
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[4]));
-    char* b = (char*)ctx->dmc;
-    HIP_TRY(ctx, hipMemcpyAsync(b + off[0], X, sz[0], hipMemcpyHostToDevice, ctx->stream));
-    const double* dX = (const double*)(b + off[0]);
-    double* dy = (double*)(b + off[1]);
-    double* dg = (double*)(b + off[2]);
-    double* dH = (double*)(b + off[3]);
+    NsStage st(ctx);
+    const auto rX = st.in(X, n * d);
+    const auto ry = st.out(y_out, n), rg = st.out(g_out, n * d), rH = st.out(H_out, n * d * d);
+    GPRY_TRY(st.begin());
 #define HS(DP, KID) \
-    hipLaunchKernelGGL((hessian_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX, dy, dg, dH)
+    hipLaunchKernelGGL((hessian_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, st.dev(rX), \
+                       st.dev(ry), st.dev(rg), st.dev(rH))
     DISPATCH_DP_KID(d, ctx->kernel_id, HS)
 #undef HS
-    HIP_TRY(ctx, hipGetLastError());
-    void* dst[3] = {y_out, g_out, H_out};
-    for (int i = 1; i < 4; i++)
-        HIP_TRY(ctx, hipMemcpyAsync(dst[i - 1], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    return 0;
+    return st.end(device_ms);
 }
 
 }  // extern "C"

@@ -239,70 +239,39 @@ int gpry_hmc_chains_reflect(gpry_ctx* ctx, const double* lo, const double* hi, c
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_hmc_chains: ctx is NULL");
     if (!lo || !hi || !X0 || !y0 || !Lp || !X_last || !y_last || !naccept || !ncalls || !ngrad)
         return gpry_fail(ctx, -1, "gpry_hmc_chains: NULL argument");
-    if ((X_prop == nullptr) != (y_prop == nullptr))
-        return gpry_fail(ctx, -1, "gpry_hmc_chains: X_prop and y_prop are both NULL or both given");
-    if (nchains < 1 || nchains > 0x7fffffffll || nsteps < 0 || thin < 1 || batch < 0 || batch > 0xffffffffll)
-        return gpry_fail(ctx, -1, "gpry_hmc_chains: nchains = %lld, nsteps = %d, thin = %d, batch = %lld",
-                         (long long)nchains, nsteps, thin, (long long)batch);
-    if (!(T > 0.0) || !isfinite(T)) return gpry_fail(ctx, -1, "gpry_hmc_chains: temperature T = %g", T);
+    GPRY_TRY(ns_check_chains(ctx, "gpry_hmc_chains", nchains, 0, nsteps, thin, batch, &T, X_rec, y_rec, X_prop, y_prop));
     if (!(eps > 0.0) || !isfinite(eps)) return gpry_fail(ctx, -1, "gpry_hmc_chains: step size eps = %g", eps);
     if (nleap < 1 || nleap > 1024) return gpry_fail(ctx, -1, "gpry_hmc_chains: nleap = %d is outside 1 .. 1024", nleap);
     if (reflect && (max_reflect < 1 || max_reflect > 1024))
         return gpry_fail(ctx, -1, "gpry_hmc_chains: max_reflect = %d is outside 1 .. 1024", max_reflect);
-    const int nrec = nsteps / thin;
-    if (nrec > 0 && (!X_rec || !y_rec)) return gpry_fail(ctx, -1, "gpry_hmc_chains: NULL argument");
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "gpry_hmc_chains", lo, hi, seed, &a, &kp, &ap));
     const int d = ctx->d;
-    const int64_t n = nchains;
-    // one buffer: [X0 | y0 | Lp | records X | records y | last X | last y | accepted | evaluations | gradients |
-    //              end points X | their y | dH | G0 | reflections], a hook's region empty unless it is asked for
-    const int64_t sz[15] = {8 * n * d, 8 * n, 8 * (int64_t)d * d, 8 * n * nrec * d, 8 * n * nrec, 8 * n * d, 8 * n, 8 * n,
-                            8 * n, 8 * n, X_prop ? 8 * n * nsteps * d : 0, X_prop ? 8 * n * nsteps : 0,
-                            dH_prop ? 8 * n * nsteps : 0, G0 ? 8 * n * d : 0, reflect && nreflect ? 8 * n : 0};
-    int64_t off[16];
-    ns_layout(sz, off);
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[15]));
-    char* b = (char*)ctx->dmc;
-    HIP_TRY(ctx, hipMemcpyAsync(b + off[0], X0, sz[0], hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(b + off[1], y0, sz[1], hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(b + off[2], Lp, sz[2], hipMemcpyHostToDevice, ctx->stream));
-    const double* dX0 = (const double*)(b + off[0]);
-    const double* dy0 = (const double*)(b + off[1]);
-    const double* dL = (const double*)(b + off[2]);
-    double* dXr = (double*)(b + off[3]);
-    double* dyr = (double*)(b + off[4]);
-    double* dXl = (double*)(b + off[5]);
-    double* dyl = (double*)(b + off[6]);
-    int64_t* dna = (int64_t*)(b + off[7]);
-    int64_t* dnc = (int64_t*)(b + off[8]);
-    int64_t* dng = (int64_t*)(b + off[9]);
-    double* dXp = X_prop ? (double*)(b + off[10]) : nullptr;
-    double* dyp = X_prop ? (double*)(b + off[11]) : nullptr;
-    double* ddH = dH_prop ? (double*)(b + off[12]) : nullptr;
-    double* dG0 = G0 ? (double*)(b + off[13]) : nullptr;
-    int64_t* dnr = sz[14] ? (int64_t*)(b + off[14]) : nullptr;
+    const int64_t n = nchains, nrec = nsteps / thin;
+    NsStage st(ctx);
+    const auto rX0 = st.in(X0, n * d), ry0 = st.in(y0, n), rL = st.in(Lp, (int64_t)d * d);
+    const auto rXr = st.out(X_rec, n * nrec * d), ryr = st.out(y_rec, n * nrec);
+    const auto rXl = st.out(X_last, n * d), ryl = st.out(y_last, n);
+    const auto rna = st.out(naccept, n), rnc = st.out(ncalls, n), rgr = st.out(ngrad, n);
+    const auto rXp = st.out(X_prop, n * nsteps * d), ryp = st.out(y_prop, n * nsteps), rdH = st.out(dH_prop, n * nsteps);
+    const auto rG0 = st.out(G0, n * d);
+    const auto rnr = st.out(reflect ? nreflect : nullptr, n);
+    GPRY_TRY(st.begin());
 #define HM(DP, KID, RF, RFARG)                                                                                           \
-    hipLaunchKernelGGL((hmc_chain_kernel<DP, KID, RF>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX0, dy0, \
-                       dL, eps, nleap, T, minus_inf_value, (unsigned)batch, nsteps, thin, dXr, dyr, dXl, dyl, dna, dnc,  \
-                       dng, dXp, dyp, ddH, dG0, RFARG)
+    hipLaunchKernelGGL((hmc_chain_kernel<DP, KID, RF>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap,          \
+                       st.dev(rX0), st.dev(ry0), st.dev(rL), eps, nleap, T, minus_inf_value, (unsigned)batch, nsteps, thin,  \
+                       st.dev(rXr), st.dev(ryr), st.dev(rXl), st.dev(ryl), st.dev(rna), st.dev(rnc), st.dev(rgr),          \
+                       st.dev(rXp), st.dev(ryp), st.dev(rdH), st.dev(rG0), RFARG)
 #define HM_PLAIN(DP, KID) HM(DP, KID, false, HmcRf<false>{})
-#define HM_RF(DP, KID) HM(DP, KID, true, (HmcRf<true>{max_reflect, dnr}))
+#define HM_RF(DP, KID) HM(DP, KID, true, (HmcRf<true>{max_reflect, st.dev(rnr)}))
     if (reflect) { DISPATCH_DP_KID(d, ctx->kernel_id, HM_RF) }
     else { DISPATCH_DP_KID(d, ctx->kernel_id, HM_PLAIN) }
 #undef HM_RF
 #undef HM_PLAIN
 #undef HM
-    HIP_TRY(ctx, hipGetLastError());
     if (!reflect && nreflect) memset(nreflect, 0, 8 * n);
-    void* dst[12] = {X_rec, y_rec, X_last, y_last, naccept, ncalls, ngrad, X_prop, y_prop, dH_prop, G0, nreflect};
-    for (int i = 3; i < 15; i++)
-        if (sz[i] > 0) HIP_TRY(ctx, hipMemcpyAsync(dst[i - 3], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    return 0;
+    return st.end(device_ms);
 }
 
 int gpry_hmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const double* X0, const double* y0, int64_t nchains,

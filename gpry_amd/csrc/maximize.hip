@@ -66,55 +66,23 @@ int gpry_maximize_mean(gpry_ctx* ctx, const double* lo, const double* hi, const 
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_maximize_mean: ctx is NULL");
     if (!lo || !hi || !X0 || !y0 || !fixed || !H0 || !X_out || !y_out || !G_out || !iters || !ncalls || !ngrad || !status)
         return gpry_fail(ctx, -1, "gpry_maximize_mean: NULL argument");
+    const BfgsCtl ctl = {max_iter, max_halvings, gtol, ftol};
+    BfgsOut out = {X_out, y_out, G_out, iters, ncalls, ngrad, status};
+    BfgsHooks hk = {U_tr, y_tr, G_tr, nhalv_tr, reset_tr};
     const bool hooks = U_tr != nullptr;
-    if ((y_tr != nullptr) != hooks || (G_tr != nullptr) != hooks || (nhalv_tr != nullptr) != hooks ||
-        (reset_tr != nullptr) != hooks)
-        return gpry_fail(ctx, -1, "gpry_maximize_mean: the trace hooks are all NULL or all given");
-    if (nstart < 1 || nstart > 0x7fffffffll || max_iter < 0 || max_iter > 100000 || max_halvings < 0 || max_halvings > 1000)
-        return gpry_fail(ctx, -1, "gpry_maximize_mean: nstart = %lld, max_iter = %d, max_halvings = %d",
-                         (long long)nstart, max_iter, max_halvings);
-    if (!(gtol >= 0.0) || !isfinite(gtol)) return gpry_fail(ctx, -1, "gpry_maximize_mean: gtol = %g", gtol);
-    if (!(ftol >= 0.0) || !isfinite(ftol)) return gpry_fail(ctx, -1, "gpry_maximize_mean: ftol = %g", ftol);
+    GPRY_TRY(bfgs_check(ctx, "gpry_maximize_mean", nstart, ctl, H0, hk));
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "gpry_maximize_mean", lo, hi, 0, &a, &kp, &ap));
     const int d = ctx->d;
-    for (int e = 0; e < d * d; e++)
-        if (!isfinite(H0[e])) return gpry_fail(ctx, -1, "gpry_maximize_mean: H0 has an entry that is not finite");
-    const int64_t n = nstart, m1 = max_iter + 1, m0 = max_iter;
-    // one buffer: [X0 | y0 | H0 | fixed | X_out | y_out | G_out | iters | ncalls | ngrad | status | U_tr | y_tr | G_tr |
-    //              nhalv_tr | reset_tr], a hook's region empty unless asked for
-    const int64_t sz[16] = {8 * n * d, 8 * n, 8 * (int64_t)d * d, d, 8 * n * d, 8 * n, 8 * n * d, 4 * n, 8 * n, 8 * n, 4 * n,
-                            hooks ? 8 * n * m1 * d : 0, hooks ? 8 * n * m1 : 0, hooks ? 8 * n * m1 * d : 0,
-                            hooks ? 4 * n * m0 : 0, hooks ? 4 * n * m0 : 0};
-    int64_t off[17];
-    ns_layout(sz, off);
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[16]));
-    char* b = (char*)ctx->dmc;
-    const void* src[4] = {X0, y0, H0, fixed};
-    for (int i = 0; i < 4; i++) HIP_TRY(ctx, hipMemcpyAsync(b + off[i], src[i], sz[i], hipMemcpyHostToDevice, ctx->stream));
-    // unused trace slots: NaN (all bits set) and -1
-    if (hooks) HIP_TRY(ctx, hipMemsetAsync(b + off[11], 0xff, off[16] - off[11], ctx->stream));
-    const double* dX0 = (const double*)(b + off[0]);
-    const double* dy0 = (const double*)(b + off[1]);
-    const double* dH0 = (const double*)(b + off[2]);
-    const unsigned char* dfx = (const unsigned char*)(b + off[3]);
-    double* dXo = (double*)(b + off[4]);
-    double* dyo = (double*)(b + off[5]);
-    double* dGo = (double*)(b + off[6]);
-    int* dit = (int*)(b + off[7]);
-    int64_t* dnc = (int64_t*)(b + off[8]);
-    int64_t* dng = (int64_t*)(b + off[9]);
-    int* dst_ = (int*)(b + off[10]);
-    const BfgsCtl ctl = {max_iter, max_halvings, gtol, ftol};
-    const BfgsOut out = {dXo, dyo, dGo, dit, dnc, dng, dst_};
-    BfgsHooks hk = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (hooks) hk = {(double*)(b + off[11]), (double*)(b + off[12]), (double*)(b + off[13]), (int*)(b + off[14]), (int*)(b + off[15])};
+    const int64_t n = nstart;
+    NsStage st(ctx);
+    const auto rX0 = st.in(X0, n * d), ry0 = st.in(y0, n), rH0 = st.in(H0, (int64_t)d * d);
+    const auto rfx = st.in(fixed, d);
+    GPRY_TRY(bfgs_begin(st, n, d, max_iter, &out, &hk));
 #define MX(DP, KID, HK)                                                                                                   \
-    hipLaunchKernelGGL((maxmean_kernel<DP, KID, HK>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX0, dy0, dfx, \
-                       dH0, ctl, minus_inf_value, out, hk)
+    hipLaunchKernelGGL((maxmean_kernel<DP, KID, HK>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, st.dev(rX0), \
+                       st.dev(ry0), st.dev(rfx), st.dev(rH0), ctl, minus_inf_value, out, hk)
 #define MX_PLAIN(DP, KID) MX(DP, KID, false)
 #define MX_HOOKS(DP, KID) MX(DP, KID, true)
     if (hooks) { DISPATCH_DP_KID(d, ctx->kernel_id, MX_HOOKS) }
@@ -122,12 +90,7 @@ int gpry_maximize_mean(gpry_ctx* ctx, const double* lo, const double* hi, const 
 #undef MX_HOOKS
 #undef MX_PLAIN
 #undef MX
-    HIP_TRY(ctx, hipGetLastError());
-    void* dst[12] = {X_out, y_out, G_out, iters, ncalls, ngrad, status, U_tr, y_tr, G_tr, nhalv_tr, reset_tr};
-    for (int i = 4; i < 16; i++)
-        if (sz[i] > 0) HIP_TRY(ctx, hipMemcpyAsync(dst[i - 4], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    return 0;
+    return st.end(device_ms);
 }
 
 }  // extern "C"

@@ -238,15 +238,11 @@ int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const d
     if (!lo || !hi || !X0 || !fixed || !H0 || !X_out || !a_out || !y_out || !sigma_out || !G_out || !iters || !ncalls ||
         !ngrad || !status)
         return gpry_fail(ctx, -1, "gpry_maximize_acq: NULL argument");
+    const BfgsCtl ctl = {max_iter, max_halvings, gtol, ftol};
+    BfgsOut out = {X_out, a_out, G_out, iters, ncalls, ngrad, status};
+    BfgsHooks hk = {U_tr, a_tr, G_tr, nhalv_tr, reset_tr};
     const bool hooks = U_tr != nullptr;
-    if ((a_tr != nullptr) != hooks || (G_tr != nullptr) != hooks || (nhalv_tr != nullptr) != hooks ||
-        (reset_tr != nullptr) != hooks)
-        return gpry_fail(ctx, -1, "gpry_maximize_acq: the trace hooks are all NULL or all given");
-    if (nstart < 1 || nstart > 0x7fffffffll || max_iter < 0 || max_iter > 100000 || max_halvings < 0 || max_halvings > 1000)
-        return gpry_fail(ctx, -1, "gpry_maximize_acq: nstart = %lld, max_iter = %d, max_halvings = %d",
-                         (long long)nstart, max_iter, max_halvings);
-    if (!(gtol >= 0.0) || !isfinite(gtol)) return gpry_fail(ctx, -1, "gpry_maximize_acq: gtol = %g", gtol);
-    if (!(ftol >= 0.0) || !isfinite(ftol)) return gpry_fail(ctx, -1, "gpry_maximize_acq: ftol = %g", ftol);
+    GPRY_TRY(bfgs_check(ctx, "gpry_maximize_acq", nstart, ctl, H0, hk));
     if (!(sigma_n >= 0.0) || !isfinite(sigma_n)) return gpry_fail(ctx, -1, "gpry_maximize_acq: sigma_n = %g", sigma_n);
     if (!isfinite(zeta) || !isfinite(baseline))
         return gpry_fail(ctx, -1, "gpry_maximize_acq: zeta = %g, baseline = %g", zeta, baseline);
@@ -258,41 +254,19 @@ int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const d
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "gpry_maximize_acq", lo, hi, 0, &a, &kp, &ap));
     const int d = ctx->d;
-    for (int e = 0; e < d * d; e++)
-        if (!isfinite(H0[e])) return gpry_fail(ctx, -1, "gpry_maximize_acq: H0 has an entry that is not finite");
-    const int64_t n = nstart, m1 = max_iter + 1, m0 = max_iter;
-    // one buffer: [X0 | H0 | fixed | X_out | a_out | y_out | sigma_out | G_out | iters | ncalls | ngrad | status | U_tr |
-    //              a_tr | G_tr | nhalv_tr | reset_tr], a hook's region empty unless asked for
-    const int64_t sz[17] = {8 * n * d, 8 * (int64_t)d * d, d, 8 * n * d, 8 * n, 8 * n, 8 * n, 8 * n * d, 4 * n, 8 * n, 8 * n,
-                            4 * n, hooks ? 8 * n * m1 * d : 0, hooks ? 8 * n * m1 : 0, hooks ? 8 * n * m1 * d : 0,
-                            hooks ? 4 * n * m0 : 0, hooks ? 4 * n * m0 : 0};
-    int64_t off[18];
-    ns_layout(sz, off);
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[17]));
-    char* b = (char*)ctx->dmc;
-    const void* src[3] = {X0, H0, fixed};
-    for (int i = 0; i < 3; i++) HIP_TRY(ctx, hipMemcpyAsync(b + off[i], src[i], sz[i], hipMemcpyHostToDevice, ctx->stream));
-    // unused trace slots: NaN (all bits set) and -1
-    if (hooks) HIP_TRY(ctx, hipMemsetAsync(b + off[12], 0xff, off[17] - off[12], ctx->stream));
-    const double* dX0 = (const double*)(b + off[0]);
-    const double* dH0 = (const double*)(b + off[1]);
-    const unsigned char* dfx = (const unsigned char*)(b + off[2]);
-    double* dyo = (double*)(b + off[5]);
-    double* dso = (double*)(b + off[6]);
+    const int64_t n = nstart;
+    NsStage st(ctx);
+    const auto rX0 = st.in(X0, n * d), rH0 = st.in(H0, (int64_t)d * d);
+    const auto rfx = st.in(fixed, d);
+    const auto ryo = st.out(y_out, n), rso = st.out(sigma_out, n);
+    GPRY_TRY(bfgs_begin(st, n, d, max_iter, &out, &hk));
     const AcqParams q = {ctx->dV, ctx->Np, zeta, baseline, sigma_n, minus_inf_value};
-    const BfgsCtl ctl = {max_iter, max_halvings, gtol, ftol};
-    const BfgsOut out = {(double*)(b + off[3]), (double*)(b + off[4]), (double*)(b + off[7]), (int*)(b + off[8]),
-                         (int64_t*)(b + off[9]), (int64_t*)(b + off[10]), (int*)(b + off[11])};
-    BfgsHooks hk = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (hooks) hk = {(double*)(b + off[12]), (double*)(b + off[13]), (double*)(b + off[14]), (int*)(b + off[15]), (int*)(b + off[16])};
     const int lds = (int)(8 * ctx->Np);         // with the static arrays above 64 KB from Np = 2048 on
 #define MA(DP, KID, HK)                                                                                                   \
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)maxacq_kernel<DP, KID, HK>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                      lds));                                                                               \
-    hipLaunchKernelGGL((maxacq_kernel<DP, KID, HK>), dim3((unsigned)n), dim3(256), lds, ctx->stream, a, kp, ap, q, dX0, dfx, \
-                       dH0, ctl, out, dyo, dso, hk)
+    hipLaunchKernelGGL((maxacq_kernel<DP, KID, HK>), dim3((unsigned)n), dim3(256), lds, ctx->stream, a, kp, ap, q,           \
+                       st.dev(rX0), st.dev(rfx), st.dev(rH0), ctl, out, st.dev(ryo), st.dev(rso), hk)
 #define MA_PLAIN(DP, KID) MA(DP, KID, false)
 #define MA_HOOKS(DP, KID) MA(DP, KID, true)
     if (hooks) { DISPATCH_DP_KID(d, ctx->kernel_id, MA_HOOKS) }
@@ -300,12 +274,7 @@ int gpry_maximize_acq(gpry_ctx* ctx, const double* lo, const double* hi, const d
 #undef MA_HOOKS
 #undef MA_PLAIN
 #undef MA
-    HIP_TRY(ctx, hipGetLastError());
-    void* dst[14] = {X_out, a_out, y_out, sigma_out, G_out, iters, ncalls, ngrad, status, U_tr, a_tr, G_tr, nhalv_tr, reset_tr};
-    for (int i = 3; i < 17; i++)
-        if (sz[i] > 0) HIP_TRY(ctx, hipMemcpyAsync(dst[i - 3], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    return 0;
+    return st.end(device_ms);
 }
 
 }  // extern "C"

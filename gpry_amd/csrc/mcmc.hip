@@ -106,72 +106,26 @@ int gpry_mcmc_chains(gpry_ctx* ctx, const double* lo, const double* hi, const do
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_mcmc_chains: ctx is NULL");
     if (!lo || !hi || !X0 || !y0 || !Lp || !X_last || !y_last || !naccept || !ncalls)
         return gpry_fail(ctx, -1, "gpry_mcmc_chains: NULL argument");
-    if ((X_prop == nullptr) != (y_prop == nullptr))
-        return gpry_fail(ctx, -1, "gpry_mcmc_chains: X_prop and y_prop are both NULL or both given");
-    if (nchains < 1 || nchains > 0x7fffffffll || nsteps < 0 || thin < 1 || batch < 0 || batch > 0xffffffffll)
-        return gpry_fail(ctx, -1, "gpry_mcmc_chains: nchains = %lld, nsteps = %d, thin = %d, batch = %lld",
-                         (long long)nchains, nsteps, thin, (long long)batch);
-    if (!(T > 0.0) || !isfinite(T)) return gpry_fail(ctx, -1, "gpry_mcmc_chains: temperature T = %g", T);
-    const int nrec = nsteps / thin;
-    if (nrec > 0 && (!X_rec || !y_rec)) return gpry_fail(ctx, -1, "gpry_mcmc_chains: NULL argument");
+    GPRY_TRY(ns_check_chains(ctx, "gpry_mcmc_chains", nchains, 0, nsteps, thin, batch, &T, X_rec, y_rec, X_prop, y_prop));
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "gpry_mcmc_chains", lo, hi, seed, &a, &kp, &ap));
     const int d = ctx->d;
-    const int64_t n = nchains, hook = X_prop ? 1 : 0;
-    // one buffer: [X0 | y0 | Lp | records X | records y | last X | last y | accepted | evaluations | proposals X | their y]
-    const int64_t sz[11] = {8 * n * d, 8 * n, 8 * (int64_t)d * d, 8 * n * nrec * d, 8 * n * nrec, 8 * n * d, 8 * n, 8 * n,
-                            8 * n, 8 * hook * n * nsteps * d, 8 * hook * n * nsteps};
-    int64_t off[12];
-    ns_layout(sz, off);
-    const bool mapped = ctx->opt_mcmc_mapped != 0;
-    char *h = nullptr, *b = nullptr;
-    if (mapped) {
-        GPRY_TRY(ensure_pinned(ctx, off[11]));
-        h = (char*)ctx->hpin;
-        b = (char*)ctx->hpin_dev;
-        memcpy(h + off[0], X0, sz[0]);
-        memcpy(h + off[1], y0, sz[1]);
-        memcpy(h + off[2], Lp, sz[2]);
-    }
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    if (!mapped) {
-        GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[11]));
-        b = (char*)ctx->dmc;
-        HIP_TRY(ctx, hipMemcpyAsync(b + off[0], X0, sz[0], hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(b + off[1], y0, sz[1], hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(b + off[2], Lp, sz[2], hipMemcpyHostToDevice, ctx->stream));
-    }
-    const double* dX0 = (const double*)(b + off[0]);
-    const double* dy0 = (const double*)(b + off[1]);
-    const double* dL = (const double*)(b + off[2]);
-    double* dXr = (double*)(b + off[3]);
-    double* dyr = (double*)(b + off[4]);
-    double* dXl = (double*)(b + off[5]);
-    double* dyl = (double*)(b + off[6]);
-    int64_t* dna = (int64_t*)(b + off[7]);
-    int64_t* dnc = (int64_t*)(b + off[8]);
-    double* dXp = hook ? (double*)(b + off[9]) : nullptr;
-    double* dyp = hook ? (double*)(b + off[10]) : nullptr;
+    const int64_t n = nchains, nrec = nsteps / thin;
+    NsStage st(ctx, ctx->opt_mcmc_mapped != 0);
+    const auto rX0 = st.in(X0, n * d), ry0 = st.in(y0, n), rL = st.in(Lp, (int64_t)d * d);
+    const auto rXr = st.out(X_rec, n * nrec * d), ryr = st.out(y_rec, n * nrec);
+    const auto rXl = st.out(X_last, n * d), ryl = st.out(y_last, n);
+    const auto rna = st.out(naccept, n), rnc = st.out(ncalls, n);
+    const auto rXp = st.out(X_prop, n * nsteps * d), ryp = st.out(y_prop, n * nsteps);
+    GPRY_TRY(st.begin());
 #define MC(DP, KID) hipLaunchKernelGGL((mcmc_chain_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, \
-                                       ap, dX0, dy0, dL, T, minus_inf_value, (unsigned)batch, nsteps, thin, dXr, dyr, dXl, \
-                                       dyl, dna, dnc, dXp, dyp)
+                                       ap, st.dev(rX0), st.dev(ry0), st.dev(rL), T, minus_inf_value, (unsigned)batch,     \
+                                       nsteps, thin, st.dev(rXr), st.dev(ryr), st.dev(rXl), st.dev(ryl), st.dev(rna),     \
+                                       st.dev(rnc), st.dev(rXp), st.dev(ryp))
     DISPATCH_DP_KID(d, ctx->kernel_id, MC)
 #undef MC
-    if (!mapped) {
-        HIP_TRY(ctx, hipGetLastError());
-        void* dst[8] = {X_rec, y_rec, X_last, y_last, naccept, ncalls, X_prop, y_prop};
-        for (int i = 3; i < 11; i++)
-            if (sz[i] > 0) HIP_TRY(ctx, hipMemcpyAsync(dst[i - 3], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
-    }
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    if (mapped) {
-        void* dst[8] = {X_rec, y_rec, X_last, y_last, naccept, ncalls, X_prop, y_prop};
-        for (int i = 3; i < 11; i++)
-            if (sz[i] > 0) memcpy(dst[i - 3], h + off[i], sz[i]);
-    }
-    return 0;
+    return st.end(device_ms);
 }
 
 }  // extern "C"

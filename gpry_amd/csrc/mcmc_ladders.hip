@@ -192,87 +192,39 @@ int gpry_mcmc_ladders(gpry_ctx* ctx, const double* lo, const double* hi, const d
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_mcmc_ladders: ctx is NULL");
     if (!lo || !hi || !X0 || !y0 || !Lp || !T || !X_last || !y_last || !naccept || !ncalls)
         return gpry_fail(ctx, -1, "gpry_mcmc_ladders: NULL argument");
-    if ((X_prop == nullptr) != (y_prop == nullptr))
-        return gpry_fail(ctx, -1, "gpry_mcmc_ladders: X_prop and y_prop are both NULL or both given");
     if (nrungs < 1 || nrungs > ML_MAX_RUNGS)
         return gpry_fail(ctx, -1, "gpry_mcmc_ladders: nrungs = %d outside 1 .. %d", nrungs, ML_MAX_RUNGS);
-    if (nladders < 1 || nladders * nrungs > 0x7fffffffll || nsteps < 0 || thin < 1 || batch < 0 || batch > 0xffffffffll)
-        return gpry_fail(ctx, -1, "gpry_mcmc_ladders: nladders = %lld, nrungs = %d, nsteps = %d, thin = %d, batch = %lld",
-                         (long long)nladders, nrungs, nsteps, thin, (long long)batch);
+    GPRY_TRY(ns_check_chains(ctx, "gpry_mcmc_ladders", nladders, nrungs, nsteps, thin, batch, T, X_rec, y_rec, X_prop, y_prop));
     if (swap_every < 0) return gpry_fail(ctx, -1, "gpry_mcmc_ladders: swap_every = %d", swap_every);
     if (swap_log && swap_every == 0)
         return gpry_fail(ctx, -1, "gpry_mcmc_ladders: swap_log given with swap_every = 0");
-    for (int r = 0; r < nrungs; r++)
-        if (!(T[r] > 0.0) || !isfinite(T[r]))
-            return gpry_fail(ctx, -1, "gpry_mcmc_ladders: temperature T[%d] = %g", r, T[r]);
     if (nrungs > 1 && (!nswap_try || !nswap_acc)) return gpry_fail(ctx, -1, "gpry_mcmc_ladders: NULL argument");
-    const int nrec = nsteps / thin;
-    if (nrec > 0 && (!X_rec || !y_rec)) return gpry_fail(ctx, -1, "gpry_mcmc_ladders: NULL argument");
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "gpry_mcmc_ladders", lo, hi, seed, &a, &kp, &ap));
     const int d = ctx->d;
-    const int64_t n = nladders * nrungs, npair = nladders * (nrungs - 1), hook = X_prop ? 1 : 0;
+    const int64_t n = nladders * nrungs, npair = nladders * (nrungs - 1), nrec = nsteps / thin;
     const int64_t nround = swap_every > 0 ? nsteps / swap_every : 0;
-    // one buffer: [X0 | y0 | Lp | T | records X | records y | last X | last y | accepted | evaluations | swaps tried |
-    //              swaps accepted | proposals X | their y | swap log]
-    const int64_t sz[15] = {8 * n * d, 8 * n, 8 * (int64_t)nrungs * d * d, 8 * (int64_t)nrungs, 8 * n * nrec * d,
-                            8 * n * nrec, 8 * n * d, 8 * n, 8 * n, 8 * n, 8 * npair, 8 * npair, 8 * hook * n * nsteps * d,
-                            8 * hook * n * nsteps, swap_log ? nround * npair : 0};
-    int64_t off[16];
-    ns_layout(sz, off);
-    const void* src[4] = {X0, y0, Lp, T};
-    void* dst[11] = {X_rec, y_rec, X_last, y_last, naccept, ncalls, nswap_try, nswap_acc, X_prop, y_prop, swap_log};
-    const bool mapped = ctx->opt_mcmc_mapped != 0;
-    char *h = nullptr, *b = nullptr;
-    if (mapped) {
-        GPRY_TRY(ensure_pinned(ctx, off[15]));
-        h = (char*)ctx->hpin;
-        b = (char*)ctx->hpin_dev;
-        for (int i = 0; i < 4; i++) memcpy(h + off[i], src[i], sz[i]);
-    }
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    if (!mapped) {
-        GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, off[15]));
-        b = (char*)ctx->dmc;
-        for (int i = 0; i < 4; i++)
-            HIP_TRY(ctx, hipMemcpyAsync(b + off[i], src[i], sz[i], hipMemcpyHostToDevice, ctx->stream));
-    }
-    const double* dX0 = (const double*)(b + off[0]);
-    const double* dy0 = (const double*)(b + off[1]);
-    const double* dL = (const double*)(b + off[2]);
-    const double* dT = (const double*)(b + off[3]);
-    double* dXr = (double*)(b + off[4]);
-    double* dyr = (double*)(b + off[5]);
-    double* dXl = (double*)(b + off[6]);
-    double* dyl = (double*)(b + off[7]);
-    int64_t* dna = (int64_t*)(b + off[8]);
-    int64_t* dnc = (int64_t*)(b + off[9]);
-    int64_t* dst_ = (int64_t*)(b + off[10]);
-    int64_t* dsa = (int64_t*)(b + off[11]);
-    double* dXp = hook ? (double*)(b + off[12]) : nullptr;
-    double* dyp = hook ? (double*)(b + off[13]) : nullptr;
-    int8_t* dsl = swap_log ? (int8_t*)(b + off[14]) : nullptr;
+    NsStage st(ctx, ctx->opt_mcmc_mapped != 0);
+    const auto rX0 = st.in(X0, n * d), ry0 = st.in(y0, n), rL = st.in(Lp, (int64_t)nrungs * d * d), rT = st.in(T, nrungs);
+    const auto rXr = st.out(X_rec, n * nrec * d), ryr = st.out(y_rec, n * nrec);
+    const auto rXl = st.out(X_last, n * d), ryl = st.out(y_last, n);
+    const auto rna = st.out(naccept, n), rnc = st.out(ncalls, n);
+    const auto rst = st.out(nswap_try, npair), rsa = st.out(nswap_acc, npair);
+    const auto rXp = st.out(X_prop, n * nsteps * d), ryp = st.out(y_prop, n * nsteps);
+    const auto rsl = st.out(swap_log, nround * npair);
+    GPRY_TRY(st.begin());
 #define ML_(DP, KID, RP) hipLaunchKernelGGL((ladder_chain_kernel<DP, KID, RP>), dim3((unsigned)nladders), dim3(256), 0,      \
-                                            ctx->stream, a, kp, ap, nrungs, dX0, dy0, dL, dT, minus_inf_value,                \
-                                            (unsigned)batch, nsteps, thin, swap_every, dXr, dyr, dXl, dyl, dna, dnc, dst_,    \
-                                            dsa, dXp, dyp, dsl)
+                                            ctx->stream, a, kp, ap, nrungs, st.dev(rX0), st.dev(ry0), st.dev(rL), st.dev(rT), \
+                                            minus_inf_value, (unsigned)batch, nsteps, thin, swap_every, st.dev(rXr),          \
+                                            st.dev(ryr), st.dev(rXl), st.dev(ryl), st.dev(rna), st.dev(rnc), st.dev(rst),     \
+                                            st.dev(rsa), st.dev(rXp), st.dev(ryp), st.dev(rsl))
     // RP: the smallest of 2 / 4 / 8 that holds the ladder
 #define ML(DP, KID) if (nrungs <= 2) { ML_(DP, KID, 2); } else if (nrungs <= 4) { ML_(DP, KID, 4); } else { ML_(DP, KID, 8); }
     DISPATCH_DP_KID(d, ctx->kernel_id, ML)
 #undef ML
 #undef ML_
-    if (!mapped) {
-        HIP_TRY(ctx, hipGetLastError());
-        for (int i = 4; i < 15; i++)
-            if (sz[i] > 0) HIP_TRY(ctx, hipMemcpyAsync(dst[i - 4], b + off[i], sz[i], hipMemcpyDeviceToHost, ctx->stream));
-    }
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    if (mapped)
-        for (int i = 4; i < 15; i++)
-            if (sz[i] > 0) memcpy(dst[i - 4], h + off[i], sz[i]);
-    return 0;
+    return st.end(device_ms);
 }
 
 }  // extern "C"

@@ -277,10 +277,6 @@ struct NsGenRequest {
     double *X_new = nullptr, *y_new = nullptr, *device_ms = nullptr; int64_t* ncalls = nullptr;
 };
 
-// The regions of a generation's pinned, mapped buffer, in this order.  NS_LAB is used with labels alone; with cum_p the
-// kernel reads the member lists NS_MEM / NS_MOF and NS_CP instead; a region that is not used has no bytes.
-enum { NS_XS, NS_YS, NS_W, NS_LAB, NS_MEM, NS_MOF, NS_CP, NS_XN, NS_YN, NS_CNT, NS_REGIONS };
-
 static int ns_check(gpry_ctx* ctx, const NsGenRequest& rq) {
     const char* who = rq.who;
     const int32_t* labels = rq.labels; const double* cum_p = rq.cum_p;
@@ -331,23 +327,23 @@ static void ns_members(const int32_t* labels, int64_t nsurv, int n_clusters, int
     for (int64_t i = 0; i < nsurv; i++) mem[fill[labels[i]]++] = (int32_t)i;
 }
 
-// the chain kernel of the context's (DP, KID), recording (PH) iff there is a phantom buffer, on the regions at `hd`
+// a generation's arrays as the kernel sees them.  lab is used with labels alone; with cum_p the kernel reads the member
+// lists mem / mof and cp instead; what is not used is NULL.  Xp / yp: the phantoms (NULL: not recorded).
+struct NsGenDev {
+    const double *Xs, *ys, *W; const int *lab, *mem, *mof; const double* cp;
+    double *Xn, *yn; int64_t* cnt; double *Xp, *yp;
+};
+
+// the chain kernel of the context's (DP, KID), recording (PH) iff there is a phantom buffer
 static void ns_launch_chains(gpry_ctx* ctx, const NsGenRequest& rq, const NsArgs& a, const KernParams& kp,
-                             const AffParams& ap, char* hd, const int64_t* off, int nw, int n_ph, double* dXp, double* dyp) {
-    const bool lists = rq.cum_p != nullptr;
-    const int* dlab = rq.labels && !lists ? (const int*)(hd + off[NS_LAB]) : nullptr;
-    const int* dmem = lists ? (const int*)(hd + off[NS_MEM]) : nullptr;
-    const int* dmof = lists ? (const int*)(hd + off[NS_MOF]) : nullptr;
-    const double* dcp = lists ? (const double*)(hd + off[NS_CP]) : nullptr;
+                             const AffParams& ap, const NsGenDev& g, int nw, int n_ph) {
 #define NS_CHAIN(DP, KID, PH)                                                                                          \
     hipLaunchKernelGGL((ns_chain_kernel<DP, KID, PH>), dim3((unsigned)rq.k), dim3(256), 0, ctx->stream, a, kp, ap,      \
-                       (const double*)(hd + off[NS_XS]), (const double*)(hd + off[NS_YS]), rq.nsurv,                   \
-                       (const double*)(hd + off[NS_W]), dlab, dmem, dmof, dcp, nw, rq.lstar, (unsigned)rq.generation,   \
-                       rq.num_repeats, (double*)(hd + off[NS_XN]), (double*)(hd + off[NS_YN]),                         \
-                       (int64_t*)(hd + off[NS_CNT]), rq.thin, n_ph, dXp, dyp)
+                       g.Xs, g.ys, rq.nsurv, g.W, g.lab, g.mem, g.mof, g.cp, nw, rq.lstar, (unsigned)rq.generation,    \
+                       rq.num_repeats, g.Xn, g.yn, g.cnt, rq.thin, n_ph, g.Xp, g.yp)
 #define NS_CHAIN_PLAIN(DP, KID) NS_CHAIN(DP, KID, false)
 #define NS_CHAIN_PH(DP, KID) NS_CHAIN(DP, KID, true)
-    if (dXp) { DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_CHAIN_PH) }
+    if (g.Xp) { DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_CHAIN_PH) }
     else { DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_CHAIN_PLAIN) }
 #undef NS_CHAIN_PH
 #undef NS_CHAIN_PLAIN
@@ -370,40 +366,35 @@ static int ns_generation_impl(gpry_ctx* ctx, const NsGenRequest& rq) {
         return gpry_fail(ctx, -1, "%s: %d chains x %d phantoms x %d coordinates need %lld bytes, the limit is %lld", rq.who,
                          rq.k, n_ph, (int)d, (long long)(psz[0] + psz[1]), (long long)NS_PHANTOM_MAX_BYTES);
     const bool rec = k > 0 && n_ph > 0;
-    // ---- lay out and fill the buffer
-    int64_t sz[NS_REGIONS] = {0}, off[NS_REGIONS + 1];
-    sz[NS_XS] = 8 * n * d; sz[NS_YS] = 8 * n; sz[NS_W] = 8 * nw * d * d;
-    if (lists) { sz[NS_MEM] = 4 * n; sz[NS_MOF] = 4 * (nc + 1); sz[NS_CP] = 8 * nc; }
-    else if (rq.labels) sz[NS_LAB] = 4 * n;
-    sz[NS_XN] = 8 * k * d; sz[NS_YN] = 8 * k; sz[NS_CNT] = 8 * k;
-    ns_layout(sz, off);
-    GPRY_TRY(ensure_pinned(ctx, off[NS_REGIONS]));
-    char* h = (char*)ctx->hpin;
-    memcpy(h + off[NS_XS], rq.X_surv, sz[NS_XS]);
-    memcpy(h + off[NS_YS], rq.y_surv, sz[NS_YS]);
-    memcpy(h + off[NS_W], rq.W, sz[NS_W]);
+    // ---- the pinned, mapped buffer: with cum_p the member lists and cum_p, else the labels if there are any
+    std::vector<int32_t> mem, mof;
     if (lists) {
-        ns_members(rq.labels, n, (int)nc, (int32_t*)(h + off[NS_MEM]), (int32_t*)(h + off[NS_MOF]));
-        memcpy(h + off[NS_CP], rq.cum_p, sz[NS_CP]);
-    } else if (rq.labels) memcpy(h + off[NS_LAB], rq.labels, sz[NS_LAB]);
+        mem.resize(n);
+        mof.resize(nc + 1);
+        ns_members(rq.labels, n, (int)nc, mem.data(), mof.data());
+    }
+    NsStage st(ctx, /*mapped=*/true);
+    const auto rXs = st.in(rq.X_surv, n * d), rys = st.in(rq.y_surv, n), rW = st.in(rq.W, nw * d * d);
+    const auto rcp = st.in(rq.cum_p, nc);
+    const auto rlab = st.in(lists ? nullptr : rq.labels, n);
+    const auto rmem = st.in(mem.data(), (int64_t)mem.size()), rmof = st.in(mof.data(), (int64_t)mof.size());
+    const auto rXn = st.out(rq.X_new, k * d), ryn = st.out(rq.y_new, k);
+    const auto rcnt = st.out(rq.ncalls, k);
+    GPRY_TRY(st.begin());
     // ---- launch
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
     if (rec) GPRY_TRY(dev_grow(ctx, &ctx->dph, &ctx->ph_cap, poff[2]));
     double* dXp = rec ? (double*)ctx->dph : nullptr;
     double* dyp = rec ? (double*)(ctx->dph + poff[1]) : nullptr;
-    if (k > 0) ns_launch_chains(ctx, rq, a, kp, ap, (char*)ctx->hpin_dev, off, (int)nw, n_ph, dXp, dyp);
+    const NsGenDev g = {st.dev(rXs), st.dev(rys), st.dev(rW), st.dev(rlab), st.dev(rmem), st.dev(rmof), st.dev(rcp),
+                        st.dev(rXn), st.dev(ryn), st.dev(rcnt), dXp, dyp};
+    if (k > 0) ns_launch_chains(ctx, rq, a, kp, ap, g, (int)nw, n_ph);
     // ---- copy back
     if (rec) {
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(rq.X_ph, dXp, (size_t)psz[0], hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(rq.y_ph, dyp, (size_t)psz[1], hipMemcpyDeviceToHost, ctx->stream));
     }
-    GPRY_TRY(ns_end(ctx, &tm, rq.device_ms));
-    memcpy(rq.X_new, h + off[NS_XN], sz[NS_XN]);
-    memcpy(rq.y_new, h + off[NS_YN], sz[NS_YN]);
-    memcpy(rq.ncalls, h + off[NS_CNT], sz[NS_CNT]);
-    return 0;
+    return st.end(rq.device_ms);
 }
 
 // the part of a request that every generation entry point takes
@@ -428,26 +419,15 @@ int gpry_ns_prior(gpry_ctx* ctx, const double* lo, const double* hi, uint64_t se
     GPRY_TRY(require_model(ctx, true));
     NsArgs a; KernParams kp; AffParams ap;
     GPRY_TRY(ns_args(ctx, "nested sampler", lo, hi, seed, &a, &kp, &ap));
-    NsTimer tm;
-    GPRY_TRY(ns_begin(ctx, &tm));
-    const int64_t sz[2] = {8 * n * ctx->d, 8 * n};      // [X | y] in the pinned, mapped buffer
-    int64_t off[3];
-    ns_layout(sz, off);
-    if (n > 0) {
-        GPRY_TRY(ensure_pinned(ctx, off[2]));
-        double* dX = (double*)((char*)ctx->hpin_dev + off[0]);
-        double* dy = (double*)((char*)ctx->hpin_dev + off[1]);
-#define NS_PRIOR(DP, KID) \
-    hipLaunchKernelGGL((ns_prior_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, dX, dy)
-        DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_PRIOR)
+    NsStage st(ctx, /*mapped=*/true);
+    const auto rX = st.out(X_out, n * ctx->d), ry = st.out(y_out, n);
+    GPRY_TRY(st.begin());
+#define NS_PRIOR(DP, KID)                                                                                          \
+    hipLaunchKernelGGL((ns_prior_kernel<DP, KID>), dim3((unsigned)n), dim3(256), 0, ctx->stream, a, kp, ap, st.dev(rX), \
+                       st.dev(ry))
+    if (n > 0) { DISPATCH_DP_KID(ctx->d, ctx->kernel_id, NS_PRIOR) }
 #undef NS_PRIOR
-    }
-    GPRY_TRY(ns_end(ctx, &tm, device_ms));
-    if (n > 0) {
-        memcpy(X_out, (char*)ctx->hpin + off[0], sz[0]);
-        memcpy(y_out, (char*)ctx->hpin + off[1], sz[1]);
-    }
-    return 0;
+    return st.end(device_ms);
 }
 
 int gpry_ns_generation(gpry_ctx* ctx, const double* lo, const double* hi, const double* X_surv, const double* y_surv,

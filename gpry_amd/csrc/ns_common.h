@@ -181,3 +181,103 @@ static int ns_end(gpry_ctx* ctx, NsTimer* tm, double* device_ms) {
     return 0;
 }
 
+// The staged buffer of one call: an entry point declares its inputs (in) and outputs (out) in any order, begin() lays
+// them end to end on 256-byte boundaries and uploads the inputs, dev() gives the kernel its pointers, end() brings every
+// output back to its host array and times the call.  A region whose host pointer is NULL or whose count is 0 has no
+// bytes, dev() == nullptr and no copy.  An output may start filled with a byte (0xff: NaN and -1).
+// Backing, chosen at construction: the context's device buffer (dmc), with asynchronous copies between the two events, or
+// (mapped) its pinned, mapped buffer (hpin), with memcpy in before the first event and out after the synchronise.
+struct NsStage {
+    template <class T> struct In { int i; };
+    template <class T> struct Out { int i; };
+    struct Region { const void* src; void* dst; int64_t bytes, off; int fill; };
+    static const int CAP = 24;
+    gpry_ctx* ctx; bool mapped;
+    Region r[CAP + 1];                  // (slot CAP: where a region beyond the capacity lands; begin() then fails)
+    int n = 0;
+    int64_t total = 0;
+    char* base = nullptr;               // the buffer as the device sees it
+    NsTimer tm;
+
+    NsStage(gpry_ctx* c, bool m = false) : ctx(c), mapped(m) {}
+    int add(const void* src, void* dst, bool given, int64_t bytes, int fill) {
+        const int i = n < CAP ? n : CAP;
+        r[i] = {src, dst, given ? bytes : 0, total, fill};
+        total += round_up(r[i].bytes, 256);
+        n++;
+        return i;
+    }
+    template <class T> In<T> in(const T* p, int64_t count) { return {add(p, nullptr, p != nullptr, (int64_t)sizeof(T) * count, -1)}; }
+    template <class T> Out<T> out(T* p, int64_t count, int fill = -1) {
+        return {add(nullptr, p, p != nullptr, (int64_t)sizeof(T) * count, fill)};
+    }
+    template <class T> const T* dev(In<T> h) const { return r[h.i].bytes ? (const T*)(base + r[h.i].off) : nullptr; }
+    template <class T> T* dev(Out<T> h) const { return r[h.i].bytes ? (T*)(base + r[h.i].off) : nullptr; }
+
+    // the buffer, the inputs and the fills, and the first event
+    int begin() {
+        if (n > CAP) return gpry_fail(ctx, -1, "NsStage: %d regions, the table holds %d", n, CAP);
+        if (mapped) {
+            GPRY_TRY(ensure_pinned(ctx, total));
+            base = (char*)ctx->hpin_dev;
+            char* h = (char*)ctx->hpin;
+            for (int i = 0; i < n; i++) {
+                if (r[i].bytes && r[i].src) memcpy(h + r[i].off, r[i].src, r[i].bytes);
+                if (r[i].bytes && r[i].fill >= 0) memset(h + r[i].off, r[i].fill, r[i].bytes);
+            }
+            return ns_begin(ctx, &tm);
+        }
+        GPRY_TRY(ns_begin(ctx, &tm));
+        GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, total));
+        base = (char*)ctx->dmc;
+        for (int i = 0; i < n; i++) {
+            if (r[i].bytes && r[i].src)
+                HIP_TRY(ctx, hipMemcpyAsync(base + r[i].off, r[i].src, r[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+            if (r[i].bytes && r[i].fill >= 0) HIP_TRY(ctx, hipMemsetAsync(base + r[i].off, r[i].fill, r[i].bytes, ctx->stream));
+        }
+        return 0;
+    }
+    // the launch's error, the outputs, the second event, the synchronise and device_ms
+    int end(double* device_ms) {
+        if (!mapped) {
+            HIP_TRY(ctx, hipGetLastError());
+            for (int i = 0; i < n; i++)
+                if (r[i].bytes && r[i].dst)
+                    HIP_TRY(ctx, hipMemcpyAsync(r[i].dst, base + r[i].off, r[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        GPRY_TRY(ns_end(ctx, &tm, device_ms));
+        if (mapped)
+            for (int i = 0; i < n; i++)
+                if (r[i].bytes && r[i].dst) memcpy(r[i].dst, (const char*)ctx->hpin + r[i].off, r[i].bytes);
+        return 0;
+    }
+};
+
+// ---- the argument checks the chain entry points share (mcmc.hip, mcmc_ladders.hip, hmc.hip) --------
+// rung < 0: the one temperature of a plain chain call
+static int ns_check_temperature(gpry_ctx* ctx, const char* who, double T, int rung = -1) {
+    if (T > 0.0 && isfinite(T)) return 0;
+    if (rung < 0) return gpry_fail(ctx, -1, "%s: temperature T = %g", who, T);
+    return gpry_fail(ctx, -1, "%s: temperature T[%d] = %g", who, rung, T);
+}
+
+// nrungs = 0: nchains plain chains at the temperature T[0]; nrungs >= 1 (already in range): nchains ladders of nrungs
+// chains at the temperatures T[0 .. nrungs)
+static int ns_check_chains(gpry_ctx* ctx, const char* who, int64_t nchains, int nrungs, int nsteps, int thin, int64_t batch,
+                           const double* T, const void* X_rec, const void* y_rec, const void* X_prop, const void* y_prop) {
+    if ((X_prop == nullptr) != (y_prop == nullptr))
+        return gpry_fail(ctx, -1, "%s: X_prop and y_prop are both NULL or both given", who);
+    if (nchains < 1 || nchains * (nrungs ? nrungs : 1) > 0x7fffffffll || nsteps < 0 || thin < 1 || batch < 0 ||
+        batch > 0xffffffffll) {
+        if (nrungs)
+            return gpry_fail(ctx, -1, "%s: nladders = %lld, nrungs = %d, nsteps = %d, thin = %d, batch = %lld", who,
+                             (long long)nchains, nrungs, nsteps, thin, (long long)batch);
+        return gpry_fail(ctx, -1, "%s: nchains = %lld, nsteps = %d, thin = %d, batch = %lld", who, (long long)nchains, nsteps,
+                         thin, (long long)batch);
+    }
+    if (!nrungs) GPRY_TRY(ns_check_temperature(ctx, who, T[0]));
+    for (int r = 0; r < nrungs; r++) GPRY_TRY(ns_check_temperature(ctx, who, T[r], r));
+    if (nsteps / thin > 0 && (!X_rec || !y_rec)) return gpry_fail(ctx, -1, "%s: NULL argument", who);
+    return 0;
+}
+
