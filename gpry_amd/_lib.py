@@ -62,6 +62,7 @@ SIGNATURES = {
     "gpry_lml": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_double), _vp, _P(C.c_int)]),
     "gpry_lml_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "gpry_loo_objective": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_double), _vp, _P(C.c_int)]),
+    "gpry_loo_objective_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "gpry_predict": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_debug_serve_stats": (C.c_int, [_vp, _P(C.c_int64), _P(C.c_int64)]),
     "gpry_ns_prior": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int64, _vp, _vp, _P(C.c_double)]),
@@ -416,6 +417,21 @@ class Device:
         if eval_gradient:
             return val.value, grad, info.value
         return val.value, info.value
+
+    def loo_objective_batch(self, thetas, eval_gradient=True):
+        """``loo_objective`` for every row of ``thetas`` in one call (gpry_loo_objective_batch): ``(value (B,), grad (B,
+        n_theta), info (B,))``, or ``(value, info)`` without gradients.  Up to the ``lml_batch`` limit one chain of launches
+        carries all rows; every row has the bits of a single ``loo_objective`` call."""
+        thetas = _f64(np.atleast_2d(thetas))
+        B, w = thetas.shape
+        if w != self.n_theta:
+            raise ValueError(f"expected {self.n_theta} columns, got {w}")
+        val = np.empty(B)
+        grad = np.zeros((B, w)) if eval_gradient else None
+        info = np.zeros(B, dtype=np.int32)
+        self._check(self._lib.gpry_loo_objective_batch(self._h, _ptr(thetas), B, int(bool(eval_gradient)), _ptr(val),
+                                                       _ptr(grad), _ptr(info)), "gpry_loo_objective_batch")
+        return (val, grad, info) if eval_gradient else (val, info)
 
     def lml_batch(self, thetas, eval_gradient=True):
         """``lml`` for every row of ``thetas`` in one call: ``(lml (B,), grad (B, 1 + d), info (B,))`` (``(lml, info)``

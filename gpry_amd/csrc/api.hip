@@ -121,7 +121,7 @@ static int lml_chain(gpry_ctx* ctx, int want_grad, double* dres) {
     return launch_lml_traces(ctx, ctx->dW3, da, dout + 2, dout, dres, RES_INFO);
 }
 
-// ---- B thetas in ONE chain of launches (128 < Np <= lml_batch) --------------------------------------------------
+// ---- B thetas in ONE chain of launches (128 < Np <= lml_batch; the leave-one-out objective: from Np = 128) ----------
 // The reference runs the optimiser restarts of a fit one after another (gpry/gpr.py:968-984, 10 + 2 d of them by default,
 // gpry/run.py:315-325); stepped side by side (gpry_amd/lockstep.py) they hand a round's thetas to gpry_lml_batch.  Above
 // N = 128 one evaluation is a chain of 20-60 launches that keeps a handful of CUs busy (0.001-0.02 of the FP64 peak at
@@ -131,7 +131,9 @@ struct BatchLayout {
     int64_t w, w2, w3, xs, vec, part, split, par, info;     // offsets (doubles) within a theta's set
     int64_t part_cap, split_cap, stride;
 };
-static int batch_layout(gpry_ctx* ctx, BatchLayout* L) {
+// (bc.part_min / bc.split_min: what the chain's own tail needs of the two shared pieces; 0 for the LML, whose layout is the
+// factor chain's)
+static int batch_layout(gpry_ctx* ctx, const BatchChain& bc, BatchLayout* L) {
     const int64_t Np = ctx->Np, nn = Np * Np;
     int slices = 0;
     GPRY_TRY(factor_chain_slices(ctx, Np, &slices));
@@ -143,8 +145,12 @@ static int batch_layout(gpry_ctx* ctx, BatchLayout* L) {
     L->w = take(nn); L->w2 = take(nn); L->w3 = take(nn);
     L->xs = take(Np * ctx->dpad);
     L->vec = take(8 * Np + 4096);
-    L->part_cap = p1 > p2 ? p1 : p2; L->part = take(L->part_cap);
-    L->split_cap = (int64_t)slices * nn; L->split = take(L->split_cap > 0 ? L->split_cap : 1);
+    L->part_cap = p1 > p2 ? p1 : p2;
+    if (L->part_cap < bc.part_min) L->part_cap = bc.part_min;
+    L->part = take(L->part_cap);
+    L->split_cap = (int64_t)slices * nn;
+    if (L->split_cap < bc.split_min) L->split_cap = bc.split_min;
+    L->split = take(L->split_cap > 0 ? L->split_cap : 1);
     L->par = take(GPRY_BPAR_ROW);
     L->info = take(8);                      // 16 status / arrival words
     L->stride = o + 32 * 9;                 // not a multiple of a large power of two: consecutive sets start on different channels
@@ -157,7 +163,7 @@ static int ensure_batch_buffers(gpry_ctx* ctx, int64_t arena_doubles, int64_t re
         ctx->barena = nullptr; ctx->barena_cap = 0;
         const hipError_t e = hipMalloc((void**)&ctx->barena, sizeof(double) * (size_t)arena_doubles);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); ctx->barena = nullptr; return 2; }
-        if (e != hipSuccess) { ctx->barena = nullptr; return gpry_fail(ctx, -2, "lml_batch: hipMalloc of the scratch arena failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { ctx->barena = nullptr; return gpry_fail(ctx, -2, "batched objective: hipMalloc of the scratch arena failed: %s", hipGetErrorString(e)); }
         ctx->barena_cap = arena_doubles;
     }
     if (res_bytes > ctx->hbres_cap) {
@@ -174,7 +180,11 @@ static int ensure_batch_buffers(gpry_ctx* ctx, int64_t arena_doubles, int64_t re
 static bool lml_batch_usable(const gpry_ctx* ctx) {
     return ctx->N > 0 && ctx->Np > 128 && ctx->Np <= ctx->opt_lml_batch && ctx->d <= 32 && ctx->opt_chol == 0;
 }
-static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad, double* lml, double* grad, int* info) {
+// the LML's chain as objective_batch_general runs it (gpry_loo_objective_batch hands in its own: loo_fit.hip)
+static const BatchChain LML_BATCH = {"lml_batch", lml_chain, false, 0, 0, 2, RES_INFO,
+                                     [](const double* o) { return -0.5 * o[1] - o[0]; }};
+int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* thetas, int64_t B, int want_grad, double* lml, double* grad,
+                            int* info) {
     const int w = ctx_ntheta(ctx);
     for (int64_t i = 0; i < B * w; i++)
         if (!isfinite(thetas[i])) return gpry_fail(ctx, -1, "theta[%d] is not finite", (int)(i % w));
@@ -203,10 +213,11 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
     // THE THROUGHPUT SCHEDULE (option "lml_schedule" = 1; gpry_ctx::opt_lml_schedule): whole-tile products only, the recursive
     // inverse at every size, the Cholesky in column blocks, the thetas of a chunk dealt over stream groups.  Everything a theta's
     // result depends on is a function of the model size alone -- never of B, of the chunking or of the grouping.
-    const bool tp = ctx->opt_lml_schedule == 1;
+    // (a chain without that form -- the leave-one-out objective's -- runs the latency schedule whatever the option says)
+    const bool tp = !bc.latency_only && ctx->opt_lml_schedule == 1;
     ctx->tp = tp;
     BatchLayout L;
-    GPRY_TRY(batch_layout(ctx, &L));
+    GPRY_TRY(batch_layout(ctx, bc, &L));
     // thetas per chain: the diagonal workgroup of a panel step waits for the other workgroups of ITS theta to have read the
     // block it overwrites -- only those wait, one per theta, so any number well below the GPU's workgroup slots is safe
     int64_t chunk = B < 96 ? B : 96;
@@ -227,7 +238,7 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
     const int64_t min_chunk = tp ? 1 : 2;
     if (chunk < min_chunk) {
         if (!tp) return 1;
-        return gpry_fail(ctx, -2, "lml_batch: no device memory for one scratch set (%lld MiB)", (long long)((8 * L.stride) >> 20));
+        return gpry_fail(ctx, -2, "%s: no device memory for one scratch set (%lld MiB)", bc.name, (long long)((8 * L.stride) >> 20));
     }
     // a failed allocation (another context took the memory in between) halves the chunk; below `min_chunk` sets the thetas go
     // through one after another instead of the fit failing (latency schedule).  Only an out-of-memory answer is retried.
@@ -239,9 +250,10 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
         chunk /= 2;
         if (chunk < min_chunk) {
             if (!tp) return 1;
-            return gpry_fail(ctx, -2, "lml_batch: no device memory for one scratch set");
+            return gpry_fail(ctx, -2, "%s: no device memory for one scratch set", bc.name);
         }
     }
+    ctx->batch_set_doubles = L.stride; ctx->batch_chunk = chunk;
     double* hres = static_cast<double*>(ctx->hbres);
     double* hpar = hres + chunk * GPRY_BRES_STRIDE;         // [C, l_1 .. l_d] rows of a chunk, staged in the pinned buffer
     double* a0 = ctx->barena;
@@ -266,7 +278,7 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
             row[0] = exp(th[0]);                                     // as make_kp / make_ap for one evaluation
             for (int k = 0; k < ctx->d; k++) row[1 + k] = exp(th[1 + k]);
             row[GPRY_BPAR_WHITE] = ctx->white ? exp(th[1 + ctx->d]) : 0.0;
-            hres[b * GPRY_BRES_STRIDE + RES_INFO] = -1.0; hres[b * GPRY_BRES_STRIDE + RES_INFO + 1] = -1.0;     // "not written"
+            hres[b * GPRY_BRES_STRIDE + bc.info_at] = -1.0; hres[b * GPRY_BRES_STRIDE + bc.info_at + 1] = -1.0;     // "not written"
         }
         for (int k = 0; k < w; k++) ctx->theta[k] = thetas[b0 * w + k];      // (the launchers read the sizes, not these, in a batch)
         // test hook ("panel_debug" bit 7): every scratch set starts as NaNs -- a result that depended on what a set held before shows
@@ -292,7 +304,7 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
             HIP_TRY(ctx, hipEventRecord(ctx->tp_events[0], main_stream));        // the parameters are on the device
         }
         {
-            StageScope s(ctx, "lml_batch", main_stream);
+            StageScope s(ctx, bc.name, main_stream);
             int64_t t0 = 0;
             int rc = 0;
             for (int g = 0; g < G && rc == 0; g++) {
@@ -300,10 +312,10 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
                 const hipStream_t st = g == 0 ? main_stream : ctx->tp_streams[(size_t)g - 1];
                 if (g > 0) {
                     const hipError_t e = hipStreamWaitEvent(st, ctx->tp_events[0], 0);
-                    if (e != hipSuccess) { rc = gpry_fail(ctx, -2, "lml_batch: %s", hipGetErrorString(e)); break; }
+                    if (e != hipSuccess) { rc = gpry_fail(ctx, -2, "%s: %s", bc.name, hipGetErrorString(e)); break; }
                 }
                 point_at(t0, n, st);
-                rc = lml_chain(ctx, want_grad, static_cast<double*>(ctx->hbres_dev) + t0 * GPRY_BRES_STRIDE);
+                rc = bc.chain(ctx, want_grad, static_cast<double*>(ctx->hbres_dev) + t0 * GPRY_BRES_STRIDE);
                 t0 += n;
             }
             // the main stream joins the groups (also on the error path: nothing of this call may still be in flight afterwards)
@@ -318,9 +330,9 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
         HIP_TRY(ctx, hipStreamSynchronize(main_stream));
         for (int64_t b = 0; b < nb; b++) {
             const double* o = hres + b * GPRY_BRES_STRIDE;
-            if (o[RES_INFO] < 0.0) return gpry_fail(ctx, -2, "lml_batch: evaluation %lld did not deliver its status", (long long)(b0 + b));
-            const int i0 = (int)o[RES_INFO], i1 = (int)o[RES_INFO + 1];
-            if (panel_timed_out((int)o[RES_INFO + 2])) return panel_timeout_error(ctx, (int)o[RES_INFO + 2]);
+            if (o[bc.info_at] < 0.0) return gpry_fail(ctx, -2, "%s: evaluation %lld did not deliver its status", bc.name, (long long)(b0 + b));
+            const int i0 = (int)o[bc.info_at], i1 = (int)o[bc.info_at + 1];
+            if (panel_timed_out((int)o[bc.info_at + 2])) return panel_timeout_error(ctx, (int)o[bc.info_at + 2]);
             const int inf = i0 != 0 ? i0 : i1;
             if (info) info[b0 + b] = inf;
             if (inf != 0) {   // sklearn:_gpr.py:586-589
@@ -328,8 +340,8 @@ static int lml_batch_general(gpry_ctx* ctx, const double* thetas, int64_t B, int
                 if (want_grad) for (int k = 0; k < w; k++) grad[(b0 + b) * w + k] = 0.0;
                 continue;
             }
-            lml[b0 + b] = -0.5 * o[1] - o[0] - 0.5 * (double)ctx->N * log2pi;
-            if (want_grad) for (int k = 0; k < w; k++) grad[(b0 + b) * w + k] = o[2 + k];
+            lml[b0 + b] = bc.value(o) - 0.5 * (double)ctx->N * log2pi;
+            if (want_grad) for (int k = 0; k < w; k++) grad[(b0 + b) * w + k] = o[bc.head + k];
         }
     }
     return 0;
@@ -521,7 +533,7 @@ int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, dou
 
 // B objective evaluations in one call: the optimiser runs of a multi-restart fit stepped side by side (gpry/gpr.py:883-994 runs
 // them one after another).  N <= 128, d <= 16: ONE launch, one workgroup per theta (lml_small.hip); up to Np = lml_batch
-// (default 4096): ONE chain of launches for all thetas (lml_batch_general) -- either way every theta gets the arithmetic of a
+// (default 4096): ONE chain of launches for all thetas (objective_batch_general) -- either way every theta gets the arithmetic of a
 // single gpry_lml call, hence the same bits; otherwise the thetas are evaluated one after another.
 int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad, double* lml, double* grad, int* info) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_lml_batch: ctx is NULL");
@@ -532,7 +544,7 @@ int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad
     for (int64_t i = 0; fused && i < B * w; i++) fused = isfinite(thetas[i]);
     // (throughput schedule: a single theta goes through the chain of the many as well -- its result must not depend on B)
     if (!fused && (B >= 2 || ctx->opt_lml_schedule == 1) && lml_batch_usable(ctx)) {
-        const int r = lml_batch_general(ctx, thetas, B, want_grad, lml, grad, info);
+        const int r = objective_batch_general(ctx, LML_BATCH, thetas, B, want_grad, lml, grad, info);
         if (r <= 0) return r;               // 1: no room for two sets, one after another below
     }
     if (!fused) {

@@ -12,12 +12,15 @@
 
 // ------------------------------------------------------------------------------------
 // Inverse of every 64x64 diagonal block: lane c solves L x = e_c by forward substitution
-// (L broadcast from LDS, x in registers).  Writes zeros above the diagonal.
-__global__ __launch_bounds__(64) void trtri_diag_kernel(const double* __restrict__ L,
-                                                        double* __restrict__ V, int64_t ld,
-                                                        const int* info) {
+// (L broadcast from LDS, x in registers).  Writes zeros above the diagonal.  grid.z: the thetas of a batched launch
+// (gpry_ctx::bn; only gpry_loo_objective_batch comes here in a batch: Np = 128 with the stacked factor chain switched off).
+__global__ __launch_bounds__(64) void trtri_diag_kernel(const double* __restrict__ L_,
+                                                        double* __restrict__ V_, int64_t ld,
+                                                        const int* info, int64_t bstride) {
     __shared__ double Lk[64 * 64];
-    if (*info != 0) return;
+    if (*bset(info, (int)blockIdx.z, bstride) != 0) return;
+    const double* __restrict__ L = bset(L_, (int)blockIdx.z, bstride);
+    double* __restrict__ V = bset(V_, (int)blockIdx.z, bstride);
     const int t = threadIdx.x;
     const int64_t b0 = (int64_t)blockIdx.x * 64;
     for (int e = t; e < 64 * 64; e += 64) {
@@ -341,9 +344,9 @@ int trtri_lower(gpry_ctx* ctx, const double* L, double* V, double* T, int64_t Np
     } else if (!clear_in_diag) HIP_TRY(ctx, hipMemsetAsync(V, 0, sizeof(double) * Np * Np, st));
     TrtriPlan* pl = nullptr;
     GPRY_TRY(trtri_plan_get(ctx, Np, &pl));
-    if (single_wave && ctx->bn > 1) return gpry_fail(ctx, -1, "batched chain: the single-wave diagonal stage is not batched");
     if (single_wave) {
-        hipLaunchKernelGGL(trtri_diag_kernel, dim3((unsigned)(Np / 64)), dim3(64), 0, st, L, V, Np, ctx->dinfo);
+        hipLaunchKernelGGL(trtri_diag_kernel, dim3((unsigned)(Np / 64), 1, (unsigned)ctx->bn), dim3(64), 0, st, L, V, Np, ctx->dinfo,
+                           ctx->bstride);
         HIP_TRY(ctx, hipGetLastError());
     } else if (pl->leaf == 2) {         // (128 < Np <= 1024: exactly the sizes that clear in the diagonal stage)
         GPRY_TRY(launch_trtri_diag128(ctx, L, V, Np, st, !tp_min_clear));

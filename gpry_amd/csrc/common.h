@@ -89,10 +89,11 @@ struct gpry_ctx {
     int64_t opt_tp_block = 512;        // throughput schedule: width of the column blocks of the Cholesky (multiple of 128)
     int opt_tp_left = 0;               // throughput schedule: 0 = the column blocks right-looking (one launch of the block's width behind each; default: measured ahead), 1 = left-looking (one deep launch in front of each); same bits
     int64_t opt_tp_tail = 1024;        // ... and the size of the last block, factored with riding tiles only
+    int64_t batch_set_doubles = 0, batch_chunk = 0;     // the last batched evaluation's scratch set and thetas per chain (diagnostic, gpry_timing_get)
     int64_t batch_shrinks = 0;         // times a batched evaluation halved its chunk after an out-of-memory answer (diagnostic, gpry_timing_get "lml_batch_shrinks")
     int opt_chol_tp_segments = 0;      // 1: every factorisation of the context takes the column blocks of the throughput schedule (comparator: same bits)
     int opt_panel_debug = 0;           // ORed into GPRY_PANEL_FLAGS (chol_panel.hip); 64: the diagonal workgroup of every panel step reports a timed-out wait (test hook)
-    bool tp = false;                   // a throughput-schedule chain is being queued (set by lml_batch_general only)
+    bool tp = false;                   // a throughput-schedule chain is being queued (set by objective_batch_general only)
     std::vector<hipStream_t> tp_streams;   // the extra streams of the groups (created on first use)
     std::vector<hipEvent_t> tp_events;
 
@@ -508,6 +509,20 @@ bool panel_timed_out(int marker);                       // fourth status word: a
 int panel_timeout_error(gpry_ctx* ctx, int marker);
 // loo.hip: gpry_loo's pass over an inverse factor V (partial sums per 64 x 64 tile; ceil(N / 64) x Np doubles each)
 int loo_pass_launch(gpry_ctx* ctx, const double* V, double* qpart, double* wpart);
+// api.hip: the B thetas of a call in ONE chain of launches (arena of scratch sets, chunking, parameter and result staging) --
+// the chain itself is the caller's: gpry_lml_batch's (lml_chain) or gpry_loo_objective_batch's (loo_fit.hip).  A chain is the
+// code of a single evaluation that honours gpry_ctx::bn / bstride / bpar and writes theta tb's results to row tb of `dres`.
+struct BatchChain {
+    const char* name;                                       // stage timer and roctx range around a chunk; prefix of the messages
+    int (*chain)(gpry_ctx* ctx, int want_grad, double* dres);
+    bool latency_only;                                      // no throughput-schedule form: option "lml_schedule" is not read
+    int64_t part_min, split_min;                            // doubles the chain's tail needs of the `part` and `split` pieces (0: the factor chain's)
+    int head, info_at;                                      // result row: the gradient from `head`, the status words from `info_at`
+    double (*value)(const double* row);                     // the objective from the row's head, without - N/2 log 2 pi
+};
+// returns 1 where fewer than two scratch sets fit (latency schedule: the caller evaluates one theta after another -- same bits)
+int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* thetas, int64_t B, int want_grad, double* value,
+                            double* grad, int* info);
 
 int ensure_capacity(gpry_ctx* ctx, int64_t N, int d);
 int ensure_pinned(gpry_ctx* ctx, int64_t bytes);

@@ -435,6 +435,8 @@ int gpry_timing_get(gpry_ctx* ctx, const char* name, double* total_ms, int64_t* 
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_timing_get: ctx is NULL");
     // (not a timer: how often a batched objective halved its chunk after an out-of-memory answer since the context was created)
     if (name && !strcmp(name, "lml_batch_shrinks")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->batch_shrinks; return 0; }
+    if (name && !strcmp(name, "batch_set_doubles")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->batch_set_doubles; return 0; }
+    if (name && !strcmp(name, "batch_chunk")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->batch_chunk; return 0; }
     // (not timers either: what ensure_capacity has allocated, in training rows and in padded columns)
     if (name && !strcmp(name, "capacity_rows")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->cap; return 0; }
     if (name && !strcmp(name, "capacity_cols")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->dp_cap; return 0; }

@@ -45,10 +45,14 @@ struct LgoGroup {
     int n, np, c0, pad;     // size, padded size, first chunk that holds a non-zero row
 };
 
-// grid: the lower-triangle tiles (ti, tj), tj <= ti, of the leading nt x nt tiles; 256 threads
-__global__ __launch_bounds__(256) void loo_pass_kernel(const double* __restrict__ V, int64_t Np, int64_t N,
-                                                       const double* __restrict__ y, double* __restrict__ qpart,
-                                                       double* __restrict__ wpart) {
+// grid: the lower-triangle tiles (ti, tj), tj <= ti, of the leading nt x nt tiles; 256 threads.  grid.z: the thetas of a
+// batched objective (gpry_ctx::bn) -- V and the partial sums of theta blockIdx.z lie bstride doubles further on; y is shared
+__global__ __launch_bounds__(256) void loo_pass_kernel(const double* __restrict__ V_, int64_t Np, int64_t N,
+                                                       const double* __restrict__ y, double* __restrict__ qpart_,
+                                                       double* __restrict__ wpart_, int64_t bstride) {
+    const double* __restrict__ V = bset(V_, (int)blockIdx.z, bstride);
+    double* __restrict__ qpart = bset(qpart_, (int)blockIdx.z, bstride);
+    double* __restrict__ wpart = bset(wpart_, (int)blockIdx.z, bstride);
     __shared__ double sV[LOO_T * LOO_LD];
     __shared__ double sY[LOO_T];
     __shared__ double sQ[4 * LOO_T], sW[4 * LOO_T];
@@ -271,8 +275,8 @@ int loo_require(gpry_ctx* ctx, const char* who) {
 // the partial sums -- and q_i once they are added ascending -- are the bits gpry_loo forms for the same model
 int loo_pass_launch(gpry_ctx* ctx, const double* V, double* qpart, double* wpart) {
     const int nt = (int)((ctx->N + LOO_T - 1) / LOO_T);
-    hipLaunchKernelGGL(loo_pass_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, ctx->stream, V, ctx->Np, ctx->N, ctx->dy,
-                       qpart, wpart);
+    hipLaunchKernelGGL(loo_pass_kernel, dim3((unsigned)(nt * (nt + 1) / 2), 1, (unsigned)ctx->bn), dim3(256), 0, ctx->stream, V, ctx->Np,
+                       ctx->N, ctx->dy, qpart, wpart, ctx->bstride);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -303,7 +307,7 @@ int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* 
     {
         StageScope scope(ctx, "loo");
         hipLaunchKernelGGL(loo_pass_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, ctx->dV, Np, N, ctx->dy,
-                           qpart, wpart);
+                           qpart, wpart, (int64_t)0);
         hipLaunchKernelGGL(loo_finish_kernel, dim3((unsigned)nt), dim3(LOO_T), 0, st, ctx->dV, Np, N, nt, qpart, wpart, ctx->dy,
                            ctx->dalpha_, ctx->dnoise, ctx_white(ctx), ctx->white ? 1 : 0, ctx->tf.y_mean, ctx->tf.y_std, out);
         HIP_TRY(ctx, hipGetLastError());

@@ -19,6 +19,12 @@
 // a fixed order and hands everything to the host through mapped memory.  Rows and columns of the padding are masked to
 // zero wherever they are read, so what the factor chain leaves there does not matter.
 //
+// gpry_loo_objective_batch: B thetas through ONE such chain (the arena, the chunking and the staging of gpry_lml_batch:
+// objective_batch_general, api.hip).  Every kernel here takes its theta from blockIdx.z and moves its per-theta pointers by
+// bset(p, blockIdx.z, bstride); C and w come from the theta's parameter row.  Tile maps, the split of the Gram product and
+// every summation order are functions of the model size alone, so a theta's bits are those of a single evaluation whatever
+// B, its position in the batch, the chunking and its neighbours.
+//
 // The evaluation works in the objective's scratch (dW, dW2, dW3, dvec, dpart, dsplit) alone: the factor held for
 // prediction, a Kriging-believer session, the resident pool and ctx->dloo are not touched.  L and V of the scratch are
 // overwritten (H, M), so the factor cache of gpry_lml is cleared: gpry_factorize never adopts them.
@@ -43,10 +49,18 @@ __device__ __forceinline__ void lf_tri(int64_t t, int* bi, int* bj) {
 // grid: Np / 64 workgroups of one wave.  q_i from the partial sums of loo_pass_kernel in loo_finish_kernel's order; the
 // point's term of the value; s_i = sqrt(-c_i), a_i = alpha_i / q_i; zeros in the padding.  vpart[tile]: the tile's 64
 // terms added by a fixed butterfly.
-__global__ __launch_bounds__(64) void loo_fit_terms_kernel(const double* __restrict__ qpart, int64_t Np, int64_t N, int nt,
-                                                            const double* __restrict__ alpha, double* __restrict__ q_out,
-                                                            double* __restrict__ s_out, double* __restrict__ a_out,
-                                                            double* __restrict__ vpart) {
+__global__ __launch_bounds__(64) void loo_fit_terms_kernel(const double* __restrict__ qpart_, int64_t Np, int64_t N, int nt,
+                                                            const double* __restrict__ alpha_, double* __restrict__ q_out_,
+                                                            double* __restrict__ s_out_, double* __restrict__ a_out_,
+                                                            double* __restrict__ vpart_, int64_t bstride) {
+    // batched launch (gpry_ctx::bn): the buffers of theta blockIdx.z
+    const int z = (int)blockIdx.z;
+    const double* __restrict__ qpart = bset(qpart_, z, bstride);
+    const double* __restrict__ alpha = bset(alpha_, z, bstride);
+    double* __restrict__ q_out = bset(q_out_, z, bstride);
+    double* __restrict__ s_out = bset(s_out_, z, bstride);
+    double* __restrict__ a_out = bset(a_out_, z, bstride);
+    double* __restrict__ vpart = bset(vpart_, z, bstride);
     const int tb = (int)blockIdx.x, lane = threadIdx.x;
     const int64_t i = (int64_t)tb * LF_T + lane;
     double q = 0.0, s = 0.0, a = 0.0, term = 0.0;
@@ -69,9 +83,16 @@ __global__ __launch_bounds__(64) void loo_fit_terms_kernel(const double* __restr
 // H = diag(s) K^-1 and, off the diagonal, its mirror image (H is a full square), and the tile's share of b = K^-1 a:
 // bpart[t][k], t = 0 .. Np / 64 - 1, holds for row k of tile row tk the product with the columns of tile t -- from tile
 // (tk, t) for t <= tk, from the transpose of tile (t, tk) above it; every entry has exactly one writer.
-__global__ __launch_bounds__(256) void loo_fit_mirror_kernel(const double* __restrict__ Kinv, int64_t Np, int64_t N,
-                                                             const double* __restrict__ s, const double* __restrict__ a,
-                                                             double* __restrict__ H, double* __restrict__ bpart) {
+__global__ __launch_bounds__(256) void loo_fit_mirror_kernel(const double* __restrict__ Kinv_, int64_t Np, int64_t N,
+                                                             const double* __restrict__ s_, const double* __restrict__ a_,
+                                                             double* __restrict__ H_, double* __restrict__ bpart_, int64_t bstride) {
+    // batched launch (gpry_ctx::bn): the buffers of theta blockIdx.z -- pointer arithmetic on entry, nothing else changes
+    const int z = (int)blockIdx.z;
+    const double* __restrict__ Kinv = bset(Kinv_, z, bstride);
+    const double* __restrict__ s = bset(s_, z, bstride);
+    const double* __restrict__ a = bset(a_, z, bstride);
+    double* __restrict__ H = bset(H_, z, bstride);
+    double* __restrict__ bpart = bset(bpart_, z, bstride);
     __shared__ double sT[LF_T * LF_LD];
     __shared__ double sAr[LF_T], sAc[LF_T], sSr[LF_T], sSc[LF_T];
     __shared__ double sR[4 * LF_T], sC[4 * LF_T];
@@ -124,8 +145,10 @@ __global__ __launch_bounds__(256) void loo_fit_mirror_kernel(const double* __res
 }
 
 // b_k = sum over the tiles t ascending of bpart[t][k]
-__global__ __launch_bounds__(256) void loo_fit_bsum_kernel(const double* __restrict__ bpart, int64_t Np, int nb,
-                                                           double* __restrict__ b) {
+__global__ __launch_bounds__(256) void loo_fit_bsum_kernel(const double* __restrict__ bpart_, int64_t Np, int nb,
+                                                           double* __restrict__ b_, int64_t bstride) {
+    const double* __restrict__ bpart = bset(bpart_, (int)blockIdx.z, bstride);
+    double* __restrict__ b = bset(b_, (int)blockIdx.z, bstride);
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= Np) return;
     double v = 0.0;
@@ -141,9 +164,17 @@ __global__ __launch_bounds__(256) void loo_fit_bsum_kernel(const double* __restr
 // part[tile][DP + 1] (a model with a white term, diagonal tiles): sum_k (b_k alpha_k - M_kk) -- the finish multiplies by w.
 template <int DP, int KID>
 __global__ __launch_bounds__(256) void loo_fit_traces_kernel(
-    const double* __restrict__ Xs, const double* __restrict__ M, int64_t ld, const double* __restrict__ alpha,
-    const double* __restrict__ b, double* __restrict__ part, KernParams kp) {
-    constexpr int XLD = 66;         // (lml_traces_kernel: 64 puts the sixteen k of a row into one pair of LDS banks)
+    const double* __restrict__ Xs_, const double* __restrict__ M_, int64_t ld, const double* __restrict__ alpha_,
+    const double* __restrict__ b_, double* __restrict__ part_, KernParams kp, const double* __restrict__ bpar, int64_t bstride) {
+    // batched launch (gpry_ctx::bn): the buffers and the constant of theta blockIdx.z, as lml_traces_kernel
+    const double* __restrict__ Xs = bset(Xs_, (int)blockIdx.z, bstride);
+    const double* __restrict__ M = bset(M_, (int)blockIdx.z, bstride);
+    const double* __restrict__ alpha = bset(alpha_, (int)blockIdx.z, bstride);
+    const double* __restrict__ b = bset(b_, (int)blockIdx.z, bstride);
+    double* __restrict__ part = bset(part_, (int)blockIdx.z, bstride);
+    if (bpar) kp.C = bset(bpar, (int)blockIdx.z, bstride)[0];
+    // (the white entry needs no w here: the diagonal tiles leave tr W', loo_fit_finish_kernel multiplies)
+    constexpr int XLD = 66;        // (lml_traces_kernel: 64 puts the sixteen k of a row into one pair of LDS banks)
     __shared__ __attribute__((aligned(16))) double Xi[DP * XLD];
     __shared__ __attribute__((aligned(16))) double Xj[DP * XLD];
     __shared__ double ai[64], aj[64], bi_[64], bj_[64];
@@ -272,11 +303,20 @@ __global__ __launch_bounds__(256) void loo_fit_traces_kernel(
 
 // Last kernel of an evaluation.  Workgroup k < nth (with a gradient): entry k of the gradient, strided partial sums and
 // a fixed LDS tree as reduce_traces_kernel; workgroup 0 also adds the value's partial sums ascending and hands the
-// factorisation status on.  Everything goes straight into the mapped host buffer.
-__global__ __launch_bounds__(256) void loo_fit_finish_kernel(const double* __restrict__ part, int64_t ntile, int stride, int want_grad,
+// factorisation status on.  Everything goes straight into the mapped host buffer: theta blockIdx.z of a batched launch
+// writes row blockIdx.z (GPRY_BRES_STRIDE doubles) and multiplies the white entry by ITS w (parameter row).
+static_assert(LF_INFO + 3 <= GPRY_BRES_STRIDE, "result row too short");
+__global__ __launch_bounds__(256) void loo_fit_finish_kernel(const double* __restrict__ part_, int64_t ntile, int stride, int want_grad,
                                                              int nplain, int white_col, double white,
-                                                             const double* __restrict__ vpart, int nv, const int* __restrict__ info,
-                                                             double* __restrict__ host_res) {
+                                                             const double* __restrict__ vpart_, int nv, const int* __restrict__ info_,
+                                                             double* __restrict__ host_res, const double* __restrict__ bpar,
+                                                             int64_t bstride) {
+    const int tb = (int)blockIdx.z;
+    if (bpar) white = bset(bpar, tb, bstride)[GPRY_BPAR_WHITE];
+    const double* __restrict__ part = bset(part_, tb, bstride);
+    const double* __restrict__ vpart = bset(vpart_, tb, bstride);
+    const int* __restrict__ info = bset(info_, tb, bstride);
+    host_res += (int64_t)tb * GPRY_BRES_STRIDE;
     __shared__ double red[256];
     const int k = blockIdx.x, t = threadIdx.x;
     if (want_grad) {
@@ -302,19 +342,44 @@ __global__ __launch_bounds__(256) void loo_fit_finish_kernel(const double* __res
 
 namespace {
 
-// the launches of one evaluation at the theta the context holds; results and status land in `dres` (mapped host memory)
+// What an evaluation needs of the partial-sum buffer and of the split-K scratch -- functions of the model size alone.  The
+// single evaluation grows the context's buffers to it before its first launch; a batched one sizes the arena's pieces by it.
+// part: q and w of the pass over V | b | traces -- and solve_alpha's partial sums, which are done with by then.
+struct LooFitPlan {
+    int nt, nb, DPsel, nsplit;                      // row tiles with training rows, 64-row tiles, width class of the traces, split of M = H^T H
+    int64_t ntile, o_q, o_w, o_b, o_tr, need;       // offsets into the partial sums and their total (doubles)
+};
+LooFitPlan loo_fit_plan(const gpry_ctx* ctx) {
+    LooFitPlan p;
+    const int64_t Np = ctx->Np;
+    p.nt = (int)((ctx->N + LF_T - 1) / LF_T); p.nb = (int)(Np / LF_T);
+    p.ntile = (int64_t)p.nb * (p.nb + 1) / 2;
+    p.DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    p.o_q = 0; p.o_w = p.o_q + (int64_t)p.nt * Np; p.o_b = p.o_w + (int64_t)p.nt * Np; p.o_tr = p.o_b + (int64_t)p.nb * Np;
+    p.need = p.o_tr + p.ntile * (p.DPsel + 2);
+    const int64_t need_solve = ((Np + 255) / 256) * Np;
+    if (p.need < need_solve) p.need = need_solve;
+    // the split of K^-1 = V^T V's engine launch (lauum_lower)
+    const int64_t tiles = (Np / 128) * (Np / 128 + 1) / 2;
+    p.nsplit = 1;
+    while (p.nsplit < 4 && tiles * p.nsplit * 2 <= 1100 && Np / (p.nsplit * 2) >= 256) p.nsplit *= 2;
+    return p;
+}
+
+// the launches of one evaluation at the theta the context holds -- or, in a batched evaluation (gpry_ctx::bn), at the bn
+// thetas whose parameter rows sit in the arena; results and status land in `dres` (mapped host memory; theta tb at row tb
+// of GPRY_BRES_STRIDE doubles)
 int loo_fit_chain(gpry_ctx* ctx, int want_grad, double* dres) {
     const int64_t Np = ctx->Np, N = ctx->N;
-    const int nt = (int)((N + LF_T - 1) / LF_T), nb = (int)(Np / LF_T);
-    const int64_t ntile = (int64_t)nb * (nb + 1) / 2;
-    const int DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
-    // partial sums: q and w of the pass over V | b | traces -- and solve_alpha's, which are done with by then.  Sized before
-    // the first launch: nothing is re-allocated under way.
-    const int64_t o_q = 0, o_w = o_q + (int64_t)nt * Np, o_b = o_w + (int64_t)nt * Np, o_tr = o_b + (int64_t)nb * Np;
-    int64_t need = o_tr + ntile * (DPsel + 2);
-    const int64_t need_solve = ((Np + 255) / 256) * Np;
-    if (need < need_solve) need = need_solve;
-    GPRY_TRY(dev_grow(ctx, &ctx->dpart, &ctx->part_cap, need));
+    const LooFitPlan pl = loo_fit_plan(ctx);
+    const int nt = pl.nt, nb = pl.nb, DPsel = pl.DPsel;
+    const int64_t ntile = pl.ntile, o_q = pl.o_q, o_w = pl.o_w, o_b = pl.o_b, o_tr = pl.o_tr;
+    // Sized before the first launch: nothing is re-allocated under way.  (A batched evaluation works in the arena: its
+    // pieces were sized by the same plan and never grow.)
+    if (pl.need > ctx->part_cap && ctx->bpar) return gpry_fail(ctx, -1, "batched chain: partial sums exceed the arena");
+    GPRY_TRY(dev_grow(ctx, &ctx->dpart, &ctx->part_cap, pl.need));
+    const unsigned bn = (unsigned)ctx->bn;
+    const int64_t bs = ctx->bstride;
     GPRY_TRY(build_factor(ctx, ctx->dW, ctx->dW2, ctx->dW3, nullptr));
     hipStream_t st = ctx->stream;
     double* dz = ctx->dvec;                 // z = V y
@@ -329,7 +394,8 @@ int loo_fit_chain(gpry_ctx* ctx, int want_grad, double* dres) {
     {
         StageScope s(ctx, "loo_q");
         GPRY_TRY(loo_pass_launch(ctx, ctx->dW2, part + o_q, part + o_w));
-        hipLaunchKernelGGL(loo_fit_terms_kernel, dim3((unsigned)nb), dim3(LF_T), 0, st, part + o_q, Np, N, nt, da, dq, ds, daq, dvp);
+        hipLaunchKernelGGL(loo_fit_terms_kernel, dim3((unsigned)nb, 1, bn), dim3(LF_T), 0, st, part + o_q, Np, N, nt, da, dq, ds, daq,
+                           dvp, bs);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (want_grad) {
@@ -340,8 +406,9 @@ int loo_fit_chain(gpry_ctx* ctx, int want_grad, double* dres) {
         {
             // H into dW: L is dead (the objective needs no log-determinant)
             StageScope s(ctx, "loo_mirror");
-            hipLaunchKernelGGL(loo_fit_mirror_kernel, dim3((unsigned)ntile), dim3(256), 0, st, ctx->dW3, Np, N, ds, daq, ctx->dW, part + o_b);
-            hipLaunchKernelGGL(loo_fit_bsum_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, part + o_b, Np, nb, db);
+            hipLaunchKernelGGL(loo_fit_mirror_kernel, dim3((unsigned)ntile, 1, bn), dim3(256), 0, st, ctx->dW3, Np, N, ds, daq, ctx->dW,
+                               part + o_b, bs);
+            hipLaunchKernelGGL(loo_fit_bsum_kernel, dim3((unsigned)((Np + 255) / 256), 1, bn), dim3(256), 0, st, part + o_b, Np, nb, db, bs);
             HIP_TRY(ctx, hipGetLastError());
         }
         {
@@ -351,9 +418,7 @@ int loo_fit_chain(gpry_ctx* ctx, int want_grad, double* dres) {
             g.A = ctx->dW; g.lda = Np; g.B = ctx->dW; g.ldb = Np; g.C = ctx->dW2; g.ldc = Np;
             g.M = (int)Np; g.N = (int)Np; g.K = (int)Np;
             g.kmode = KM_FULL; g.lower_only = 1; g.tile_map = TM_ROWMAJOR; g.info = ctx->dinfo;
-            const int64_t tiles = (Np / 128) * (Np / 128 + 1) / 2;
-            int nsplit = 1;
-            while (nsplit < 4 && tiles * nsplit * 2 <= 1100 && Np / (nsplit * 2) >= 256) nsplit *= 2;
+            const int nsplit = pl.nsplit;
             if (nsplit > 1) {
                 double* sbuf = nullptr;
                 GPRY_TRY(gemm_split_scratch(ctx, nsplit, Np * Np, &sbuf));
@@ -366,8 +431,8 @@ int loo_fit_chain(gpry_ctx* ctx, int want_grad, double* dres) {
     StageScope s(ctx, "loo_traces");
     const KernParams kp = make_kp(ctx);
     if (want_grad) {
-#define LFT2(DP, KID) hipLaunchKernelGGL((loo_fit_traces_kernel<DP, KID>), dim3((unsigned)ntile), dim3(256), 0, st, ctx->dXs, \
-                                         ctx->dW2, Np, da, db, part + o_tr, kp)
+#define LFT2(DP, KID) hipLaunchKernelGGL((loo_fit_traces_kernel<DP, KID>), dim3((unsigned)ntile, 1, bn), dim3(256), 0, st, ctx->dXs, \
+                                         ctx->dW2, Np, da, db, part + o_tr, kp, ctx->bpar, bs)
 #define LFT4(KID) { if (DPsel == 4) LFT2(4, KID); else if (DPsel == 8) LFT2(8, KID); \
                     else if (DPsel == 16) LFT2(16, KID); else if (DPsel == 24) LFT2(24, KID); else LFT2(32, KID); }
         DISPATCH_KID(ctx->kernel_id, LFT4)
@@ -375,8 +440,8 @@ int loo_fit_chain(gpry_ctx* ctx, int want_grad, double* dres) {
 #undef LFT2
         HIP_TRY(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(loo_fit_finish_kernel, dim3((unsigned)(want_grad ? ctx_ntheta(ctx) : 1)), dim3(256), 0, st, part + o_tr, ntile,
-                       DPsel + 2, want_grad, ctx->d + 1, DPsel + 1, kp.white, dvp, nb, ctx->dinfo, dres);
+    hipLaunchKernelGGL(loo_fit_finish_kernel, dim3((unsigned)(want_grad ? ctx_ntheta(ctx) : 1), 1, bn), dim3(256), 0, st, part + o_tr,
+                       ntile, DPsel + 2, want_grad, ctx->d + 1, DPsel + 1, kp.white, dvp, nb, ctx->dinfo, dres, ctx->bpar, bs);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -427,6 +492,44 @@ int gpry_loo_objective(gpry_ctx* ctx, const double* theta, int want_grad, double
     }
     *value = hres[0] - 0.5 * (double)ctx->N * log(2.0 * M_PI);
     if (want_grad) for (int k = 0; k < nth; k++) grad[k] = hres[1 + k];
+    return 0;
+}
+
+// B evaluations in one call: the optimiser runs of a "loo" fit stepped side by side (gpry_amd/lockstep.py), as gpry_lml_batch
+// serves the LML's (the reference runs its restarts one after another, gpry/gpr.py:968-984).  From Np = 128 -- there is no
+// single-launch form of this objective -- up to option "lml_batch": ONE chain of launches for all thetas of a chunk
+// (objective_batch_general, api.hip, with loo_fit_chain as its chain), always in the latency schedule: option "lml_schedule"
+// concerns gpry_lml_batch alone.  Above that, with the rocSOLVER comparator or where fewer than two scratch sets fit: one
+// gpry_loo_objective after another.  Either way every theta gets the launches of a single evaluation, hence its bits.
+int gpry_loo_objective_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad, double* value, double* grad, int* info) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_loo_objective_batch: ctx is NULL");
+    GPRY_TRY(serve_stop(ctx));
+    if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
+    if (B <= 0) return gpry_fail(ctx, -1, "loo_objective_batch: B = %lld thetas", (long long)B);
+    if (!thetas || !value || (want_grad && !grad))
+        return gpry_fail(ctx, -1, "loo_objective_batch: thetas, value and (with want_grad) grad must not be NULL");
+    const int w = ctx_ntheta(ctx);
+    for (int64_t i = 0; i < B * w; i++)
+        if (!isfinite(thetas[i])) return gpry_fail(ctx, -1, "theta[%d] of evaluation %lld is not finite", (int)(i % w), (long long)(i / w));
+    if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
+    if (B >= 2 && ctx->Np >= 128 && ctx->Np <= ctx->opt_lml_batch && ctx->opt_chol == 0) {
+        const LooFitPlan pl = loo_fit_plan(ctx);
+        const BatchChain bc = {"loo_batch", loo_fit_chain, true, pl.need, pl.nsplit > 1 ? (int64_t)pl.nsplit * ctx->Np * ctx->Np : 0,
+                               1, LF_INFO, [](const double* o) { return o[0]; }};
+        const bool had = ctx->have_theta;
+        ctx->lml_cache = false;         // (the arena is the call's own, but the contract is gpry_loo_objective's)
+        const int r = objective_batch_general(ctx, bc, thetas, B, want_grad, value, grad, info);
+        if (r <= 0) {
+            if (had && ctx->factor_valid) ctx->xs_foreign = true;       // as the single call leaves it
+            if (r < 0) (void)hipStreamSynchronize(ctx->stream);         // nothing of this call stays in flight
+            return r;
+        }                               // 1: no room for two scratch sets, one after another below
+    }
+    for (int64_t b = 0; b < B; b++) {
+        int inf = 0;
+        GPRY_TRY(gpry_loo_objective(ctx, thetas + b * w, want_grad, value + b, want_grad ? grad + b * w : nullptr, &inf));
+        if (info) info[b] = inf;
+    }
     return 0;
 }
 

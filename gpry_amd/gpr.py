@@ -773,20 +773,32 @@ class GaussianProcessRegressor(_RM, _BE):
         return val if np.isfinite(val) else -np.inf
 
     def fit_gpr_hyperparameters(self, simple=False, start_from_current=True, n_restarts=None,
-                                hyperparameter_bounds=None, objective=None):
+                                hyperparameter_bounds=None, objective=None, side_by_side=None):
         """Maximise the marginal likelihood over theta (gpry/gpr.py:883-994): same restart
         schedule, RNG order (:969-978) and optimiser (scipy L-BFGS-B with jac) as the
         reference; the objective and its gradient are evaluated on the device.
 
         ``objective``: ``"lml"``, the log marginal likelihood, or ``"loo"``, the leave-one-out log predictive density
         (``loo_log_predictive``; more robust where the kernel family is misspecified, R&W 5.4.2); ``None`` reads the
-        attribute ``fit_objective`` (default ``"lml"``).  A ``"loo"`` fit runs its restarts one after another, picks
-        the best by the leave-one-out value (``loo_value_``) and sets ``log_marginal_likelihood_value_`` to the LML at
-        the chosen theta."""
+        attribute ``fit_objective`` (default ``"lml"``).  A ``"loo"`` fit picks the best run by the leave-one-out value
+        (``loo_value_``) and sets ``log_marginal_likelihood_value_`` to the LML at the chosen theta.
+
+        ``side_by_side`` (a ``"loo"`` fit only; ``None`` reads the attribute ``fit_loo_side_by_side``, default False):
+        by default the restarts of a ``"loo"`` fit run one after another; with True they advance together, a round's
+        thetas evaluated by one ``gpry_loo_objective_batch`` -- the same optima and the same chosen theta, bit for bit,
+        on another schedule.  Where that is not possible (``fit_stats["why"]`` says so) the fit runs sequentially.  An
+        ``"lml"`` fit decides this for itself: True is refused."""
         if objective is None:
             objective = getattr(self, "fit_objective", "lml")
         if objective not in ("lml", "loo"):
             raise ValueError(f"objective: 'lml' or 'loo' (got {objective!r})")
+        if objective == "lml":
+            if side_by_side:
+                raise ValueError("side_by_side=True is the opt-in of a 'loo' fit; an 'lml' fit steps its restarts "
+                                 "together wherever it can (fit_stats['side_by_side'])")
+            loo_together = False
+        else:
+            loo_together = bool(getattr(self, "fit_loo_side_by_side", False) if side_by_side is None else side_by_side)
         if simple:
             start_from_current, n_restarts = True, 1
         if not self._fitted:
@@ -829,20 +841,22 @@ class GaussianProcessRegressor(_RM, _BE):
                     "bounds are finite. You can pass some finite bounds manually using "
                     "``hyperparameter_bounds``.")
         self._rng = check_random_state(self.random_state)
-        # (the leave-one-out objective has one evaluation per call and lives on the model's own context: no farm, no lock-step)
+        # (the leave-one-out objective lives on the model's own context unless its restarts are stepped side by side: no farm)
         ctx_devs = (fit_context_devices(getattr(self.device, "device", 0), n_restarts, getattr(self, "fit_devices", None))
                     if self.optimizer == "fmin_l_bfgs_b" and objective == "lml" else [0])
         self._side_by_side_why = ""
-        side_by_side = objective == "lml" and n_restarts > 1 and self._can_step_restarts_together()
-        if objective == "loo" and n_restarts > 1:
-            self._side_by_side_why = "the leave-one-out objective has no batched evaluation: the restarts run one after another"
+        side_by_side = ((objective == "lml" or loo_together) and n_restarts > 1
+                        and self._can_step_restarts_together(objective))
+        if objective == "loo" and n_restarts > 1 and not loo_together:
+            self._side_by_side_why = ("the restarts of a leave-one-out fit run one after another unless asked otherwise "
+                                      "(side_by_side=True / fit_loo_side_by_side)")
         if side_by_side or len(ctx_devs) > 1:
             # the optimiser never touches the RNG: drawing the start points up front gives the reference's
             # sequence (gpry/gpr.py:969-978)
             starts = [np.array(self.kernel_.theta) if (it == 0 and start_from_current) else
                       self._rng.uniform(hyperparameter_bounds[:, 0], hyperparameter_bounds[:, 1])
                       for it in range(n_restarts)]
-            optima = (self._restarts_side_by_side(starts, hyperparameter_bounds) if side_by_side
+            optima = (self._restarts_side_by_side(starts, hyperparameter_bounds, objective) if side_by_side
                       else self._concurrent_restarts(starts, hyperparameter_bounds, ctx_devs))
         else:
             # The sequential loop evaluates with single gpry_lml calls (the latency schedule).  ``GPRY_HIP_FIT_SCHEDULE=throughput``
@@ -889,19 +903,32 @@ class GaussianProcessRegressor(_RM, _BE):
         self._fitted = True
         return self
 
-    def _can_step_restarts_together(self):
+    def _can_step_restarts_together(self, objective="lml"):
         """Can ``gpry_lml_batch`` evaluate a round's thetas together?  N <= 128, d <= 16: ONE launch with a workgroup per
         run (the single-launch objective); above that and up to the device's ``lml_batch`` limit (4096): ONE chain of
-        launches whose every kernel carries all runs.  Then the optimiser runs of a fit advance side by side."""
-        if (self.optimizer != "fmin_l_bfgs_b" or getattr(self, "fit_lockstep", True) is False
-                or os.environ.get("GPRY_HIP_FIT_LOCKSTEP", "1") == "0"):
+        launches whose every kernel carries all runs.  Then the optimiser runs of a fit advance side by side.
+        ``objective="loo"`` (``gpry_loo_objective_batch``): the general chain at every size up to that limit -- the d <= 16
+        condition belongs to the single-launch LML kernel.  ``_side_by_side_why`` says which condition failed."""
+        loo = objective == "loo"
+        if self.optimizer != "fmin_l_bfgs_b":
+            if loo:
+                self._side_by_side_why = f"optimizer {self.optimizer!r}: the side-by-side form steps scipy's L-BFGS-B"
             return False
-        if not hasattr(self.device, "lml_batch"):
+        if getattr(self, "fit_lockstep", True) is False or os.environ.get("GPRY_HIP_FIT_LOCKSTEP", "1") == "0":
+            if loo:
+                self._side_by_side_why = "lock-step restarts are switched off (fit_lockstep / GPRY_HIP_FIT_LOCKSTEP)"
+            return False
+        if not hasattr(self.device, "loo_objective_batch" if loo else "lml_batch"):
+            if loo:
+                self._side_by_side_why = "the device has no loo_objective_batch"
             return False
         if self.n <= 128:
-            if self.d > 16:
+            if self.d > 16 and not loo:
                 return False
         elif self.n > int(getattr(self.device, "lml_batch_max", 128)):
+            if loo:
+                self._side_by_side_why = (f"{self.n} training points are above the batched objective's limit "
+                                          f"(lml_batch = {int(getattr(self.device, 'lml_batch_max', 128))})")
             return False
         from gpry_amd import lockstep
         if lockstep.available():
@@ -912,9 +939,9 @@ class GaussianProcessRegressor(_RM, _BE):
         self._side_by_side_why = lockstep.why()
         return False
 
-    def _restarts_side_by_side(self, starts, bounds):
+    def _restarts_side_by_side(self, starts, bounds, objective="lml"):
         try:
-            return self._restarts_side_by_side_impl(starts, bounds)
+            return self._restarts_side_by_side_impl(starts, bounds, objective)
         finally:
             # the model's own context goes back to the schedule of the single evaluations, whatever happened
             if getattr(self, "_fit_sched", "latency") == "throughput" and hasattr(self.device, "set_option"):
@@ -924,7 +951,7 @@ class GaussianProcessRegressor(_RM, _BE):
                     pass
             self._fit_sched = "latency"
 
-    def _restarts_side_by_side_impl(self, starts, bounds):
+    def _restarts_side_by_side_impl(self, starts, bounds, objective="lml"):
         """The runs of a multi-restart fit stepped together (``gpry_amd.lockstep``: scipy's own L-BFGS-B routine, one
         reverse-communication call per run and round), the objective of a round evaluated for all runs in one
         ``gpry_lml_batch``.  Every run sees the values -- to the bit -- and takes the steps it would take alone, so
@@ -934,7 +961,10 @@ class GaussianProcessRegressor(_RM, _BE):
         lock-step driver, a host thread and a device context of its own (``batch_contexts``; the contexts follow
         ``fit_context_devices``, i.e. all GPUs of a single-process run): a round costs the latency of the kernel chain
         whatever its width, and the chains of the groups run beside each other on the GPU -- the thread farm's overlap
-        with the batching inside every thread.  No group waits for another; a run never changes group."""
+        with the batching inside every thread.  No group waits for another; a run never changes group.
+
+        ``objective="loo"``: the same driver with ``gpry_loo_objective_batch`` as the objective of a round, always in the
+        latency schedule (that objective has no other)."""
         from gpry_amd import lockstep
         self._upload_train()
         dev, d = self.device, self.d
@@ -943,7 +973,8 @@ class GaussianProcessRegressor(_RM, _BE):
         k = 1
         # which schedule of the batched objective (fit_schedule): set on the model's own context here, copied to the others below
         sched, tp_groups = ("latency", None)
-        if hasattr(dev, "set_option") and 128 < self.n <= int(getattr(dev, "lml_batch_max", 128)):
+        batch_name = "loo_objective_batch" if objective == "loo" else "lml_batch"
+        if objective != "loo" and hasattr(dev, "set_option") and 128 < self.n <= int(getattr(dev, "lml_batch_max", 128)):
             sched, tp_groups = fit_schedule(self.n, n_runs)
             try:
                 dev.set_option("lml_schedule", 1 if sched == "throughput" else 0)
@@ -980,6 +1011,7 @@ class GaussianProcessRegressor(_RM, _BE):
             kern = clone(self.kernel_)              # (kernel objects are not shared between threads)
             fast = hasattr(kern, "set_theta_and_full")
             dv = devs[g]
+            batch = getattr(dv, batch_name)             # the objective of a round: (values, gradients, info) of its thetas
             # theta = [log C, log l_1 .. log l_d] (the automatic kernel): the device vector is log(exp(theta)) row by row --
             # what ``device_spec`` returns after ``kernel.theta = theta`` -- and the gradient needs no chain rule.  Going
             # through the kernel object cost 15 us per theta, more than the device's share of a round below ~300 points.
@@ -991,7 +1023,7 @@ class GaussianProcessRegressor(_RM, _BE):
                     fulls = np.empty_like(T)
                     for j in range(len(T)):
                         fulls[j] = np.log(np.exp(T[j]))       # (per row, as one evaluation does it: same bits)
-                    lml, grad_full, _ = dv.lml_batch(fulls, True)
+                    lml, grad_full, _ = batch(fulls, True)
                     counts[g] += len(T)
                     bad = ~np.isfinite(lml)
                     F, G = -lml, -grad_full[:, :T.shape[1]]
@@ -1006,7 +1038,7 @@ class GaussianProcessRegressor(_RM, _BE):
                     else:
                         kern.theta = np.asarray(th, dtype=float)
                         fulls.append(np.array(kern.device_spec(d)[1], dtype=float))
-                lml, grad_full, _ = dv.lml_batch(np.array(fulls), True)
+                lml, grad_full, _ = batch(np.array(fulls), True)
                 counts[g] += len(Thetas)
                 F, G = np.empty(len(Thetas)), np.zeros((len(Thetas), len(Thetas[0])))
                 for j, th in enumerate(Thetas):
@@ -1495,7 +1527,7 @@ class GaussianProcessRegressor(_RM, _BE):
             bounds=self.bounds, random_state=self.random_state, account_for_inf=None)
         for name in ("n_eval", "n_eval_loglike", "noise_level_", "alpha", "n_last_appended",
                      "n_last_appended_finite", "newly_appended_for_inv", "_fitted",
-                     "log_marginal_likelihood_value_", "loo_value_", "fit_objective"):
+                     "log_marginal_likelihood_value_", "loo_value_", "fit_objective", "fit_loo_side_by_side"):
             if hasattr(self, name):
                 setattr(c, name, getattr(self, name))
         for name in ("X_train", "y_train", "X_train_", "y_train_", "X_train_all", "y_train_all",

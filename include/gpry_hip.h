@@ -107,12 +107,14 @@ int gpry_ctx_sync(gpry_ctx* ctx);
  *     "lml_batch"             largest padded size at which gpry_lml_batch runs all its thetas through ONE chain of launches
  *                             (default 4096: beyond it the host's thread farm of three contexts is faster; 0 = one after another)
  *     "lml_batch_mb"          upper limit of the scratch arena of such a batch in MiB (default 49152; longer batches go in chunks)
+ *                             (both also hold for gpry_loo_objective_batch, which shares the arena)
  *     "lml_schedule" 0/1      schedule of gpry_lml_batch above 128 rows.  0 (default) latency: every theta gets the launches -- and the
  *                             bits -- of a single gpry_lml.  1 throughput: the chain for many thetas at once (whole-tile products only,
  *                             the recursive inverse at every size, the Cholesky in column blocks with one SYRK launch behind each, the
  *                             thetas dealt over "lml_streams" streams); a theta's result does not depend on how many thetas share the
  *                             call (B = 1 included) and differs from the latency schedule's by rounding.  The host mirror sets it for
- *                             the multi-restart fits (gpry/gpr.py:968-984)
+ *                             the multi-restart fits (gpry/gpr.py:968-984).  Concerns gpry_lml_batch alone: gpry_loo_objective_batch
+ *                             always runs the latency schedule
  *     "lml_streams" 1..8      throughput schedule: stream groups per call (default 2)
  *     "tp_block", "tp_tail"   throughput schedule: width of the column blocks of the Cholesky (default 512) and size of the last
  *                             block, factored with riding tiles only (default 1024); multiples of 128.  No bit depends on them
@@ -625,6 +627,19 @@ int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* 
  * (training set, theta, kernel id) alone, and the value's not on want_grad.  Stage timers: those of the factor chain,
  * "solve_alpha", "loo_q", "lauum", "loo_mirror", "loo_gram", "loo_traces". */
 int gpry_loo_objective(gpry_ctx* ctx, const double* theta, int want_grad, double* value, double* grad, int* info);
+/* B evaluations of gpry_loo_objective in one call: the optimiser runs of a multi-restart "loo" fit stepped side by side
+ * (gpry/gpr.py:968-984 runs the restarts one after another; gpry_amd/lockstep.py), the twin of gpry_lml_batch and with its
+ * arguments: thetas is B rows of 1 + d (2 + d with GPRY_KERNEL_WHITE) entries, value B, grad B rows, info (nullable) B.
+ * From 128 padded rows up to option "lml_batch": ONE chain of launches for the thetas of a chunk (grid.z; at most 96, and
+ * what option "lml_batch_mb" and 70 % of the free device memory hold of scratch sets), always in the latency schedule --
+ * option "lml_schedule" concerns gpry_lml_batch alone.  Above "lml_batch", with "chol" != 0 or where fewer than two scratch
+ * sets fit: one gpry_loo_objective after another.  Per theta, value, gradient and info are bit for bit those of
+ * gpry_loo_objective on the same model, whatever B, the position in the batch, the chunking and the neighbours; a theta
+ * whose matrix is not positive definite gives -inf, a zero gradient row and info > 0 and leaves the other rows alone.
+ * Refused with an error: NULL pointers, B <= 0, a theta entry that is not finite.  State contract: gpry_loo_objective's.
+ * Stage timer "loo_batch" around a chunk, beside the per-stage ones. */
+int gpry_loo_objective_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad, double* value, double* grad,
+                             int* info);
 int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, int64_t ngroups, double* mean, double* cov,
                    double* chi2, double* logpdf, int* info, double* device_ms);
 
@@ -888,7 +903,10 @@ int gpry_group_lml_batch(gpry_group* group, const double* thetas, int n_theta, i
  * *count = launches accumulated since gpry_timing_reset.  "lml_batch_shrinks" is a counter, not a timer: *count = the times a
  * batched objective of this context halved its chunk after an out-of-memory answer (any other failure is returned to the caller).
  * "capacity_rows" / "capacity_cols" are sizes, not timers: *count = the training rows / padded columns the context's buffers hold
- * (they grow with the largest model the context has seen and never shrink). */
+ * (they grow with the largest model the context has seen and never shrink).  "batch_set_doubles" / "batch_chunk": the last
+ * batched objective of this context (gpry_lml_batch, gpry_loo_objective_batch) that ran as one chain -- *count = the doubles of
+ * one theta's scratch set in its arena / the thetas one chain carried at the most (option "lml_batch_mb" holds
+ * floor(mb * 2^20 / (8 * batch_set_doubles)) sets). */
 int gpry_timing_reset(gpry_ctx* ctx);
 int gpry_timing_get(gpry_ctx* ctx, const char* name, double* total_ms, int64_t* count);
 /* Raw micro-benchmarks used by bench.py to quote measured peaks beside the spec:
