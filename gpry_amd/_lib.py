@@ -63,6 +63,7 @@ SIGNATURES = {
     "gpry_lml_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "gpry_loo_objective": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_double), _vp, _P(C.c_int)]),
     "gpry_loo_objective_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "gpry_lml_hessian": (C.c_int, [_vp, _vp, _P(C.c_double), _vp, _vp, _P(C.c_int), _P(C.c_double)]),
     "gpry_predict": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "gpry_debug_serve_stats": (C.c_int, [_vp, _P(C.c_int64), _P(C.c_int64)]),
     "gpry_ns_prior": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int64, _vp, _vp, _P(C.c_double)]),
@@ -417,6 +418,22 @@ class Device:
         if eval_gradient:
             return val.value, grad, info.value
         return val.value, info.value
+
+    def lml_hessian(self, theta):
+        """Log marginal likelihood, its gradient and its Hessian in theta at ``theta`` (gpry_lml_hessian), transformed
+        units: a dict ``lml``, ``grad`` (n_theta,), ``H`` (n_theta, n_theta; symmetric to the last bit), ``info``,
+        ``device_ms``.  ``lml`` and ``grad`` have the bits of ``lml(theta, True)``; ``(-inf, zeros, zeros, info > 0)``
+        where the matrix is not positive definite.  Models of more than 4096 padded rows are refused.  The factor held
+        for prediction is not disturbed."""
+        theta = _f64(np.asarray(theta, dtype=np.float64).ravel())
+        if theta.shape[0] != self.n_theta:
+            raise ValueError(f"expected {self.n_theta} entries, got {theta.shape[0]}")
+        grad = np.zeros(self.n_theta)
+        H = np.zeros((self.n_theta, self.n_theta))
+        val, info, ms = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
+        self._check(self._lib.gpry_lml_hessian(self._h, _ptr(theta), C.byref(val), _ptr(grad), _ptr(H), C.byref(info),
+                                               C.byref(ms)), "gpry_lml_hessian")
+        return {"lml": val.value, "grad": grad, "H": H, "info": info.value, "device_ms": ms.value}
 
     def loo_objective_batch(self, thetas, eval_gradient=True):
         """``loo_objective`` for every row of ``thetas`` in one call (gpry_loo_objective_batch): ``(value (B,), grad (B,

@@ -100,9 +100,9 @@ int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* info_host)
 // evaluation (gpry_ctx::bn), at the bn thetas whose [C, l...] rows sit in the arena: covariance build, factor, V = L^-1,
 // alpha, log-det and quadratic form, and with want_grad K^-1 = V^T V and the traces.  The last kernel writes results and
 // factorisation status into `dres` (device view of pinned host memory; theta tb at row tb of GPRY_BRES_STRIDE doubles).
-constexpr int RES_INFO = 2 + GPRY_THETA_MAX;      // [logdet/2, quad, grad (1 + d, + 1 with a white term) ..., info0, info1]
+constexpr int RES_INFO = LML_RES_INFO;            // [logdet/2, quad, grad (1 + d, + 1 with a white term) ..., info0, info1]
 static_assert(RES_INFO + 3 <= GPRY_BRES_STRIDE, "result row too short");
-static int lml_chain(gpry_ctx* ctx, int want_grad, double* dres) {
+int lml_chain(gpry_ctx* ctx, int want_grad, double* dres) {
     GPRY_TRY(build_factor(ctx, ctx->dW, ctx->dW2, ctx->dW3, nullptr));
     double* dz = ctx->dvec;                 // z = V y
     double* da = ctx->dvec + ctx->Np;       // alpha

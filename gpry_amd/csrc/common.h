@@ -261,6 +261,8 @@ struct gpry_ctx {
     uint8_t* dloo = nullptr;           // gpry_loo / gpry_leave_out: partial sums of the pass over V, partial Grams, outputs (bytes)
     int64_t loo_cap = 0;
     void* hloo = nullptr; int64_t hloo_cap = 0;    // gpry_loo: pinned landing place of its five output rows (bytes)
+    double* dhess = nullptr;           // gpry_lml_hessian: full-square K^-1, the d matrices K_i and K^-1 K_i, partial sums (doubles)
+    int64_t hess_cap = 0;
     uint8_t* dsvm = nullptr;           // gpry_svm_fit: coordinate-major training set, alpha, gradient, labels, status block (bytes)
     int64_t svm_cap = 0;
     void* hsvm = nullptr; int64_t hsvm_cap = 0;    // gpry_svm_fit: pinned image of its upload (bytes)
@@ -505,6 +507,11 @@ int serve_predict_mean(gpry_ctx* ctx, const double* X, int64_t M, double* part, 
 // ---- api.hip: the factor chain of one objective evaluation, shared with loo_fit.hip ------
 // A <- chol(K + diag(alpha)), V <- A^-1 at the theta the context holds (T: scratch); info_host NULL: the caller reads dinfo itself
 int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* info_host);
+// the launches of one gpry_lml evaluation at the theta the context holds, shared with lml_hessian.hip: leaves L in dW, V in
+// dW2, alpha at dvec + Np, [logdet/2, quad, grad ...] at dvec + 2 Np and, with want_grad, K^-1 (lower) in dW3; results and
+// the status words (from LML_RES_INFO) go to `dres` (mapped host memory)
+constexpr int LML_RES_INFO = 2 + GPRY_THETA_MAX;
+int lml_chain(gpry_ctx* ctx, int want_grad, double* dres);
 bool panel_timed_out(int marker);                       // fourth status word: a bounded wait of a panel step ran out
 int panel_timeout_error(gpry_ctx* ctx, int marker);
 // loo.hip: gpry_loo's pass over an inverse factor V (partial sums per 64 x 64 tile; ceil(N / 64) x Np doubles each)

@@ -162,6 +162,12 @@ int ensure_capacity(gpry_ctx* ctx, int64_t N, int d) {
         (void)hipFree(ctx->barena);
         ctx->barena = nullptr; ctx->barena_cap = 0;
     }
+    // the scratch of gpry_lml_hessian, (1 + 2 d) Np^2 doubles, by the same rule
+    if (ctx->dhess && 2 * (1 + 2 * (int64_t)d) * Np * Np < ctx->hess_cap) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(ctx->dhess);
+        ctx->dhess = nullptr; ctx->hess_cap = 0;
+    }
     ctx->N = N; ctx->Np = Np; ctx->d = d; ctx->dpad = dpad;
     return 0;
 }
@@ -248,7 +254,7 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
                     ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc, ctx->dknn,
-                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm};
+                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm, ctx->dhess};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hloo) (void)hipHostFree(ctx->hloo);

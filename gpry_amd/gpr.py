@@ -772,6 +772,40 @@ class GaussianProcessRegressor(_RM, _BE):
         val, _ = dev.loo_objective(theta_full, False)
         return val if np.isfinite(val) else -np.inf
 
+    def _lml_hessian_full(self, theta=None):
+        """``(kernel, theta_full, result)``: the device call of ``lml_hessian`` in the device's own vector
+        ``[log C, log l_1 .. l_d (, log w)]``; theta in the kernel's entries, None: ``kernel_.theta``."""
+        self.n_eval_loglike += 1
+        kernel = self.kernel_ if self.kernel_ is not None else clone(self.kernel)
+        if theta is not None:
+            kernel = kernel.clone_with_theta(np.asarray(theta, dtype=float))
+        kid, theta_full = kernel.device_spec(self.d)
+        if not self._dev_train_ok:
+            self._upload_train()
+        dev = self._dev if self._dev is not None else self.device
+        if dev.N != len(self.y_train_):
+            raise RuntimeError("device training set out of sync")
+        return kernel, np.asarray(theta_full, dtype=float), dev.lml_hessian(theta_full)
+
+    def lml_hessian(self, theta=None):
+        """``(lml, grad, H)``: the log marginal likelihood, its gradient and its Hessian in theta, transformed units, on
+        the device (``gpry_lml_hessian``, closed form): the twin of ``log_marginal_likelihood`` and
+        ``loo_log_predictive`` -- same kernel handling, same mapping of theta and gradient (fixed and isotropic entries, a
+        ``WhiteKernel`` in either operand order; H is mapped by the same chain rule on both sides), ``(-inf, zeros,
+        zeros)`` where the matrix is not positive definite.  ``theta=None``: at the fitted ``kernel_.theta``.  Counted in
+        ``n_eval_loglike`` as one evaluation.  Models of more than 4096 padded rows are refused by the device."""
+        kernel, theta_full, out = self._lml_hessian_full(theta)
+        p = len(theta_full)
+        # grad_from_full is linear: its matrix, column by column
+        M = np.stack([kernel.grad_from_full(e, self.d) for e in np.eye(p)], axis=1)
+        n = M.shape[0]
+        if not np.isfinite(out["lml"]):
+            return -np.inf, np.zeros(n), np.zeros((n, n))
+        if n == p and np.array_equal(M, np.eye(p)):         # theta is the device's own vector: nothing to map
+            return out["lml"], out["grad"], out["H"]
+        H = M.dot(out["H"]).dot(M.T)
+        return out["lml"], M.dot(out["grad"]), 0.5 * (H + H.T)
+
     def fit_gpr_hyperparameters(self, simple=False, start_from_current=True, n_restarts=None,
                                 hyperparameter_bounds=None, objective=None, side_by_side=None):
         """Maximise the marginal likelihood over theta (gpry/gpr.py:883-994): same restart

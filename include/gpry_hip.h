@@ -643,6 +643,37 @@ int gpry_loo_objective_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int
 int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, int64_t ngroups, double* mean, double* cov,
                    double* chi2, double* logpdf, int* info, double* device_ms);
 
+/* ---- The Hessian of the log marginal likelihood in theta (lml_hessian.hip; gpry_amd/gpr.py: lml_hessian,
+ * gpry_amd/hyper.py: hyper_laplace).  theta = [log C, log l_1 .. log l_d], log w last with GPRY_KERNEL_WHITE, p entries;
+ * K = C k(r^2) + diag(alpha + w), r^2 = sum_k D_k, D_k(a,b) = ((x_ak - x_bk) / l_k)^2, alpha_ = K^-1 y_,
+ * W = alpha_ alpha_^T - K^-1, K_i = dK / dtheta_i, K_ij = d2K / dtheta_i dtheta_j, transformed units like gpry_lml:
+ *   H_ij = 1/2 tr(W K_ij) - (K_i alpha_)^T K^-1 (K_j alpha_) + 1/2 tr(K^-1 K_i K^-1 K_j)
+ *   K_0 = C k (no noise on the diagonal), K_i = C h D_i (d k / d log l_i = h D_i), K_w = w I;
+ *   K_00 = K_0, K_0i = K_i, K_ww = w I; EVERY cross entry with log w is zero, (log C, log w) included;
+ *   K_ij = C (g D_i D_j - 2 delta_ij h D_i) for two length scales, g = -2 dh / dr^2: RBF g = k; Matern-1/2
+ *   g = e^-r (1 + r) / r^3; Matern-3/2 g = 9 e^-t / t, t = sqrt(3) r; Matern-5/2 g = 25/3 e^-t, t = sqrt(5) r.
+ * At r = 0 (the diagonal, duplicated rows) D_i D_j = 0: the second-derivative entry is defined as 0 there for every
+ * kernel, as h is for Matern-1/2.
+ * lml, grad (p): bit for bit gpry_lml(theta, want_grad = 1) on the same context.  hess: p x p row-major, symmetric to the
+ * last bit.  (Where gpry_lml answers from its single launch -- N <= 128, d <= 16, option "lml_small" -- lml and grad come
+ * from that launch and hess from the chain at 128 padded rows, whose own gradient agrees with it to rounding: there
+ * "row 0 of hess is grad" holds to rounding, not to the bit.)  Not positive definite: returns 0 with *lml = -inf, grad and hess all zero, *info > 0 (gpry_lml's
+ * convention); a panel time-out is an error.  Refused with -1 and a message: NULL arguments (device_ms may be NULL), a
+ * theta entry that is not finite, no training set, d > 32, and a model of more than 4096 padded rows (the limit of
+ * gpry_predict_cov and gpry_maximize_acq; refused before anything is launched, the context answers the next call as
+ * before).  Cost: the d products K^-1 K_i, 2 N^3 each, in one batched launch of the GEMM engine, and O(p^2 N^2) besides;
+ * scratch of its own: (1 + 2 d) Np^2 doubles (8.7 GB at 4096 rows, d = 32), allocated on first use, released with the
+ * context, given back when gpry_set_train brings a model of less than half that footprint.  Models below 128 rows take
+ * the chain at 128 padded rows.
+ * State contract: evaluates at the theta passed in; the context's theta, the factor held for prediction, a
+ * Kriging-believer session, the resident pool and the buffers of gpry_loo are not touched; the factor cache of gpry_lml
+ * (option "lml_cache") is cleared, whose scratch it overwrites.  A result's bits depend on (training set, theta, kernel
+ * id) alone: not on earlier calls, not on which context of a device evaluates it.  Stage timers: those of gpry_lml with
+ * gradient, then "hess_pairs", "hess_products", "hess_btraces", "hess_middle", "hess_finish".  device_ms (nullable):
+ * device time of the call. */
+int gpry_lml_hessian(gpry_ctx* ctx, const double* theta, double* lml, double* grad, double* hess, int* info,
+                     double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
