@@ -89,37 +89,57 @@ def loo_terms(X_, y_, alpha, theta, kid, white=False):
     return Kinv.dot(y_), np.diag(Kinv).copy()
 
 
-def value_extended(X_, y_, alpha, theta, kid, white=False):
-    """The value alone in numpy's extended precision (kernel matrix, Cholesky, V = L^-1 all in ``np.longdouble``), for
-    the central differences: a float64 value carries a rounding error of about 1e-16 cond(K) of its size, which a step
-    of 1e-6 turns into 1e-10 cond(K) of the gradient -- above 1e-5 on the models without a white term (cond 5e5 .. 1e6)."""
+def sqdist_extended(A, B, ls):
+    """Squared distances of the rows of ``A`` and ``B`` scaled by the length scales ``ls``, all ``np.longdouble``."""
+    As, Bs = A / ls, B / ls
+    r2 = np.zeros((len(A), len(B)), dtype=np.longdouble)
+    for k in range(A.shape[1]):
+        df = As[:, None, k] - Bs[None, :, k]
+        r2 += df * df
+    return r2
+
+
+def corr_extended(r2, kid):
+    """The correlation from the scaled squared distance in ``np.longdouble``."""
+    ld = np.longdouble
+    if kid == orc.RBF:
+        return np.exp(-r2 / 2)
+    t = np.sqrt(r2) * np.sqrt(ld(2 * orc._NU[kid]))
+    poly = {orc.MATERN12: 1, orc.MATERN32: 1 + t, orc.MATERN52: 1 + t + t * t / 3}[kid]
+    return poly * np.exp(-t)
+
+
+def factor_extended(X_, alpha, theta, kid, white=False):
+    """(K, L, V = L^-1) of the training matrix in numpy's extended precision: the kernel matrix, the Cholesky factor column
+    by column and its inverse row by row, all in ``np.longdouble``.  ``None`` where a pivot is not positive."""
     ld = np.longdouble
     X = np.asarray(X_, dtype=ld)
     theta = np.asarray(theta, dtype=ld)
     N, d = X.shape
-    Xs = X / np.exp(theta[1:d + 1])
-    r2 = np.zeros((N, N), dtype=ld)
-    for k in range(d):
-        df = Xs[:, None, k] - Xs[None, :, k]
-        r2 += df * df
-    if kid == orc.RBF:
-        k_ = np.exp(-r2 / 2)
-    else:
-        t = np.sqrt(r2) * np.sqrt(ld(2 * orc._NU[kid]))
-        poly = {orc.MATERN12: 1, orc.MATERN32: 1 + t, orc.MATERN52: 1 + t + t * t / 3}[kid]
-        k_ = poly * np.exp(-t)
-    K = np.exp(theta[0]) * k_
+    K = np.exp(theta[0]) * corr_extended(sqdist_extended(X, X, np.exp(theta[1:d + 1])), kid)
     K[np.diag_indices(N)] = np.exp(theta[0]) + np.asarray(np.broadcast_to(alpha, (N,)), dtype=ld) \
         + (np.exp(theta[d + 1]) if white else ld(0))
     L = np.zeros((N, N), dtype=ld)
     for j in range(N):                              # Cholesky, column by column
         s = K[j, j] - L[j, :j].dot(L[j, :j])
+        if not s > 0:
+            return None
         L[j, j] = np.sqrt(s)
         L[j + 1:, j] = (K[j + 1:, j] - L[j + 1:, :j].dot(L[j, :j])) / L[j, j]
     V = np.zeros((N, N), dtype=ld)
     for i in range(N):                              # V = L^-1, row by row
         V[i, :i] = -L[i, :i].dot(V[:i, :i]) / L[i, i]
         V[i, i] = 1 / L[i, i]
+    return K, L, V
+
+
+def value_extended(X_, y_, alpha, theta, kid, white=False):
+    """The value alone in numpy's extended precision (``factor_extended``), for the central differences: a float64 value
+    carries a rounding error of about 1e-16 cond(K) of its size, which a step of 1e-6 turns into 1e-10 cond(K) of the
+    gradient -- above 1e-5 on the models without a white term (cond 5e5 .. 1e6)."""
+    ld = np.longdouble
+    K, L, V = factor_extended(X_, alpha, theta, kid, white)
+    N = len(V)
     al = V.T.dot(V.dot(np.asarray(y_, dtype=ld)))
     q = np.einsum("ki,ki->i", V, V)
     return np.sum(np.log(q) / 2 - al * al / q / 2) - ld(N) / 2 * np.log(2 * ld(np.pi))
