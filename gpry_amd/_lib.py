@@ -93,6 +93,7 @@ SIGNATURES = {
     "gpry_maximize_acq": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int,
                                     C.c_int, C.c_double, C.c_double, C.c_double] + [_vp] * 14 + [_P(C.c_double)]),
     "gpry_hessian_mean": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_mean_theta_grad": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_cov": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_sample_joint": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp, _vp,
                                     _P(C.c_int), _P(C.c_double), _P(C.c_double)]),
@@ -765,6 +766,23 @@ class Device:
         ms = C.c_double(0.0)
         self._check(self._lib.gpry_hessian_mean(self._h, _ptr(X), n, _ptr(out["y"]), _ptr(out["g"]), _ptr(out["H"]),
                                                 C.byref(ms)), "gpry_hessian_mean")
+        out["device_ms"] = ms.value
+        return out
+
+    # -- the derivative of the mean in theta (gpry_amd/gpr.py: mean_theta_grad; gpry_amd/hyper.py: hyper_spread) ----
+    def mean_theta_grad(self, X):
+        """The posterior mean and its derivative in theta = [log C, log l_1 .. log l_d (, log w)] at the rows of ``X``
+        (npts, d), raw coordinates (gpry_mean_theta_grad): a dict with ``y`` (npts,; ``predict(x[None])`` bit for bit, a
+        gated point is -inf), ``G`` (npts, p; of the unclipped, ungated mean, units of y per unit of log theta) and
+        ``device_ms``.  Any number of points; all four kernels."""
+        X = _f64(X)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError(f"expected points of shape (npts, {self.d}), got {X.shape}")
+        n = X.shape[0]
+        out = dict(y=np.empty(n), G=np.empty((n, self.n_theta)))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_mean_theta_grad(self._h, _ptr(X), n, _ptr(out["y"]), _ptr(out["G"]), C.byref(ms)),
+                    "gpry_mean_theta_grad")
         out["device_ms"] = ms.value
         return out
 

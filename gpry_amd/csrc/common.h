@@ -263,6 +263,8 @@ struct gpry_ctx {
     void* hloo = nullptr; int64_t hloo_cap = 0;    // gpry_loo: pinned landing place of its five output rows (bytes)
     double* dhess = nullptr;           // gpry_lml_hessian: full-square K^-1, the d matrices K_i and K^-1 K_i, partial sums (doubles)
     int64_t hess_cap = 0;
+    double* dtg = nullptr;             // gpry_mean_theta_grad: the right-hand sides U, T = V U and W = K^-1 U of one call (doubles)
+    int64_t tg_cap = 0;
     uint8_t* dsvm = nullptr;           // gpry_svm_fit: coordinate-major training set, alpha, gradient, labels, status block (bytes)
     int64_t svm_cap = 0;
     void* hsvm = nullptr; int64_t hsvm_cap = 0;    // gpry_svm_fit: pinned image of its upload (bytes)

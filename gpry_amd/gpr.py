@@ -806,6 +806,37 @@ class GaussianProcessRegressor(_RM, _BE):
         H = M.dot(out["H"]).dot(M.T)
         return out["lml"], M.dot(out["grad"]), 0.5 * (H + H.T)
 
+    def _mean_theta_grad_full(self, X, validate=True):
+        """The device call of ``mean_theta_grad`` in the device's own vector: its dict (``y``, ``G``, ``device_ms``)."""
+        from gpry_amd.mc import _push_model
+        X = np.ascontiguousarray(self._validate_X(np.atleast_2d(X), validate), dtype=float)
+        if X.ndim != 2 or X.shape[1] != self.d or len(X) == 0:
+            raise ValueError(f"mean_theta_grad: rows of dimension {self.d} are needed, got shape {X.shape}")
+        if self.X_train_ is None:
+            raise ValueError("mean_theta_grad needs a model with training data")
+        _push_model(self, "mean_theta_grad")
+        out = self.device.mean_theta_grad(X)
+        self.n_eval += len(X)
+        return out
+
+    def mean_theta_grad(self, X, validate=True, full=False):
+        """``(mean, G)``: the posterior mean at the rows of ``X`` (npts, d) and its derivative in the hyper-parameters at
+        the fitted theta, on the device (``gpry_mean_theta_grad``, closed form, no refactorisation), in units of y per
+        unit of log theta.  mean (npts,) is ``predict(x[None])`` bit for bit (clip and gates included, a gated point is
+        -inf); G is of the unclipped, ungated mean and finite for a gated point too.  ``full=False``: one column per entry
+        of ``kernel_.theta`` -- ``lml_hessian``'s mapping applied to each row (an isotropic length scale sums its tied
+        columns, fixed entries drop out, a ``WhiteKernel`` in either operand order); ``full=True``: the device's own
+        vector ``[log C, log l_1 .. l_d (, log w)]``.  All four kernels; any number of points.  ``n_eval`` grows by npts."""
+        out = self._mean_theta_grad_full(X, validate)
+        G = out["G"]
+        if full:
+            return out["y"], G
+        p = G.shape[1]
+        M = np.stack([self.kernel_.grad_from_full(e, self.d) for e in np.eye(p)], axis=1)
+        if M.shape[0] == p and np.array_equal(M, np.eye(p)):
+            return out["y"], G
+        return out["y"], G.dot(M.T)
+
     def fit_gpr_hyperparameters(self, simple=False, start_from_current=True, n_restarts=None,
                                 hyperparameter_bounds=None, objective=None, side_by_side=None):
         """Maximise the marginal likelihood over theta (gpry/gpr.py:883-994): same restart

@@ -5,6 +5,7 @@
 correlated, which are held by a bound, and the Laplace evidence of the kernel family.  A report: it warns of nothing,
 gates nothing and changes no fit.
 """
+import warnings
 from collections import namedtuple
 from time import time
 
@@ -92,3 +93,110 @@ def hyper_laplace(gpr, theta=None):
     return HyperLaplace(theta=th, names=names, lml=float(out["lml"]), grad=g, H=H, bounds=bounds, free=free, negdef=negdef,
                         cov=cov, sigma_log=sigma, corr=corr, eigvals=eigvals, eigvecs=eigvecs, log_evidence=float(log_evidence),
                         device_s=out["device_ms"] / 1e3, wall_s=time() - t_start)
+
+
+class HyperSpread:
+    """What ``hyper_spread`` returns.  Per draw s (arrays of length ``n_draws``): ``dtheta`` (n_draws, p; the draw in the
+    device's vector, zero in the held entries), ``dlogZ`` (the change of log Z), ``means`` (n_draws, d), ``covs``
+    (n_draws, d, d) and ``ess`` (Kish) of the sample reweighted under draw s.  Summaries, those of ``SurrogateSpread``:
+    ``mean0`` / ``cov0`` (the sample's own mean and covariance), ``logZ_std``, ``mean_shift_sigma`` (d,; the std over draws
+    of the mean in units of the baseline posterior sigma), ``cov_ratio_std`` (d,; the std over draws of var_s / var_0 per
+    parameter), ``ess_min``.  ``sigma_theta`` (n_points,): sqrt(G cov G^T) per kept row, the part of the mean's error bar
+    that comes from theta (times ``scale``).  ``max_abs_logr``: the largest |log r_si|, the reach of the linearisation --
+    beyond about 1 the first order is only indicative.  ``keep`` (the indices of the rows that take part), ``n_points``,
+    ``device_ms``, ``seed``, ``scale``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return (f"HyperSpread(n_points={self.n_points}, n_draws={len(self.dlogZ)}, logZ_std={self.logZ_std:.3g}, "
+                f"mean_shift_sigma={np.array2string(np.asarray(self.mean_shift_sigma), precision=3)}, "
+                f"ess_min={self.ess_min:.1f}, max_abs_logr={self.max_abs_logr:.3g})")
+
+
+def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=1.0):
+    """How far the posterior moves because theta is only known as well as the data pin it: the Monte Carlo sample
+    ``(X, y, w)`` that ``mc_sample_from_gp`` returned, reweighted to first order under ``n_draws`` draws
+    dtheta_s ~ N(0, scale^2 cov) of the hyper-parameters, cov the Laplace covariance of ``hyper_laplace`` (``laplace``: a
+    ``HyperLaplace``; None: ``hyper_laplace(gpr)``).  The twin of ``surrogate_spread``, which takes theta as given.
+
+    With G = d mean / d theta at the rows (``gpr.mean_theta_grad(X, full=True)``, one device call, any number of rows):
+    log r_si = G(x_i) . dtheta_s, dlogZ_s = log sum_i w_i r_si, and mean, covariance and Kish effective sample size of the
+    weights w_i r_si.  The rows are those of positive finite weight and finite y; rows the gates reject take no part.
+    Entries of theta that are not ``free`` are held: their draws are zero.  The draws come from
+    ``np.random.default_rng(seed)`` through the Cholesky factor of cov (None: fresh entropy).
+
+    Raises a ValueError when ``laplace.negdef`` is false (there is no covariance to draw from) or no entry is free.
+    Warns when the smallest effective sample size is below 5 % of the rows.  Host memory is O(n_draws M + M d^2).
+    Returns a ``HyperSpread``."""
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    y = np.asarray(y, dtype=float)
+    n, d = X.shape
+    w = np.full(n, 1.0 / max(n, 1)) if w is None else np.asarray(w, dtype=float)
+    if y.shape != (n,) or w.shape != (n,):
+        raise ValueError(f"expected y and w of shape ({n},), got {y.shape} and {w.shape}")
+    n_draws, scale = int(n_draws), float(scale)
+    if n_draws < 2:
+        raise ValueError(f"n_draws must be at least 2 (got {n_draws})")
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError(f"scale must be positive and finite (got {scale})")
+    if seed is None:
+        seed = int(np.random.default_rng().integers(2**63 - 1))
+    seed = int(seed)
+    lap = hyper_laplace(gpr) if laplace is None else laplace
+    if not lap.negdef or lap.cov is None:
+        raise ValueError("hyper_spread: negdef is False -- minus the Hessian of the log marginal likelihood over the free "
+                         "entries is not positive definite, there is no covariance of theta to draw from")
+    free = np.asarray(lap.free, dtype=bool)
+    k = int(free.sum())
+    if k == 0:
+        raise ValueError("hyper_spread: no entry of theta is free (all are fixed or held by a bound): nothing to draw")
+    keep = np.flatnonzero((w > 0) & np.isfinite(w) & np.isfinite(y))
+    if len(keep) == 0:
+        raise ValueError("the sample has no row of positive weight and finite y")
+    wk = w[keep] / w[keep].sum()
+    Xk = np.ascontiguousarray(X[keep])
+    m = len(keep)
+    res = gpr._mean_theta_grad_full(Xk)
+    G = np.asarray(res["G"], dtype=float)
+    p = len(free)
+    if G.shape != (m, p):
+        raise ValueError(f"hyper_spread: the Laplace report has {p} entries of theta, the model {G.shape[1]}")
+    cov = np.asarray(lap.cov, dtype=float)
+    dtheta = np.zeros((n_draws, p))
+    dtheta[:, free] = scale * np.random.default_rng(seed).standard_normal((n_draws, k)).dot(np.linalg.cholesky(cov).T)
+    Gf = G[:, free]
+    sigma_theta = np.sqrt(np.maximum(np.einsum("if,fg,ig->i", Gf, cov, Gf), 0.0)) * scale
+    logr = dtheta.dot(G.T)                              # (n_draws, m)
+    alive = np.isfinite(res["y"])                       # rows the gates reject take no part
+    if not alive.any():
+        raise ValueError("every row of the sample is rejected by the classifier or the trust region")
+    max_abs_logr = float(np.max(np.abs(logr[:, alive])))
+    logr[:, ~alive] = -np.inf
+    top = logr.max(axis=1)
+    e = wk[None, :] * np.exp(logr - top[:, None])
+    tot = e.sum(axis=1)
+    dlogZ = top + np.log(tot)
+    ws = e / tot[:, None]
+    ess = 1.0 / np.sum(ws * ws, axis=1)
+    means = ws.dot(Xk)
+    covs = np.empty((n_draws, d, d))
+    for s in range(n_draws):                            # weighted Grams, one draw at a time: O(M d) beside ws
+        cen = Xk - means[s]
+        covs[s] = (cen * ws[s][:, None]).T.dot(cen)
+    mean0 = wk.dot(Xk)
+    cen0 = Xk - mean0
+    cov0 = (cen0 * wk[:, None]).T.dot(cen0)
+    var0 = np.diag(cov0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean_shift_sigma = means.std(axis=0) / np.sqrt(var0)
+        cov_ratio_std = (np.einsum("saa->sa", covs) / var0).std(axis=0)
+    out = HyperSpread(dtheta=dtheta, dlogZ=dlogZ, means=means, covs=covs, ess=ess, mean0=mean0, cov0=cov0,
+                      logZ_std=float(dlogZ.std()), mean_shift_sigma=mean_shift_sigma, cov_ratio_std=cov_ratio_std,
+                      ess_min=float(ess.min()), sigma_theta=sigma_theta, max_abs_logr=max_abs_logr, keep=keep, n_points=m,
+                      device_ms=res["device_ms"], seed=seed, scale=scale)
+    if out.ess_min < 0.05 * m:
+        warnings.warn(f"hyper_spread: the smallest effective sample size over the draws is {out.ess_min:.1f} of {m} "
+                      "rows (< 5 %): the hyper-parameters are too uncertain for the reweighted sample to mean anything")
+    return out

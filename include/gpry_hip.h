@@ -674,6 +674,37 @@ int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, in
 int gpry_lml_hessian(gpry_ctx* ctx, const double* theta, double* lml, double* grad, double* hess, int* info,
                      double* device_ms);
 
+/* ---- The derivative of the posterior mean in theta at a batch of points (theta_grad.hip; gpry_amd/gpr.py:
+ * mean_theta_grad, gpry_amd/hyper.py: hyper_spread).  theta = [log C, log l_1 .. log l_d], log w last with
+ * GPRY_KERNEL_WHITE, p entries, at the theta of the factor the context holds; K = C phi(r) + diag(alpha + w),
+ * alpha_ = K^-1 y_.  With diff_ia = x_a / l_a - X_ia / l_a, r_i = |diff_i|, k_i = C phi(r_i) and h(r) = -phi'(r) / r (minus
+ * the radial factor of the x-gradient: exp(-r^2/2) RBF, exp(-r) / r Matern 1/2, 3 exp(-sqrt3 r) Matern 3/2,
+ * (5/3) (1 + sqrt5 r) exp(-sqrt5 r) Matern 5/2), so that d k_i / d log l_a = C h(r_i) diff_ia^2 (Matern 1/2: 0 at r = 0, the
+ * limit of h diff^2):
+ *   U_0 = (alpha + w) o alpha_,   U_a = (dK / dlog l_a) alpha_,   U_w = w alpha_,   W = K^-1 U = V^T (V U)   (N x p)
+ *   G_0(x) = y_std sum_i k_i W_i0,   G_a(x) = y_std sum_i (C alpha_i h(r_i) diff_ia^2 - k_i W_ia),   G_w(x) = -y_std sum_i k_i W_iw.
+ * The log C entry is formed as k*^T K^-1 (D alpha_) as written, never as a difference of two O(1) numbers.  No
+ * factorisation: W costs one N x N pass over the training rows and two triangular products with p right-hand sides, every
+ * point after that one pass over the training rows.  A Matern-1/2 model is served: the derivative in theta exists at the
+ * training rows too.
+ * X (npts x d, raw coordinates where the affine map has an x-affine, as for gpry_hessian_mean); npts is unbounded (chunks of
+ * 65536 points).  Outputs:
+ *   y_out (npts, nullable)        gpry_predict of the point, bit for bit, clip and gates included (a gated point is -inf);
+ *   G_out (npts x p, row-major)   the derivative of the UNCLIPPED, UNGATED mean, in units of y per unit of log theta;
+ *                                 finite for a gated point too.
+ * The bits of y and G depend on the model and the point alone: not on npts, the point's position in the batch, how a
+ * batch is split over calls, or the context.  W is recomputed by every call (fixed summation orders: its bits depend on
+ * the model alone); nothing is cached across calls.
+ * Refused (-1, with gpry_last_error) before anything runs: a NULL X or G_out; npts < 1; no valid factor; d > 32; a
+ * coordinate that is not finite.  After a refusal the context answers the next call as before.
+ * State contract: works on a factor grown by gpry_append_rows; stops the resident predict kernel first; reads V, alpha_,
+ * the scaled training rows, y_ and the noise vector only; writes a scratch of its own (2 Np 40 doubles, released with the
+ * context) and the samplers' staging buffer.  The state of gpry_predict, a sweep, a Kriging-believer session, the
+ * samplers, the buffers of gpry_loo and the factor cache of gpry_lml are not touched.  Stage timers: "theta_grad_setup"
+ * (U, T = V U, W = V^T T), "theta_grad" (the points, once per chunk).  device_ms (nullable): device time of the call, copies
+ * included. */
+int gpry_mean_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* y_out, double* G_out, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
