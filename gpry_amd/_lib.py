@@ -405,13 +405,23 @@ class Device:
             return val.value, gr.copy(), info.value
         return val.value, info.value
 
+    def _theta_vec(self, theta):
+        theta = _f64(np.asarray(theta, dtype=np.float64).ravel())
+        if theta.shape[0] != self.n_theta:
+            raise ValueError(f"expected {self.n_theta} entries, got {theta.shape[0]}")
+        return theta
+
+    def _theta_rows(self, thetas):
+        thetas = _f64(np.atleast_2d(thetas))
+        if thetas.shape[1] != self.n_theta:
+            raise ValueError(f"expected {self.n_theta} columns, got {thetas.shape[1]}")
+        return thetas
+
     def loo_objective(self, theta, eval_gradient=False):
         """The leave-one-out log predictive density of the training targets at ``theta`` (gpry_loo_objective), transformed
         units like ``lml``: ``(value, info)`` or ``(value, grad, info)``; ``(-inf, zeros, info > 0)`` where the matrix
         is not positive definite.  The factor held for prediction is not disturbed."""
-        theta = _f64(np.asarray(theta, dtype=np.float64).ravel())
-        if theta.shape[0] != self.n_theta:
-            raise ValueError(f"expected {self.n_theta} entries, got {theta.shape[0]}")
+        theta = self._theta_vec(theta)
         grad = np.zeros(self.n_theta)
         val, info = C.c_double(0.0), C.c_int(0)
         self._check(self._lib.gpry_loo_objective(self._h, _ptr(theta), 1 if eval_gradient else 0, C.byref(val), _ptr(grad),
@@ -426,9 +436,7 @@ class Device:
         ``device_ms``.  ``lml`` and ``grad`` have the bits of ``lml(theta, True)``; ``(-inf, zeros, zeros, info > 0)``
         where the matrix is not positive definite.  Models of more than 4096 padded rows are refused.  The factor held
         for prediction is not disturbed."""
-        theta = _f64(np.asarray(theta, dtype=np.float64).ravel())
-        if theta.shape[0] != self.n_theta:
-            raise ValueError(f"expected {self.n_theta} entries, got {theta.shape[0]}")
+        theta = self._theta_vec(theta)
         grad = np.zeros(self.n_theta)
         H = np.zeros((self.n_theta, self.n_theta))
         val, info, ms = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
@@ -436,34 +444,26 @@ class Device:
                                                C.byref(ms)), "gpry_lml_hessian")
         return {"lml": val.value, "grad": grad, "H": H, "info": info.value, "device_ms": ms.value}
 
+    def _objective_batch(self, symbol, thetas, eval_gradient):
+        thetas = self._theta_rows(thetas)
+        B, w = thetas.shape
+        val = np.empty(B)
+        grad = np.zeros((B, w)) if eval_gradient else None
+        info = np.zeros(B, dtype=np.int32)
+        self._check(getattr(self._lib, symbol)(self._h, _ptr(thetas), B, int(bool(eval_gradient)), _ptr(val), _ptr(grad),
+                                               _ptr(info)), symbol)
+        return (val, grad, info) if eval_gradient else (val, info)
+
     def loo_objective_batch(self, thetas, eval_gradient=True):
         """``loo_objective`` for every row of ``thetas`` in one call (gpry_loo_objective_batch): ``(value (B,), grad (B,
         n_theta), info (B,))``, or ``(value, info)`` without gradients.  Up to the ``lml_batch`` limit one chain of launches
         carries all rows; every row has the bits of a single ``loo_objective`` call."""
-        thetas = _f64(np.atleast_2d(thetas))
-        B, w = thetas.shape
-        if w != self.n_theta:
-            raise ValueError(f"expected {self.n_theta} columns, got {w}")
-        val = np.empty(B)
-        grad = np.zeros((B, w)) if eval_gradient else None
-        info = np.zeros(B, dtype=np.int32)
-        self._check(self._lib.gpry_loo_objective_batch(self._h, _ptr(thetas), B, int(bool(eval_gradient)), _ptr(val),
-                                                       _ptr(grad), _ptr(info)), "gpry_loo_objective_batch")
-        return (val, grad, info) if eval_gradient else (val, info)
+        return self._objective_batch("gpry_loo_objective_batch", thetas, eval_gradient)
 
     def lml_batch(self, thetas, eval_gradient=True):
         """``lml`` for every row of ``thetas`` in one call: ``(lml (B,), grad (B, 1 + d), info (B,))`` (``(lml, info)``
         without gradients).  N <= 128, d <= 16: one launch, one workgroup per theta, the bits of single ``lml`` calls."""
-        thetas = _f64(np.atleast_2d(thetas))
-        B, w = thetas.shape
-        if w != self.n_theta:
-            raise ValueError(f"expected {self.n_theta} columns, got {w}")
-        lml = np.empty(B)
-        grad = np.zeros((B, w)) if eval_gradient else None
-        info = np.zeros(B, dtype=np.int32)
-        self._check(self._lib.gpry_lml_batch(self._h, _ptr(thetas), B, int(bool(eval_gradient)), _ptr(lml), _ptr(grad),
-                                             _ptr(info)), "gpry_lml_batch")
-        return (lml, grad, info) if eval_gradient else (lml, info)
+        return self._objective_batch("gpry_lml_batch", thetas, eval_gradient)
 
     # -- predict / sweep ------------------------------------------------------------
     def predict(self, X, return_std=False, mask=None):

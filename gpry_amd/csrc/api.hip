@@ -33,6 +33,56 @@ bool panel_timed_out(int marker) { return (marker & 0xFF00) == 0x5A00; }
 int panel_timeout_error(gpry_ctx* ctx, int marker) {
     return gpry_fail(ctx, -2, "Cholesky panel step timed out (wait %d; the GPU is shared with work that starves the step?)", marker & 0xFF);
 }
+
+// ---- the protocol of an objective evaluation at thetas that are not the context's own (common.h) ------------------------
+int objective_entry(gpry_ctx* ctx, const char* name, const double* thetas, int64_t B) {
+    GPRY_TRY(serve_stop(ctx));
+    if (ctx->N <= 0) return gpry_fail(ctx, -1, "%s: no training set (call gpry_set_train)", name);
+    const int w = ctx_ntheta(ctx);      // 1 + d, one more (log w) for a model set with GPRY_KERNEL_WHITE
+    for (int64_t i = 0; i < B * w; i++)
+        if (!isfinite(thetas[i]))
+            return gpry_fail(ctx, -1, "%s: theta[%d] of evaluation %lld is not finite", name, (int)(i % w), (long long)(i / w));
+    if (ctx->d > 32) return gpry_fail(ctx, -1, "%s: d > 32 is not supported", name);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->lml_cache = false;
+    return 0;
+}
+int objective_row(gpry_ctx* ctx, int64_t bytes, int info_at, double** hres, double** dres) {
+    GPRY_TRY(ensure_pinned(ctx, bytes));
+    *hres = static_cast<double*>(ctx->hpin);
+    *dres = static_cast<double*>(ctx->hpin_dev);        // the same buffer as the device sees it
+    objective_row_unwritten(*hres, info_at);
+    return 0;
+}
+int objective_status(gpry_ctx* ctx, const char* name, int64_t which, const double* row, int info_at, int* info) {
+    if (row[info_at] < 0.0) return gpry_fail(ctx, -2, "%s: evaluation %lld did not deliver its status", name, (long long)which);
+    if (panel_timed_out((int)row[info_at + 2])) return panel_timeout_error(ctx, (int)row[info_at + 2]);
+    const int i0 = (int)row[info_at], i1 = (int)row[info_at + 1];
+    *info = i0 != 0 ? i0 : i1;
+    return 0;
+}
+// The factorisation status is not waited for in the middle of a chain (every kernel behind a failed factorisation either
+// exits on *dinfo != 0 or works on values nobody reads); status and results come back together at the end, written into the
+// mapped row by the last kernels themselves (no copy-out operations behind the evaluation).
+// (Polling the status word in the mapped buffer instead of waiting for the stream returns 15 us earlier and is WRONG: inbound
+// PCIe writes to different cache lines are not ordered here -- the host saw the status before the last gradient entries in
+// 2 % of the evaluations, tests/tools/stress_concurrent_fit.py; a loop over hipStreamQuery is correct and no faster than
+// hipStreamSynchronize.)
+int objective_wait(gpry_ctx* ctx, const char* name, int rc, const double* row, int info_at, int* info) {
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) return gpry_fail(ctx, -2, "%s: %s", name, hipGetErrorString(e));
+    return row ? objective_status(ctx, name, 0, row, info_at, info) : 0;
+}
+void objective_write(const gpry_ctx* ctx, int info, double head, const double* g, const double* h, double* value, double* grad,
+                     double* hess) {
+    const int w = ctx_ntheta(ctx);
+    const bool pd = info == 0;          // otherwise sklearn:_gpr.py:586-589
+    *value = pd ? head - 0.5 * (double)ctx->N * log(2.0 * M_PI) : -INFINITY;
+    if (grad) for (int k = 0; k < w; k++) grad[k] = pd ? g[k] : 0.0;
+    if (hess) for (int k = 0; k < w * w; k++) hess[k] = pd ? h[k] : 0.0;
+}
+
 int build_factor(gpry_ctx* ctx, double* A, double* V, double* T, int* info_host) {
     // A <- K + diag(alpha); A <- chol(A) (lower); V <- A^-1
     GPRY_TRY(launch_scale_train(ctx));      // X / l (N x d, microseconds)
@@ -137,7 +187,7 @@ static int batch_layout(gpry_ctx* ctx, const BatchChain& bc, BatchLayout* L) {
     const int64_t Np = ctx->Np, nn = Np * Np;
     int slices = 0;
     GPRY_TRY(factor_chain_slices(ctx, Np, &slices));
-    const int DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    const int DPsel = dp_class(ctx->d);
     const int64_t nb = Np / 64, ntile = nb * (nb + 1) / 2;
     const int64_t p1 = ((Np + 255) / 256) * Np, p2 = ntile * (DPsel + 2);       // solve_alpha, launch_lml_traces
     int64_t o = 0;
@@ -181,15 +231,10 @@ static bool lml_batch_usable(const gpry_ctx* ctx) {
     return ctx->N > 0 && ctx->Np > 128 && ctx->Np <= ctx->opt_lml_batch && ctx->d <= 32 && ctx->opt_chol == 0;
 }
 // the LML's chain as objective_batch_general runs it (gpry_loo_objective_batch hands in its own: loo_fit.hip)
-static const BatchChain LML_BATCH = {"lml_batch", lml_chain, false, 0, 0, 2, RES_INFO,
-                                     [](const double* o) { return -0.5 * o[1] - o[0]; }};
+static const BatchChain LML_BATCH = {"lml_batch", lml_chain, false, 0, 0, 2, RES_INFO, lml_head};
 int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* thetas, int64_t B, int want_grad, double* lml, double* grad,
                             int* info) {
-    const int w = ctx_ntheta(ctx);
-    for (int64_t i = 0; i < B * w; i++)
-        if (!isfinite(thetas[i])) return gpry_fail(ctx, -1, "theta[%d] is not finite", (int)(i % w));
-    GPRY_TRY(serve_stop(ctx));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int w = ctx_ntheta(ctx);      // (the caller has run objective_entry on the thetas)
     // the chain below is the code of a single evaluation: it finds the buffers of theta 0 where the context keeps its own
     struct Scope {
         gpry_ctx* c;
@@ -268,7 +313,6 @@ int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* t
         ctx->bn = (int)n; ctx->stream = st;
     };
     ctx->have_theta = true;
-    const double log2pi = log(2.0 * M_PI);
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
         for (int64_t b = 0; b < nb; b++) {
@@ -278,7 +322,7 @@ int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* t
             row[0] = exp(th[0]);                                     // as make_kp / make_ap for one evaluation
             for (int k = 0; k < ctx->d; k++) row[1 + k] = exp(th[1 + k]);
             row[GPRY_BPAR_WHITE] = ctx->white ? exp(th[1 + ctx->d]) : 0.0;
-            hres[b * GPRY_BRES_STRIDE + bc.info_at] = -1.0; hres[b * GPRY_BRES_STRIDE + bc.info_at + 1] = -1.0;     // "not written"
+            objective_row_unwritten(hres + b * GPRY_BRES_STRIDE, bc.info_at);
         }
         for (int k = 0; k < w; k++) ctx->theta[k] = thetas[b0 * w + k];      // (the launchers read the sizes, not these, in a batch)
         // test hook ("panel_debug" bit 7): every scratch set starts as NaNs -- a result that depended on what a set held before shows
@@ -330,18 +374,10 @@ int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* t
         HIP_TRY(ctx, hipStreamSynchronize(main_stream));
         for (int64_t b = 0; b < nb; b++) {
             const double* o = hres + b * GPRY_BRES_STRIDE;
-            if (o[bc.info_at] < 0.0) return gpry_fail(ctx, -2, "%s: evaluation %lld did not deliver its status", bc.name, (long long)(b0 + b));
-            const int i0 = (int)o[bc.info_at], i1 = (int)o[bc.info_at + 1];
-            if (panel_timed_out((int)o[bc.info_at + 2])) return panel_timeout_error(ctx, (int)o[bc.info_at + 2]);
-            const int inf = i0 != 0 ? i0 : i1;
+            int inf = 0;
+            GPRY_TRY(objective_status(ctx, bc.name, b0 + b, o, bc.info_at, &inf));
             if (info) info[b0 + b] = inf;
-            if (inf != 0) {   // sklearn:_gpr.py:586-589
-                lml[b0 + b] = -INFINITY;
-                if (want_grad) for (int k = 0; k < w; k++) grad[(b0 + b) * w + k] = 0.0;
-                continue;
-            }
-            lml[b0 + b] = bc.value(o) - 0.5 * (double)ctx->N * log2pi;
-            if (want_grad) for (int k = 0; k < w; k++) grad[(b0 + b) * w + k] = o[bc.head + k];
+            objective_write(ctx, inf, bc.value(o), o + bc.head, nullptr, lml + b0 + b, want_grad ? grad + (b0 + b) * w : nullptr, nullptr);
         }
     }
     return 0;
@@ -453,81 +489,40 @@ int gpry_get_factor(gpry_ctx* ctx, double* L, double* V, double* alpha_) {
 
 int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml, double* grad, int* info) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_lml: ctx is NULL");
-    GPRY_TRY(serve_stop(ctx));
-    if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
     if (!theta || !lml || (want_grad && !grad)) return gpry_fail(ctx, -1, "lml: theta, lml and (with want_grad) grad must not be NULL");
-    const int nth = ctx_ntheta(ctx);      // 1 + d, one more (log w) for a model set with GPRY_KERNEL_WHITE
-    for (int k = 0; k < nth; k++)
-        if (!isfinite(theta[k])) return gpry_fail(ctx, -1, "theta[%d] is not finite", k);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // evaluate at `theta` without disturbing the prediction factor (dA, dV, dalpha_)
-    double saved[GPRY_THETA_MAX];
-    bool had = ctx->have_theta;
-    memcpy(saved, ctx->theta, sizeof(saved));
-    for (int k = 0; k < nth; k++) ctx->theta[k] = theta[k];
-    ctx->have_theta = true;
-    // One stream synchronisation per evaluation: the factorisation status is not waited for in the
-    // middle (every kernel behind a failed factorisation either exits on *dinfo != 0 or works on
-    // values nobody reads); status and results come back together at the end.
-    // Results and factorisation status land in the pinned, device-mapped staging buffer: the last kernels
-    // of the evaluation write them there themselves (no copy-out operations behind the evaluation).
-    int rc = ensure_pinned(ctx, 4096);
-    double* hres = static_cast<double*>(ctx->hpin);
-    double* dres = static_cast<double*>(ctx->hpin_dev);     // the same buffer as the device sees it
-    if (rc == 0) { hres[RES_INFO] = -1.0; hres[RES_INFO + 1] = -1.0; }      // "not written" marker
+    GPRY_TRY(objective_entry(ctx, "lml", theta, 1));
+    double *hres, *dres;
+    GPRY_TRY(objective_row(ctx, 4096, RES_INFO, &hres, &dres));
+    ThetaScope at(ctx, theta);
     // N <= 128, d <= 16: the whole evaluation in one launch of one workgroup (lml_small.hip); it leaves no factor in
     // dW / dW2 and does not touch the scaled coordinates of the prediction factor
     bool fused = false;
     double fhost[2 + GPRY_THETA_MAX];
-    int finfo = 0;
-    if (rc == 0 && ctx->opt_lml_small && ctx->opt_chol == 0) {
+    int rc = 0, inf = 0;
+    if (ctx->opt_lml_small && ctx->opt_chol == 0) {
         StageScope s(ctx, "lml_small");
-        const int r = launch_lml_small(ctx, want_grad, fhost, &finfo);     // returns with the results in hand
+        const int r = launch_lml_small(ctx, want_grad, fhost, &inf);     // returns with the results in hand
         if (r < 0) rc = r;
         fused = r == 0;
     }
-    const bool rescaled = rc == 0 && !fused;        // build_factor scales the training coordinates for THIS theta
-    if (rescaled) rc = lml_chain(ctx, want_grad, dres);
-    memcpy(ctx->theta, saved, sizeof(saved));
-    ctx->have_theta = had;
-    // the scaled training coordinates belong to the prediction factor: whoever needs them next restores them
-    // (ensure_pred_xs; an optimiser's next evaluation does not)
-    if (rescaled && had && ctx->factor_valid) ctx->xs_foreign = true;
-    double host[2 + GPRY_THETA_MAX];
-    int hinfo[2] = {0, 0};
-    if (rc == 0 && fused) {
-        memcpy(host, fhost, sizeof(double) * (2 + (want_grad ? nth : 0)));
-        hinfo[0] = finfo;
-    } else if (rc == 0) {
-        // (Polling the status word in the mapped buffer instead of waiting for the stream returns 15 us earlier and is
-        // WRONG: inbound PCIe writes to different cache lines are not ordered here -- the host saw the status before
-        // the last gradient entries in 2 % of the evaluations, tests/tools/stress_concurrent_fit.py; a loop over
-        // hipStreamQuery is correct and no faster than hipStreamSynchronize.)
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = gpry_fail(ctx, -2, "lml: %s", hipGetErrorString(e));
-        else if (hres[RES_INFO] < 0.0) rc = gpry_fail(ctx, -2, "lml: the evaluation did not deliver its status");
-        else {
-            memcpy(host, hres, sizeof(double) * (2 + (want_grad ? nth : 0)));
-            hinfo[0] = (int)hres[RES_INFO]; hinfo[1] = (int)hres[RES_INFO + 1];
-            if (panel_timed_out((int)hres[RES_INFO + 2])) rc = panel_timeout_error(ctx, (int)hres[RES_INFO + 2]);
+    if (!fused) {
+        if (rc == 0) {
+            rc = lml_chain(ctx, want_grad, dres);
+            at.factor_chain_ran();      // (an optimiser's next evaluation does not need the coordinates put back)
         }
+        rc = objective_wait(ctx, "lml", rc, hres, RES_INFO, &inf);
     }
-    const int inf = hinfo[0] != 0 ? hinfo[0] : hinfo[1];
-    ctx->lml_cache = (rc == 0 && inf == 0 && !fused);
+    // the chain left L in dW and V in dW2: gpry_factorize at this theta adopts them
+    ctx->lml_cache = rc == 0 && inf == 0 && !fused;
     if (ctx->lml_cache) {
         memset(ctx->lml_theta, 0, sizeof(ctx->lml_theta));
-        for (int k = 0; k < nth; k++) ctx->lml_theta[k] = theta[k];
+        for (int k = 0; k < ctx_ntheta(ctx); k++) ctx->lml_theta[k] = theta[k];
         ctx->lml_kernel_id = ctx->kernel_id | (ctx->white ? GPRY_KERNEL_WHITE : 0);
     }
     if (rc) return rc;
     if (info) *info = inf;
-    if (inf != 0) {   // sklearn:_gpr.py:586-589
-        *lml = -INFINITY;
-        if (want_grad && grad) for (int k = 0; k < nth; k++) grad[k] = 0.0;
-        return 0;
-    }
-    *lml = -0.5 * host[1] - host[0] - 0.5 * (double)ctx->N * log(2.0 * M_PI);
-    if (want_grad && grad) for (int k = 0; k < nth; k++) grad[k] = host[2 + k];
+    const double* row = fused ? fhost : hres;
+    objective_write(ctx, inf, lml_head(row), row + 2, nullptr, lml, want_grad ? grad : nullptr, nullptr);
     return 0;
 }
 
@@ -539,9 +534,9 @@ int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_lml_batch: ctx is NULL");
     if (B <= 0) return 0;
     if (!thetas || !lml || (want_grad && !grad)) return gpry_fail(ctx, -1, "lml_batch: thetas, lml and (with want_grad) grad must not be NULL");
+    GPRY_TRY(objective_entry(ctx, "lml_batch", thetas, B));
     const int w = ctx_ntheta(ctx);
-    bool fused = ctx->N > 0 && ctx->opt_lml_small && ctx->opt_chol == 0 && ctx->Np == 128 && ctx->d <= 16 && B <= 256;
-    for (int64_t i = 0; fused && i < B * w; i++) fused = isfinite(thetas[i]);
+    const bool fused = ctx->opt_lml_small && ctx->opt_chol == 0 && ctx->Np == 128 && ctx->d <= 16 && B <= 256;
     // (throughput schedule: a single theta goes through the chain of the many as well -- its result must not depend on B)
     if (!fused && (B >= 2 || ctx->opt_lml_schedule == 1) && lml_batch_usable(ctx)) {
         const int r = objective_batch_general(ctx, LML_BATCH, thetas, B, want_grad, lml, grad, info);
@@ -555,8 +550,6 @@ int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad
         }
         return 0;
     }
-    GPRY_TRY(serve_stop(ctx));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<double> par((size_t)B * 18, 1.0), out((size_t)B * (2 + 1 + GPRY_MAX_DIM), 0.0);
     std::vector<int> inf((size_t)B, 0);
     for (int64_t b = 0; b < B; b++) {
@@ -570,17 +563,10 @@ int gpry_lml_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad
         if (r < 0) return r;
         if (r != 0) return gpry_fail(ctx, -1, "lml_batch: the model does not fit the single-launch kernel");
     }
-    ctx->lml_cache = false;
     for (int64_t b = 0; b < B; b++) {
         const double* o = out.data() + b * (2 + 1 + GPRY_MAX_DIM);
         if (info) info[b] = inf[b];
-        if (inf[b] != 0) {   // sklearn:_gpr.py:586-589
-            lml[b] = -INFINITY;
-            if (want_grad) for (int k = 0; k < w; k++) grad[b * w + k] = 0.0;
-            continue;
-        }
-        lml[b] = -0.5 * o[1] - o[0] - 0.5 * (double)ctx->N * log(2.0 * M_PI);
-        if (want_grad) for (int k = 0; k < w; k++) grad[b * w + k] = o[2 + k];
+        objective_write(ctx, inf[b], lml_head(o), o + 2, nullptr, lml + b, want_grad ? grad + b * w : nullptr, nullptr);
     }
     return 0;
 }

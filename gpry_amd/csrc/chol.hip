@@ -497,8 +497,7 @@ int lauum_lower(gpry_ctx* ctx, const double* V, double* Kinv, int64_t Np) {
     // 332 -> 130 us with the balanced tile map; Np = 4096, 528 tiles: x2, 0.63 -> 0.51 ms); at
     // Np = 8192 (2080 tiles) it costs 5 %.
     const int64_t tiles = (Np / 128) * (Np / 128 + 1) / 2;
-    int nsplit = 1;
-    while (!ctx->tp && nsplit < 4 && tiles * nsplit * 2 <= 1100 && Np / (nsplit * 2) >= 256) nsplit *= 2;
+    const int nsplit = ctx->tp ? 1 : splitk_count(tiles, Np);
     if (nsplit > 1) {
         double* sbuf = nullptr;
         GPRY_TRY(gemm_split_scratch(ctx, nsplit, Np * Np, &sbuf));
@@ -527,9 +526,7 @@ int factor_chain_slices(gpry_ctx* ctx, int64_t Np, int* slices) {
     if (Np >= 512 && Np <= ctx->opt_gemm_streamk) {
         if (pl->sk_lauum.max_slices > m) m = pl->sk_lauum.max_slices;
     } else {
-        const int64_t tiles = (Np / 128) * (Np / 128 + 1) / 2;
-        int nsplit = 1;
-        while (nsplit < 4 && tiles * nsplit * 2 <= 1100 && Np / (nsplit * 2) >= 256) nsplit *= 2;
+        const int nsplit = splitk_count((Np / 128) * (Np / 128 + 1) / 2, Np);
         if (nsplit > m) m = nsplit;
     }
     *slices = m > 1 ? m : 0;

@@ -533,5 +533,53 @@ struct BatchChain {
 int objective_batch_general(gpry_ctx* ctx, const BatchChain& bc, const double* thetas, int64_t B, int want_grad, double* value,
                             double* grad, int* info);
 
+// ---- api.hip: the protocol of every entry point that evaluates a fit objective at thetas that are not the context's own
+// (gpry_lml, gpry_lml_batch, gpry_loo_objective, gpry_loo_objective_batch, gpry_lml_hessian) ------
+// Entry checks on B rows of ctx_ntheta entries: a training set is there, every entry is finite, d <= 32.  Stops the resident
+// predict kernel, selects the device and disarms the adoption of gpry_lml's factor by gpry_factorize (gpry_ctx::lml_cache: an
+// evaluation borrows the scratch that factor lives in; only gpry_lml arms it again, behind a chain that left a factor there).
+int objective_entry(gpry_ctx* ctx, const char* name, const double* thetas, int64_t B);
+// a chain's factor scaled the training coordinates for its own theta: they belong to the prediction factor, and whoever needs
+// them next restores them (ensure_pred_xs).  `had`: the context held a theta of its own when the call came in.
+static inline void note_xs_foreign(gpry_ctx* ctx, bool had) { if (had && ctx->factor_valid) ctx->xs_foreign = true; }
+// installs `theta` as the context's for the length of a scope: the prediction factor (dA, dV, dalpha_) is not disturbed
+struct ThetaScope {
+    gpry_ctx* c; bool had; double saved[GPRY_THETA_MAX];
+    ThetaScope(gpry_ctx* ctx, const double* theta) : c(ctx), had(ctx->have_theta) {
+        memcpy(saved, ctx->theta, sizeof(saved));
+        for (int k = 0; k < ctx_ntheta(ctx); k++) ctx->theta[k] = theta[k];
+        ctx->have_theta = true;
+    }
+    ~ThetaScope() { memcpy(c->theta, saved, sizeof(saved)); c->have_theta = had; }
+    void factor_chain_ran() { note_xs_foreign(c, had); }
+};
+// A result row [head ..., status words from info_at] in mapped host memory.  The last kernel of a chain writes the status
+// words; until then they hold the "not written" marker.
+static inline void objective_row_unwritten(double* row, int info_at) { row[info_at] = -1.0; row[info_at + 1] = -1.0; }
+// the context's pinned staging buffer as the result row of a single evaluation (at least `bytes`), marked "not written"
+int objective_row(gpry_ctx* ctx, int64_t bytes, int info_at, double** hres, double** dres);
+// *info of evaluation `which` from its row, read behind a stream synchronisation; a row without status and a panel step whose
+// bounded waits ran out are errors
+int objective_status(gpry_ctx* ctx, const char* name, int64_t which, const double* row, int info_at, int* info);
+// One stream synchronisation per single evaluation, also behind a chain that failed (rc != 0, which is returned): nothing of
+// the call stays in flight.  Then objective_status of `row` (NULL: no chain ran, *info stays).
+int objective_wait(gpry_ctx* ctx, const char* name, int rc, const double* row, int info_at, int* info);
+// Value, gradient (grad != NULL: ctx_ntheta entries from g) and Hessian (hess != NULL: from h) of one evaluation as the caller
+// gets them: `head` - N/2 log 2 pi, or with info != 0 the convention of sklearn:_gpr.py:586-589, -inf and zeros.
+void objective_write(const gpry_ctx* ctx, int info, double head, const double* g, const double* h, double* value, double* grad,
+                     double* hess);
+// the head of gpry_lml's row [logdet/2, quad, grad ...]
+static inline double lml_head(const double* row) { return -0.5 * row[1] - row[0]; }
+
+// width class of the kernels that are instantiated per number of dimensions
+static inline int dp_class(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 24 ? 24 : 32; }
+// split-K count of an engine launch of `tiles` 128 x 128 output tiles over K = Np: only where the tiles leave most of the GPU
+// idle and a slice keeps 256 of K
+static inline int splitk_count(int64_t tiles, int64_t Np) {
+    int nsplit = 1;
+    while (nsplit < 4 && tiles * nsplit * 2 <= 1100 && Np / (nsplit * 2) >= 256) nsplit *= 2;
+    return nsplit;
+}
+
 int ensure_capacity(gpry_ctx* ctx, int64_t N, int d);
 int ensure_pinned(gpry_ctx* ctx, int64_t bytes);

@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256) void center_cand_kernel(const double* __restri
 }
 
 int launch_cross_prepare(gpry_ctx* ctx) {
-    const int dsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    const int dsel = dp_class(ctx->d);
     if (ctx->Np * dsel > ctx->ycs_cap) {
         if (ctx->dYcs) GPRY_TRY(dev_free(ctx, ctx->dYcs));
         ctx->dYcs = nullptr; ctx->ycs_cap = 0;
@@ -618,7 +618,7 @@ static int center_cands(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc,
     AffParams ap = make_ap(ctx, kp->has_aff), cen;
     for (int k = 0; k < GPRY_MAX_DIM; k++) { cen.ls[k] = 1.0; cen.span[k] = 1.0; cen.lo[k] = k < ctx->d ? ctx->xcenter[k] : 0.0; }
     if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
-    const int dsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    const int dsel = dp_class(ctx->d);
     const int64_t ldm = round_up(mc, 256);
     if (dsel * ldm > ctx->xcs_cap) {
         if (ctx->dXcs) GPRY_TRY(dev_free(ctx, ctx->dXcs));
@@ -770,7 +770,7 @@ int launch_cross_build(gpry_ctx* ctx, const double* Xc, int64_t m0, int64_t mc, 
     dim3 grid((unsigned)((mc + 255) / 256), (unsigned)(ctx->Np / 128));
     int64_t M = ctx->sw_M;
     if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
-    const int dsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    const int dsel = dp_class(ctx->d);
     const int64_t ldm = round_up(mc, 256);
     if (dsel * ldm > ctx->xcs_cap) {
         if (ctx->dXcs) GPRY_TRY(dev_free(ctx, ctx->dXcs));
@@ -1001,7 +1001,7 @@ int launch_lml_traces(gpry_ctx* ctx, const double* Kinv, const double* alpha, do
     int64_t nb = ctx->Np / 64;
     int64_t ntile = nb * (nb + 1) / 2;
     if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
-    int DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    int DPsel = dp_class(ctx->d);
     int64_t need = ntile * (DPsel + 2);
     if (need > ctx->part_cap && ctx->bpar) return gpry_fail(ctx, -1, "batched chain: partial sums exceed the arena");
     if (need > ctx->part_cap) {

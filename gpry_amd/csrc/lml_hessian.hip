@@ -420,9 +420,7 @@ LmlHessPlan lml_hess_plan(const gpry_ctx* ctx) {
     q.o_items = q.o_tp + q.ntile * (q.MB * 16) * (q.MB * 16);
     q.need = q.o_items + LH_ITEM_DOUBLES;
     // split-K of the batched product: only where the d * (Np / 128)^2 tiles leave most of the GPU idle
-    const int64_t tiles = (int64_t)d * (Np / 128) * (Np / 128);
-    q.nsplit = 1;
-    while (q.nsplit < 4 && tiles * q.nsplit * 2 <= 1100 && Np / (q.nsplit * 2) >= 256) q.nsplit *= 2;
+    q.nsplit = splitk_count((int64_t)d * (Np / 128) * (Np / 128), Np);
     return q;
 }
 
@@ -506,24 +504,14 @@ extern "C" {
 
 int gpry_lml_hessian(gpry_ctx* ctx, const double* theta, double* lml, double* grad, double* hess, int* info, double* device_ms) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_lml_hessian: ctx is NULL");
-    GPRY_TRY(serve_stop(ctx));
-    if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
     if (!theta || !lml || !grad || !hess || !info)
         return gpry_fail(ctx, -1, "lml_hessian: theta, lml, grad, hess and info must not be NULL");
-    const int nth = ctx_ntheta(ctx);      // 1 + d, one more (log w) for a model set with GPRY_KERNEL_WHITE
-    for (int k = 0; k < nth; k++)
-        if (!isfinite(theta[k])) return gpry_fail(ctx, -1, "theta[%d] is not finite", k);
-    if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
+    GPRY_TRY(objective_entry(ctx, "lml_hessian", theta, 1));
     if (ctx->Np > LH_MAX_NP)
         return gpry_fail(ctx, -1, "lml_hessian: %lld padded rows exceed the limit of %d", (long long)ctx->Np, LH_MAX_NP);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    GPRY_TRY(ensure_pinned(ctx, 8 * (LH_HOFF + GPRY_THETA_MAX * GPRY_THETA_MAX)));
-    // evaluate at `theta` without disturbing the prediction factor (dA, dV, dalpha_), as gpry_lml does
-    double saved[GPRY_THETA_MAX];
-    const bool had = ctx->have_theta;
-    memcpy(saved, ctx->theta, sizeof(saved));
-    for (int k = 0; k < nth; k++) ctx->theta[k] = theta[k];
-    ctx->have_theta = true;
+    double *hres, *dres;
+    GPRY_TRY(objective_row(ctx, 8 * (LH_HOFF + GPRY_THETA_MAX * GPRY_THETA_MAX), LH_INFO, &hres, &dres));
+    ThetaScope at(ctx, theta);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int rc = 0;
     if (device_ms) {
@@ -536,50 +524,28 @@ int gpry_lml_hessian(gpry_ctx* ctx, const double* theta, double* lml, double* gr
     // for such a model H[0][j] == grad[j] holds to rounding, not to the bit.
     bool fused = false;
     double fhost[2 + GPRY_THETA_MAX];
-    int finfo = 0;
+    int finfo = 0, cinfo = 0;
     if (rc == 0 && ctx->opt_lml_small && ctx->opt_chol == 0) {
         StageScope s(ctx, "lml_small");
         const int r = launch_lml_small(ctx, 1, fhost, &finfo);
         if (r < 0) rc = r;
         fused = r == 0;
     }
-    double* hres = static_cast<double*>(ctx->hpin);
-    double* dres = static_cast<double*>(ctx->hpin_dev);     // the same buffer as the device sees it
-    hres[LH_INFO] = -1.0; hres[LH_INFO + 1] = -1.0;         // "not written" marker
-    ctx->lml_cache = false;         // the scratch is about to be overwritten
     const bool ran = rc == 0 && !(fused && finfo != 0);
-    if (ran) rc = lml_hess_chain(ctx, dres);
+    if (ran) {
+        rc = lml_hess_chain(ctx, dres);
+        at.factor_chain_ran();
+    }
     if (ev1 && rc == 0) (void)hipEventRecord(ev1, ctx->stream);
-    memcpy(ctx->theta, saved, sizeof(saved));
-    ctx->have_theta = had;
-    // the scaled training coordinates belong to the prediction factor: whoever needs them next restores them
-    if (ran && had && ctx->factor_valid) ctx->xs_foreign = true;
-    const hipError_t e = hipStreamSynchronize(ctx->stream);    // (also on the error path: nothing of this call stays in flight)
+    rc = objective_wait(ctx, "lml_hessian", rc, ran ? hres : nullptr, LH_INFO, &cinfo);
     float ms = 0.0f;
-    if (ev0 && ev1 && rc == 0 && e == hipSuccess) (void)hipEventElapsedTime(&ms, ev0, ev1);
+    if (ev0 && ev1 && rc == 0) (void)hipEventElapsedTime(&ms, ev0, ev1);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (device_ms) *device_ms = (double)ms;
     if (rc) return rc;
-    if (e != hipSuccess) return gpry_fail(ctx, -2, "lml_hessian: %s", hipGetErrorString(e));
-    int inf = finfo;
-    if (ran) {
-        if (hres[LH_INFO] < 0.0) return gpry_fail(ctx, -2, "lml_hessian: the evaluation did not deliver its status");
-        if (panel_timed_out((int)hres[LH_INFO + 2])) return panel_timeout_error(ctx, (int)hres[LH_INFO + 2]);
-        const int i0 = (int)hres[LH_INFO], i1 = (int)hres[LH_INFO + 1];
-        if (inf == 0) inf = i0 != 0 ? i0 : i1;
-    }
-    *info = inf;
-    if (inf != 0) {   // the convention of gpry_lml (sklearn:_gpr.py:586-589)
-        *lml = -INFINITY;
-        for (int k = 0; k < nth; k++) grad[k] = 0.0;
-        for (int k = 0; k < nth * nth; k++) hess[k] = 0.0;
-        return 0;
-    }
-    const double* vg = fused ? fhost : hres;
-    *lml = -0.5 * vg[1] - vg[0] - 0.5 * (double)ctx->N * log(2.0 * M_PI);
-    for (int k = 0; k < nth; k++) grad[k] = vg[2 + k];
-    for (int k = 0; k < nth * nth; k++) hess[k] = hres[LH_HOFF + k];
+    *info = finfo != 0 ? finfo : cinfo;
+    objective_write(ctx, *info, lml_head(fused ? fhost : hres), (fused ? fhost : hres) + 2, hres + LH_HOFF, lml, grad, hess);
     return 0;
 }
 

@@ -354,15 +354,13 @@ LooFitPlan loo_fit_plan(const gpry_ctx* ctx) {
     const int64_t Np = ctx->Np;
     p.nt = (int)((ctx->N + LF_T - 1) / LF_T); p.nb = (int)(Np / LF_T);
     p.ntile = (int64_t)p.nb * (p.nb + 1) / 2;
-    p.DPsel = ctx->d <= 4 ? 4 : ctx->d <= 8 ? 8 : ctx->d <= 16 ? 16 : ctx->d <= 24 ? 24 : 32;
+    p.DPsel = dp_class(ctx->d);
     p.o_q = 0; p.o_w = p.o_q + (int64_t)p.nt * Np; p.o_b = p.o_w + (int64_t)p.nt * Np; p.o_tr = p.o_b + (int64_t)p.nb * Np;
     p.need = p.o_tr + p.ntile * (p.DPsel + 2);
     const int64_t need_solve = ((Np + 255) / 256) * Np;
     if (p.need < need_solve) p.need = need_solve;
     // the split of K^-1 = V^T V's engine launch (lauum_lower)
-    const int64_t tiles = (Np / 128) * (Np / 128 + 1) / 2;
-    p.nsplit = 1;
-    while (p.nsplit < 4 && tiles * p.nsplit * 2 <= 1100 && Np / (p.nsplit * 2) >= 256) p.nsplit *= 2;
+    p.nsplit = splitk_count((Np / 128) * (Np / 128 + 1) / 2, Np);
     return p;
 }
 
@@ -452,46 +450,20 @@ extern "C" {
 
 int gpry_loo_objective(gpry_ctx* ctx, const double* theta, int want_grad, double* value, double* grad, int* info) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_loo_objective: ctx is NULL");
-    GPRY_TRY(serve_stop(ctx));
-    if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
     if (!theta || !value || (want_grad && !grad))
         return gpry_fail(ctx, -1, "loo_objective: theta, value and (with want_grad) grad must not be NULL");
-    const int nth = ctx_ntheta(ctx);      // 1 + d, one more (log w) for a model set with GPRY_KERNEL_WHITE
-    for (int k = 0; k < nth; k++)
-        if (!isfinite(theta[k])) return gpry_fail(ctx, -1, "theta[%d] is not finite", k);
-    if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    GPRY_TRY(ensure_pinned(ctx, 4096));
-    double* hres = static_cast<double*>(ctx->hpin);
-    double* dres = static_cast<double*>(ctx->hpin_dev);     // the same buffer as the device sees it
-    hres[LF_INFO] = -1.0; hres[LF_INFO + 1] = -1.0;         // "not written" marker
-    // evaluate at `theta` without disturbing the prediction factor (dA, dV, dalpha_), as gpry_lml does
-    double saved[GPRY_THETA_MAX];
-    const bool had = ctx->have_theta;
-    memcpy(saved, ctx->theta, sizeof(saved));
-    for (int k = 0; k < nth; k++) ctx->theta[k] = theta[k];
-    ctx->have_theta = true;
-    ctx->lml_cache = false;         // L and V of the scratch are about to be overwritten (by the factor, then by H and M)
-    int rc = loo_fit_chain(ctx, want_grad, dres);
-    memcpy(ctx->theta, saved, sizeof(saved));
-    ctx->have_theta = had;
-    // the scaled training coordinates belong to the prediction factor: whoever needs them next restores them
-    if (had && ctx->factor_valid) ctx->xs_foreign = true;
-    const hipError_t e = hipStreamSynchronize(ctx->stream);    // (also on the error path: nothing of this call stays in flight)
-    if (rc) return rc;
-    if (e != hipSuccess) return gpry_fail(ctx, -2, "loo_objective: %s", hipGetErrorString(e));
-    if (hres[LF_INFO] < 0.0) return gpry_fail(ctx, -2, "loo_objective: the evaluation did not deliver its status");
-    if (panel_timed_out((int)hres[LF_INFO + 2])) return panel_timeout_error(ctx, (int)hres[LF_INFO + 2]);
-    const int i0 = (int)hres[LF_INFO], i1 = (int)hres[LF_INFO + 1];
-    const int inf = i0 != 0 ? i0 : i1;
-    if (info) *info = inf;
-    if (inf != 0) {   // the convention of gpry_lml (sklearn:_gpr.py:586-589)
-        *value = -INFINITY;
-        if (want_grad) for (int k = 0; k < nth; k++) grad[k] = 0.0;
-        return 0;
+    GPRY_TRY(objective_entry(ctx, "loo_objective", theta, 1));
+    double *hres, *dres;
+    GPRY_TRY(objective_row(ctx, 4096, LF_INFO, &hres, &dres));
+    int inf = 0;
+    {
+        ThetaScope at(ctx, theta);      // L and V of the scratch are overwritten: by the factor, then by H and M
+        const int rc = loo_fit_chain(ctx, want_grad, dres);
+        at.factor_chain_ran();
+        GPRY_TRY(objective_wait(ctx, "loo_objective", rc, hres, LF_INFO, &inf));
     }
-    *value = hres[0] - 0.5 * (double)ctx->N * log(2.0 * M_PI);
-    if (want_grad) for (int k = 0; k < nth; k++) grad[k] = hres[1 + k];
+    if (info) *info = inf;
+    objective_write(ctx, inf, hres[0], hres + 1, nullptr, value, want_grad ? grad : nullptr, nullptr);
     return 0;
 }
 
@@ -503,24 +475,19 @@ int gpry_loo_objective(gpry_ctx* ctx, const double* theta, int want_grad, double
 // gpry_loo_objective after another.  Either way every theta gets the launches of a single evaluation, hence its bits.
 int gpry_loo_objective_batch(gpry_ctx* ctx, const double* thetas, int64_t B, int want_grad, double* value, double* grad, int* info) {
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_loo_objective_batch: ctx is NULL");
-    GPRY_TRY(serve_stop(ctx));
-    if (ctx->N <= 0) return gpry_fail(ctx, -1, "no training set (call gpry_set_train)");
     if (B <= 0) return gpry_fail(ctx, -1, "loo_objective_batch: B = %lld thetas", (long long)B);
     if (!thetas || !value || (want_grad && !grad))
         return gpry_fail(ctx, -1, "loo_objective_batch: thetas, value and (with want_grad) grad must not be NULL");
+    GPRY_TRY(objective_entry(ctx, "loo_objective_batch", thetas, B));
     const int w = ctx_ntheta(ctx);
-    for (int64_t i = 0; i < B * w; i++)
-        if (!isfinite(thetas[i])) return gpry_fail(ctx, -1, "theta[%d] of evaluation %lld is not finite", (int)(i % w), (long long)(i / w));
-    if (ctx->d > 32) return gpry_fail(ctx, -1, "d > 32 is not supported");
     if (B >= 2 && ctx->Np >= 128 && ctx->Np <= ctx->opt_lml_batch && ctx->opt_chol == 0) {
         const LooFitPlan pl = loo_fit_plan(ctx);
         const BatchChain bc = {"loo_batch", loo_fit_chain, true, pl.need, pl.nsplit > 1 ? (int64_t)pl.nsplit * ctx->Np * ctx->Np : 0,
                                1, LF_INFO, [](const double* o) { return o[0]; }};
         const bool had = ctx->have_theta;
-        ctx->lml_cache = false;         // (the arena is the call's own, but the contract is gpry_loo_objective's)
         const int r = objective_batch_general(ctx, bc, thetas, B, want_grad, value, grad, info);
         if (r <= 0) {
-            if (had && ctx->factor_valid) ctx->xs_foreign = true;       // as the single call leaves it
+            note_xs_foreign(ctx, had);                                  // (the arena is the call's own: as the single call leaves it)
             if (r < 0) (void)hipStreamSynchronize(ctx->stream);         // nothing of this call stays in flight
             return r;
         }                               // 1: no room for two scratch sets, one after another below

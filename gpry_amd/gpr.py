@@ -687,105 +687,83 @@ class GaussianProcessRegressor(_RM, _BE):
         raise NotImplementedError("This function is outdated and needs review.")
 
     # ---- marginal likelihood and fit ------------------------------------------------------
-    def log_marginal_likelihood(self, theta=None, eval_gradient=False, clone_kernel=True):
-        """Device evaluation of sklearn:_gpr.py:574-652 (counted as gpry/gpr.py:876-881)."""
-        self.n_eval_loglike += 1
-        if theta is None:
-            if eval_gradient:
-                raise ValueError("Gradient can only be evaluated for theta!=None")
-            return self.log_marginal_likelihood_value_
-        theta = np.asarray(theta, dtype=float)
+    def _at_theta(self, theta, clone_kernel=True):
+        """The preparation of every objective evaluation: ``(kernel, theta_full, dev)``.  The kernel at ``theta`` (its own
+        entries; None: as it is) -- a clone, or with ``clone_kernel=False`` ``kernel_`` itself, set to theta as the
+        reference does, which invalidates the factor; the device's vector ``[log C, log l_1 .. l_d (, log w)]``; the
+        device, with the training set on it."""
         kernel = self.kernel_ if self.kernel_ is not None else clone(self.kernel)
-        fast = hasattr(kernel, "set_theta_and_full")
-        if clone_kernel:
+        if theta is None:
+            kid, theta_full = kernel.device_spec(self.d)
+        elif clone_kernel:
             kernel = kernel.clone_with_theta(theta)
             kid, theta_full = kernel.device_spec(self.d)
         else:
             if self.kernel_ is None:
                 self.kernel_ = kernel
-            if fast:                      # same side effect as the reference: kernel_.theta = theta
+            if hasattr(kernel, "set_theta_and_full"):       # same side effect as the reference: kernel_.theta = theta
                 kid, theta_full = kernel.set_theta_and_full(theta, self.d)
             else:
                 kernel.theta = theta
                 kid, theta_full = kernel.device_spec(self.d)
-            self._dev_factor_ok = False
-            self._host_factor = {}
-            self._kb = None
+            self._invalidate()
         if not self._dev_train_ok:
             self._upload_train()
         dev = self._dev if self._dev is not None else self.device
         if dev.N != len(self.y_train_):
             raise RuntimeError("device training set out of sync")
-        if eval_gradient and getattr(self, "_seq_fit_tp", False):
+        return kernel, theta_full, dev
+
+    def _objective(self, call, fitted, theta, eval_gradient, clone_kernel):
+        """A fit objective at ``theta``: ``call`` names the device method, ``fitted`` the attribute that holds the value
+        at the fitted theta (``theta=None``).  Counted as gpry/gpr.py:876-881."""
+        self.n_eval_loglike += 1
+        if theta is None:
+            if eval_gradient:
+                raise ValueError("Gradient can only be evaluated for theta!=None")
+            return getattr(self, fitted)
+        theta = np.asarray(theta, dtype=float)
+        kernel, theta_full, dev = self._at_theta(theta, clone_kernel)
+        if not eval_gradient:
+            value, _ = getattr(dev, call)(theta_full, False)
+            return value if np.isfinite(value) else -np.inf
+        if call == "lml" and getattr(self, "_seq_fit_tp", False):
             # a sequential fit under the throughput schedule (the comparator of the side-by-side fit, fit_gpr_hyperparameters):
             # the chain of the many for ONE theta -- the bits a theta has in any batch of that schedule
             lb, gb, _ = dev.lml_batch(np.asarray(theta_full, dtype=float)[None, :], True)
-            lml, grad_full = float(lb[0]), gb[0]
-            if not np.isfinite(lml):
-                return -np.inf, np.zeros_like(theta)
-            return lml, (kernel.grad_from_full_fast(grad_full, self.d) if fast else kernel.grad_from_full(grad_full, self.d))
-        if eval_gradient:
-            lml, grad_full, _ = dev.lml(theta_full, True)
-            if not np.isfinite(lml):
-                return -np.inf, np.zeros_like(theta)
-            return lml, (kernel.grad_from_full_fast(grad_full, self.d) if fast else kernel.grad_from_full(grad_full, self.d))
-        lml, _ = dev.lml(theta_full, False)
-        return lml if np.isfinite(lml) else -np.inf
+            value, grad_full = float(lb[0]), gb[0]
+        else:
+            value, grad_full, _ = getattr(dev, call)(theta_full, True)
+        if not np.isfinite(value):
+            return -np.inf, np.zeros_like(theta)
+        if hasattr(kernel, "set_theta_and_full"):
+            return value, kernel.grad_from_full_fast(grad_full, self.d)
+        return value, kernel.grad_from_full(grad_full, self.d)
+
+    def log_marginal_likelihood(self, theta=None, eval_gradient=False, clone_kernel=True):
+        """Device evaluation of sklearn:_gpr.py:574-652 (``gpry_lml``).  ``theta=None``: the value at the fitted theta,
+        ``log_marginal_likelihood_value_``."""
+        return self._objective("lml", "log_marginal_likelihood_value_", theta, eval_gradient, clone_kernel)
 
     def loo_log_predictive(self, theta=None, eval_gradient=False, clone_kernel=True):
         """The leave-one-out log predictive density of the training targets (Rasmussen & Williams 5.4.2), transformed
         units, on the device (``gpry_loo_objective``): the twin of ``log_marginal_likelihood`` -- same kernel handling,
         same mapping of theta and gradient (a ``WhiteKernel`` in either operand order), ``(-inf, zeros)`` where the
         matrix is not positive definite.  ``theta=None``: the value at the fitted theta, ``loo_value_``."""
-        self.n_eval_loglike += 1
-        if theta is None:
-            if eval_gradient:
-                raise ValueError("Gradient can only be evaluated for theta!=None")
-            return self.loo_value_
-        theta = np.asarray(theta, dtype=float)
-        kernel = self.kernel_ if self.kernel_ is not None else clone(self.kernel)
-        fast = hasattr(kernel, "set_theta_and_full")
-        if clone_kernel:
-            kernel = kernel.clone_with_theta(theta)
-            kid, theta_full = kernel.device_spec(self.d)
-        else:
-            if self.kernel_ is None:
-                self.kernel_ = kernel
-            if fast:                      # same side effect as the reference: kernel_.theta = theta
-                kid, theta_full = kernel.set_theta_and_full(theta, self.d)
-            else:
-                kernel.theta = theta
-                kid, theta_full = kernel.device_spec(self.d)
-            self._dev_factor_ok = False
-            self._host_factor = {}
-            self._kb = None
-        if not self._dev_train_ok:
-            self._upload_train()
-        dev = self._dev if self._dev is not None else self.device
-        if dev.N != len(self.y_train_):
-            raise RuntimeError("device training set out of sync")
-        if eval_gradient:
-            val, grad_full, _ = dev.loo_objective(theta_full, True)
-            if not np.isfinite(val):
-                return -np.inf, np.zeros_like(theta)
-            return val, (kernel.grad_from_full_fast(grad_full, self.d) if fast else kernel.grad_from_full(grad_full, self.d))
-        val, _ = dev.loo_objective(theta_full, False)
-        return val if np.isfinite(val) else -np.inf
+        return self._objective("loo_objective", "loo_value_", theta, eval_gradient, clone_kernel)
 
     def _lml_hessian_full(self, theta=None):
         """``(kernel, theta_full, result)``: the device call of ``lml_hessian`` in the device's own vector
         ``[log C, log l_1 .. l_d (, log w)]``; theta in the kernel's entries, None: ``kernel_.theta``."""
         self.n_eval_loglike += 1
-        kernel = self.kernel_ if self.kernel_ is not None else clone(self.kernel)
-        if theta is not None:
-            kernel = kernel.clone_with_theta(np.asarray(theta, dtype=float))
-        kid, theta_full = kernel.device_spec(self.d)
-        if not self._dev_train_ok:
-            self._upload_train()
-        dev = self._dev if self._dev is not None else self.device
-        if dev.N != len(self.y_train_):
-            raise RuntimeError("device training set out of sync")
+        kernel, theta_full, dev = self._at_theta(None if theta is None else np.asarray(theta, dtype=float))
         return kernel, np.asarray(theta_full, dtype=float), dev.lml_hessian(theta_full)
+
+    def _grad_map(self, kernel, p):
+        """The matrix of ``kernel.grad_from_full``, which is linear, on the device's vector of p entries, column by
+        column; None where theta is that vector itself: nothing to map."""
+        M = np.stack([kernel.grad_from_full(e, self.d) for e in np.eye(p)], axis=1)
+        return None if M.shape[0] == p and np.array_equal(M, np.eye(p)) else M
 
     def lml_hessian(self, theta=None):
         """``(lml, grad, H)``: the log marginal likelihood, its gradient and its Hessian in theta, transformed units, on
@@ -795,13 +773,11 @@ class GaussianProcessRegressor(_RM, _BE):
         zeros)`` where the matrix is not positive definite.  ``theta=None``: at the fitted ``kernel_.theta``.  Counted in
         ``n_eval_loglike`` as one evaluation.  Models of more than 4096 padded rows are refused by the device."""
         kernel, theta_full, out = self._lml_hessian_full(theta)
-        p = len(theta_full)
-        # grad_from_full is linear: its matrix, column by column
-        M = np.stack([kernel.grad_from_full(e, self.d) for e in np.eye(p)], axis=1)
-        n = M.shape[0]
+        M = self._grad_map(kernel, len(theta_full))
+        n = len(theta_full) if M is None else M.shape[0]
         if not np.isfinite(out["lml"]):
             return -np.inf, np.zeros(n), np.zeros((n, n))
-        if n == p and np.array_equal(M, np.eye(p)):         # theta is the device's own vector: nothing to map
+        if M is None:
             return out["lml"], out["grad"], out["H"]
         H = M.dot(out["H"]).dot(M.T)
         return out["lml"], M.dot(out["grad"]), 0.5 * (H + H.T)
@@ -831,11 +807,8 @@ class GaussianProcessRegressor(_RM, _BE):
         G = out["G"]
         if full:
             return out["y"], G
-        p = G.shape[1]
-        M = np.stack([self.kernel_.grad_from_full(e, self.d) for e in np.eye(p)], axis=1)
-        if M.shape[0] == p and np.array_equal(M, np.eye(p)):
-            return out["y"], G
-        return out["y"], G.dot(M.T)
+        M = self._grad_map(self.kernel_, G.shape[1])
+        return out["y"], G if M is None else G.dot(M.T)
 
     def fit_gpr_hyperparameters(self, simple=False, start_from_current=True, n_restarts=None,
                                 hyperparameter_bounds=None, objective=None, side_by_side=None):

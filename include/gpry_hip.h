@@ -235,7 +235,8 @@ int gpry_append_rows(gpry_ctx* ctx, const double* Xnew_, const double* ynew_, co
  * *lml = -inf, grad = 0, *info > 0 (sklearn:_gpr.py:586-589).  Does not disturb the
  * factor held for prediction.  grad has 1+d entries (ignored if want_grad == 0).  For a model set with GPRY_KERNEL_WHITE
  * theta and grad have 2+d entries: theta[1+d] = log w, grad[1+d] = 1/2 w (alpha^T alpha - tr K^-1); the other entries are,
- * to the bit, those of the model without the flag whose alpha is alpha + w. */
+ * to the bit, those of the model without the flag whose alpha is alpha + w.  A call that fails behind its first launch
+ * returns after the stream has drained, as gpry_loo_objective and gpry_lml_hessian do: nothing of it stays in flight. */
 int gpry_lml(gpry_ctx* ctx, const double* theta, int want_grad, double* lml,
              double* grad, int* info);
 

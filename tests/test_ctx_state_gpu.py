@@ -75,6 +75,8 @@ def test_every_op_is_bit_repeatable_on_a_fresh_context(ops, fresh, model):
     case = MODELS[model]
     lml, grad, info = first["lml_nonpd"]
     assert lml == -np.inf and not grad.any() and info > 0, "lml_nonpd is meant to meet a matrix that is not positive definite"
+    value, grad, info = first["loo_objective_nonpd"]
+    assert value == -np.inf and not grad.any() and info > 0, "loo_objective_nonpd is meant to meet a matrix that is not positive definite"
     for o in ops[0]:
         if o.name in NOT_BIT_REPEATABLE:
             assert cs.close_enough(again[o.name], first[o.name], TOLERANT[o.name]), o.name

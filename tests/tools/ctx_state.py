@@ -287,6 +287,27 @@ def _(dev, case):
         return dev.lml_batch(_thetas(case), True)
 
 
+# -- the evaluations at a theta that is not the model's own which came after gpry_lml: each borrows the scratch factor
+@op("loo_objective", "loo_objective")
+def _(dev, case):
+    return dev.loo_objective(case.theta_other(1), True), dev.loo_objective(case.theta_other(1), False)
+
+
+@op("loo_objective_nonpd", "loo_objective")
+def _(dev, case):
+    return dev.loo_objective(case.theta_nonpd(), True)
+
+
+@op("loo_objective_batch", "loo_objective_batch")
+def _(dev, case):
+    return dev.loo_objective_batch(_thetas(case), True)
+
+
+@op("lml_hessian", "lml_hessian")
+def _(dev, case):
+    return dev.lml_hessian(case.theta_other(1))
+
+
 @op("kernel_cross", "kernel_cross")
 def _(dev, case):
     u = case.rng("kernel_cross").uniform(size=(37, case.d))
