@@ -1,0 +1,212 @@
+// gpry_predict_thetas: the posterior mean at M points under B thetas in one call, without touching the model the context
+// holds.  For theta b = [log C, log l_1 .. l_d (, log w)] and point x_i (raw coordinates where the affine map has an
+// x-affine):
+//   mean[b, i] = y_mean + y_std k_b(x_i)^T alpha_b,    alpha_b = (C_b phi_b + diag(noise + w_b))^-1 y_
+// the unclipped, ungated mean in untransformed units (the quantity gpry_mean_theta_grad differentiates), and with it
+// lml[b] and info[b] as gpry_lml(theta_b, want_grad = 0) returns them.  What hyper_spread(exact=True) of gpry_amd/hyper.py
+// is made of: the exact reweighting of a Monte Carlo sample under draws of theta, one refactorisation per draw.
+//
+// Route: the thetas go through gpry_lml's value-only chain (lml_chain: build_factor, solve_alpha, logdet_and_quad) with all
+// thetas of a chunk in grid.z (objective_batch_general, api.hip, always in the latency schedule), each theta in a scratch
+// set of its own; predict_thetas_kernel then reads every set's scaled training rows, alpha_ and parameter row while the
+// chunk is resident.  Where the batched chain is not available (Np above option "lml_batch", the rocSOLVER comparator,
+// fewer than two sets fit, one theta, Np = 128) the thetas go one after another through the same chain in the context's
+// own scratch, followed by the same kernel: the same bits.
+//
+// predict_thetas_kernel, grid (ceil(points / 4), 1, thetas), 256 threads: one workgroup evaluates four points of one theta
+// with ns_eval_multi (ns_common.h), i.e. with mean_slice's arithmetic operation for operation -- the slices of the
+// one-point path, the two scaled coordinates per lane ((x - lo) / span / l), the xor-shuffle sum of r^2, phase 2's groups
+// (v0 + v1) + (v2 + v3), the one-barrier tree, the finish ns_rn(mu y_std) + y_mean -- on the theta's own scaled rows, alpha_
+// and [C, l...] row, with the clip at +inf and no gates.  Every training row and alpha_ is loaded once per four points.
+// A value therefore has the bits gpry_predict(x[None]) has on a context factorised at that theta with the clip off and
+// no gates, and every summation order is a function of N alone: the bits of mean[b, i] depend on the model, theta_b and
+// x_i, never on B, M, positions, chunking, the route or option "lml_batch_mb".  (A form with one point per lane, the
+// training rows broadcast from LDS and one running sum per point runs the points four to five times as fast and was
+// measured; its sums have another order than every other mean of this library, and where two weights of opposite sign
+// and size 500 meet -- duplicated training rows -- it differs from them by 3e-13 of the mean.  It was not kept.)
+#include "ns_common.h"
+
+#define PT_R 4              // points per workgroup
+#define PT_CHUNK 65536      // points per launch
+#define PT_MAXB 96          // thetas per chain at the most (objective_batch_general's chunk)
+
+template <int DP, int KID>
+__global__ __launch_bounds__(256) void predict_thetas_kernel(NsArgs a, KernParams kp, AffParams ap, const double* __restrict__ bpar,
+                                                             int64_t bstride, const double* __restrict__ X, int64_t npts,
+                                                             double* __restrict__ out, int64_t ldo) {
+    __shared__ double r2s[PT_R * MEAN_MULTI_CH];
+    __shared__ double s_x[PT_R * GPRY_MAX_DIM];
+    __shared__ double s_y[PT_R];
+    __shared__ AffParams s_ap;
+    // batched launch (gpry_ctx::bn): the buffers and the parameter row of theta blockIdx.z
+    const int z = (int)blockIdx.z, t = threadIdx.x, d = kp.d;
+    a.Xs = bset(a.Xs, z, bstride);
+    a.alpha_ = bset(a.alpha_, z, bstride);
+    const double* __restrict__ par = bpar ? bset(bpar, z, bstride) : nullptr;
+    if (par) kp.C = par[0];
+    if (t < GPRY_MAX_DIM) {
+        s_ap.ls[t] = par ? par[1 + t] : ap.ls[t];          // (unused slots of a parameter row are 1, as make_ap's)
+        s_ap.lo[t] = ap.lo[t]; s_ap.span[t] = ap.span[t];
+    }
+    const int64_t p0 = (int64_t)blockIdx.x * PT_R;
+    if (t < PT_R * GPRY_MAX_DIM) {
+        const int p = t / GPRY_MAX_DIM, k = t - p * GPRY_MAX_DIM;
+        s_x[t] = (p0 + p < npts && k < d) ? X[(p0 + p) * d + k] : 0.0;
+    }
+    __syncthreads();
+    unsigned mask = 0;
+#pragma unroll
+    for (int p = 0; p < PT_R; p++) mask |= p0 + p < npts ? 1u << p : 0u;
+    double y[PT_R];
+#pragma unroll
+    for (int p = 0; p < PT_R; p++) y[p] = 0.0;
+    ns_eval_multi<DP, KID, PT_R>(s_x, mask, a, kp, s_ap, r2s, s_y, y);
+    if (t == 0) {
+#pragma unroll
+        for (int p = 0; p < PT_R; p++)
+            if (mask >> p & 1u) out[(int64_t)z * ldo + p0 + p] = y[p];
+    }
+}
+
+namespace {
+
+// the call in flight: the chain below is handed to objective_batch_general as a plain function and finds the points, the
+// output and how far the thetas have come here
+struct PtCall {
+    const double* dX = nullptr;     // the M x d points on the device
+    double* dout = nullptr;         // PT_MAXB x ldo means of the chunk in flight
+    int64_t M = 0, ldo = 0;
+    double* mean = nullptr;         // the caller's B x M
+    int64_t done = 0;               // thetas whose rows have been queued
+};
+thread_local PtCall* g_pt = nullptr;
+
+// gpry_lml's value-only chain, then the means of the ctx->bn thetas it served at all points, chunk of points by chunk
+int pt_chain(gpry_ctx* ctx, int /*want_grad*/, double* dres) {
+    PtCall* c = g_pt;
+    if (!c) return gpry_fail(ctx, -1, "predict_thetas: no call in flight");
+    if (ctx->bn > PT_MAXB) return gpry_fail(ctx, -1, "predict_thetas: %d thetas in one chain, the output holds %d", ctx->bn, PT_MAXB);
+    GPRY_TRY(lml_chain(ctx, 0, dres));
+    const KernParams kp = make_kp(ctx);
+    const AffParams ap = make_ap(ctx, kp.has_aff);
+    const int d = ctx->d;
+    // ns_args' slices of the one-point path -- without its ensure_pred_xs: the rows here are the chain's own
+    NsArgs a = {};
+    a.Xs = ctx->dXs; a.alpha_ = ctx->dvec + ctx->Np;         // alpha_ of the chain
+    a.nsplit = (int)(ctx->N / 1024);
+    if (a.nsplit < 1) a.nsplit = 1;
+    if (a.nsplit > 8) a.nsplit = 8;
+    a.rows_per_split = round_up((ctx->N + a.nsplit - 1) / a.nsplit, 32);
+    a.gates = 0;
+    a.y_std = ctx->tf.y_std; a.y_mean = ctx->tf.y_mean; a.clip_hi = INFINITY;
+    for (int k = 0; k < GPRY_MAX_DIM; k++) a.hi[k] = 1.0;
+    for (int64_t c0 = 0; c0 < c->M; c0 += PT_CHUNK) {
+        const int64_t n = c->M - c0 < PT_CHUNK ? c->M - c0 : PT_CHUNK;
+        {
+            StageScope s(ctx, "predict_thetas_mean");
+            const dim3 grid((unsigned)((n + PT_R - 1) / PT_R), 1, (unsigned)ctx->bn);
+#define PT(DP, KID) \
+    hipLaunchKernelGGL((predict_thetas_kernel<DP, KID>), grid, dim3(256), 0, ctx->stream, a, kp, ap, ctx->bpar, ctx->bstride, \
+                       c->dX + c0 * d, n, c->dout, c->ldo)
+            DISPATCH_DP_KID(d, ctx->kernel_id, PT)
+#undef PT
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        HIP_TRY(ctx, hipMemcpy2DAsync(c->mean + c->done * c->M + c0, sizeof(double) * c->M, c->dout, sizeof(double) * c->ldo,
+                                      sizeof(double) * n, (size_t)ctx->bn, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    c->done += ctx->bn;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* lml,
+                        int* info, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_predict_thetas: ctx is NULL");
+    if (!thetas || !X || !mean) return gpry_fail(ctx, -1, "predict_thetas: thetas, X and mean must not be NULL");
+    if (B < 1 || M < 1) return gpry_fail(ctx, -1, "predict_thetas: B = %lld thetas, M = %lld points", (long long)B, (long long)M);
+    if (ctx->N > 0 && !ctx->have_theta) return gpry_fail(ctx, -1, "predict_thetas: no kernel id (call gpry_set_theta)");
+    GPRY_TRY(objective_entry(ctx, "predict_thetas", thetas, B));
+    const int d = ctx->d, w = ctx_ntheta(ctx);
+    for (int64_t e = 0; e < M * d; e++)
+        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "predict_thetas: a coordinate of point %lld is not finite", (long long)(e / d));
+    if (ctx->tf.has_x_affine)
+        for (int k = 0; k < d; k++)
+            if (!(ctx->tf.x_span[k] != 0.0) || !isfinite(ctx->tf.x_span[k]) || !isfinite(ctx->tf.x_lo[k]))
+                return gpry_fail(ctx, -1, "predict_thetas: affine map of X: span %g, offset %g in dimension %d", ctx->tf.x_span[k],
+                                 ctx->tf.x_lo[k], k);
+    std::vector<double> vlml((size_t)B, 0.0);
+    std::vector<int> vinfo((size_t)B, 0);
+
+    // the points, once per call, and the means of one chunk of thetas and points: the samplers' staging buffer
+    PtCall call;
+    call.M = M; call.ldo = M < PT_CHUNK ? M : PT_CHUNK; call.mean = mean;
+    const int64_t xbytes = round_up((int64_t)sizeof(double) * M * d, 256);
+    const int64_t maxb = B < PT_MAXB ? B : PT_MAXB;
+    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, xbytes + (int64_t)sizeof(double) * maxb * call.ldo));
+    call.dX = reinterpret_cast<const double*>(ctx->dmc);
+    call.dout = reinterpret_cast<double*>(ctx->dmc + xbytes);
+    NsTimer tm;
+    GPRY_TRY(ns_begin(ctx, &tm));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dmc, X, sizeof(double) * M * d, hipMemcpyHostToDevice, ctx->stream));
+    struct CallGuard {
+        explicit CallGuard(PtCall* c) { g_pt = c; }
+        ~CallGuard() { g_pt = nullptr; }
+    } guard(&call);
+
+    bool batched = false;
+    if (B >= 2 && ctx->Np > 128 && ctx->Np <= ctx->opt_lml_batch && ctx->opt_chol == 0) {
+        const BatchChain bc = {"predict_thetas", pt_chain, true, 0, 0, 2, LML_RES_INFO, lml_head};
+        const bool had = ctx->have_theta;
+        const int r = objective_batch_general(ctx, bc, thetas, B, 0, vlml.data(), nullptr, vinfo.data());
+        if (r <= 0) note_xs_foreign(ctx, had);              // (the arena is the call's own: as a single evaluation leaves it)
+        if (r < 0) { (void)hipStreamSynchronize(ctx->stream); return r; }      // nothing of this call stays in flight
+        batched = r == 0;                                   // 1: no room for two scratch sets, one after another below
+    }
+    if (!batched) {
+        call.done = 0;
+        for (int64_t b = 0; b < B; b++) {
+            const double* theta = thetas + b * w;
+            ThetaScope at(ctx, theta);
+            // Np = 128, d <= 16: gpry_lml answers from its single-launch form, which leaves no alpha_ behind -- the value
+            // comes from there (its bits), the mean from the general chain at 128 padded rows
+            bool fused = false;
+            double fhost[2 + GPRY_THETA_MAX];
+            int finf = 0;
+            if (ctx->Np == 128 && ctx->opt_lml_small && ctx->opt_chol == 0) {
+                StageScope s(ctx, "lml_small");
+                const int r = launch_lml_small(ctx, 0, fhost, &finf);
+                if (r < 0) return r;
+                fused = r == 0;
+            }
+            double *hres, *dres;
+            GPRY_TRY(objective_row(ctx, 4096, LML_RES_INFO, &hres, &dres));
+            int rc, inf = 0;
+            {
+                StageScope s(ctx, "predict_thetas");
+                rc = pt_chain(ctx, 0, dres);
+            }
+            at.factor_chain_ran();
+            GPRY_TRY(objective_wait(ctx, "predict_thetas", rc, hres, LML_RES_INFO, &inf));
+            if (fused && finf != 0) inf = finf;
+            vinfo[(size_t)b] = inf;
+            objective_write(ctx, inf, lml_head(fused ? fhost : hres), nullptr, nullptr, &vlml[(size_t)b], nullptr, nullptr);
+        }
+    }
+    double ms = 0.0;
+    GPRY_TRY(ns_end(ctx, &tm, &ms));
+    // a theta whose matrix is not positive definite: a row of NaN, on its own
+    for (int64_t b = 0; b < B; b++) {
+        if (vinfo[(size_t)b] != 0)
+            for (int64_t i = 0; i < M; i++) mean[b * M + i] = NAN;
+        if (lml) lml[b] = vlml[(size_t)b];
+        if (info) info[b] = vinfo[(size_t)b];
+    }
+    if (device_ms) *device_ms = ms;
+    return 0;
+}
+
+}  // extern "C"

@@ -810,6 +810,50 @@ class GaussianProcessRegressor(_RM, _BE):
         M = self._grad_map(self.kernel_, G.shape[1])
         return out["y"], G if M is None else G.dot(M.T)
 
+    def predict_thetas(self, X, thetas, validate=True, full=False):
+        """``(mean (B, M), lml (B,), info (B,))``: the posterior mean at the rows of ``X`` (M, d) under every row of
+        ``thetas`` (B, ...), one refactorisation per row, in one device call (``gpry_predict_thetas``) that leaves the
+        fitted model as it is: ``kernel_``, the fitted attributes and the factor are not changed.  The mean is the
+        UNCLIPPED, UNGATED one in untransformed units -- the quantity whose derivative ``mean_theta_grad`` returns -- and
+        ``lml`` the log marginal likelihood at the row (transformed units, the bits of the device's ``lml``).  A row
+        whose matrix is not positive definite has ``info > 0``, ``lml = -inf`` and NaN means; the other rows are not
+        affected.  ``full=False``: a row holds the entries of ``kernel_.theta`` and is mapped to the device's vector
+        through a clone of the kernel, as ``log_marginal_likelihood`` maps its theta (isotropic and fixed entries, a
+        ``WhiteKernel`` in either operand order); ``full=True``: the device's own vector
+        ``[log C, log l_1 .. l_d (, log w)]``.  All four kernels; any number of rows and points.  ``n_eval`` grows by
+        B M, ``n_eval_loglike`` by B."""
+        thetas = np.asarray(thetas, dtype=float)
+        if thetas.ndim > 2 or thetas.size == 0:
+            raise ValueError(f"predict_thetas: thetas of shape (B, n_theta) are needed, got {thetas.shape}")
+        thetas = np.atleast_2d(thetas)
+        if not np.all(np.isfinite(thetas)):
+            raise ValueError("predict_thetas: a theta entry is not finite")
+        if full:
+            rows = thetas
+        else:
+            kernel = self.kernel_ if self.kernel_ is not None else clone(self.kernel)
+            if thetas.shape[1] != len(kernel.theta):
+                raise ValueError(f"predict_thetas: the kernel has {len(kernel.theta)} entries of theta, the rows {thetas.shape[1]}")
+            rows = np.stack([np.asarray(kernel.clone_with_theta(th).device_spec(self.d)[1], dtype=float) for th in thetas])
+        out = self._predict_thetas_full(X, rows, validate)
+        return out["mean"], out["lml"], out["info"]
+
+    def _predict_thetas_full(self, X, rows, validate=True):
+        """The device call of ``predict_thetas`` with the rows in the device's own vector: its dict (``mean``, ``lml``,
+        ``info``, ``device_ms``)."""
+        from gpry_amd.mc import _push_model
+        X = np.ascontiguousarray(self._validate_X(np.atleast_2d(X), validate), dtype=float)
+        if X.ndim != 2 or X.shape[1] != self.d or len(X) == 0:
+            raise ValueError(f"predict_thetas: rows of dimension {self.d} are needed, got shape {X.shape}")
+        if self.X_train_ is None:
+            raise ValueError("predict_thetas needs a model with training data")
+        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=float)
+        _push_model(self, "predict_thetas")
+        out = self.device.predict_thetas(rows, X)
+        self.n_eval += rows.shape[0] * len(X)
+        self.n_eval_loglike += rows.shape[0]
+        return out
+
     def fit_gpr_hyperparameters(self, simple=False, start_from_current=True, n_restarts=None,
                                 hyperparameter_bounds=None, objective=None, side_by_side=None):
         """Maximise the marginal likelihood over theta (gpry/gpr.py:883-994): same restart

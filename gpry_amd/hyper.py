@@ -104,7 +104,21 @@ class HyperSpread:
     parameter), ``ess_min``.  ``sigma_theta`` (n_points,): sqrt(G cov G^T) per kept row, the part of the mean's error bar
     that comes from theta (times ``scale``).  ``max_abs_logr``: the largest |log r_si|, the reach of the linearisation --
     beyond about 1 the first order is only indicative.  ``keep`` (the indices of the rows that take part), ``n_points``,
-    ``device_ms``, ``seed``, ``scale``."""
+    ``device_ms``, ``seed``, ``scale``.
+
+    ``exact``: False for the first-order mode, in which the fields below are None.  With ``hyper_spread(..., exact=True)``
+    log r_si is the refactorised change of the mean, ``mean_s(x_i) - mean_0(x_i)`` from one ``predict_thetas`` call, and
+    everything above is computed from it by the same code, UNWEIGHTED over the draws as in the first-order mode, so that
+    the two stay comparable (``theta_logw`` is reported, not applied).  ``lml`` (n_draws,) and ``lml0``: the log marginal
+    likelihood at theta + dtheta_s and at theta.  ``failed`` (n_draws,) bool: the draws whose matrix was not positive
+    definite; they take no part in any summary and their per-draw entries are NaN.  ``sigma_theta_draws`` (n_points,):
+    the std over the surviving draws of ``mean_s(x_i)``, the non-linear twin of ``sigma_theta`` (which stays the
+    linearised one).  ``first_order_miss``: the largest ``|log r_exact - G . dtheta|`` over the rows that take part and
+    the surviving draws -- how wrong the first-order mode would have been.  ``theta_logw`` (n_draws,):
+    ``lml_s - lml0 + dtheta_s^T cov^-1 dtheta_s / (2 scale^2)`` over the free entries, the log ratio of the marginal
+    likelihood to the Laplace Gaussian the draw came from (about 0 where Laplace is good; -inf for a draw that leaves the
+    kernel's bounds, ``HyperLaplace.bounds``, or failed).  ``theta_ess``: the Kish effective sample size of
+    ``exp(theta_logw)``."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -115,7 +129,7 @@ class HyperSpread:
                 f"ess_min={self.ess_min:.1f}, max_abs_logr={self.max_abs_logr:.3g})")
 
 
-def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=1.0):
+def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=1.0, exact=False):
     """How far the posterior moves because theta is only known as well as the data pin it: the Monte Carlo sample
     ``(X, y, w)`` that ``mc_sample_from_gp`` returned, reweighted to first order under ``n_draws`` draws
     dtheta_s ~ N(0, scale^2 cov) of the hyper-parameters, cov the Laplace covariance of ``hyper_laplace`` (``laplace``: a
@@ -129,7 +143,17 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
 
     Raises a ValueError when ``laplace.negdef`` is false (there is no covariance to draw from) or no entry is free.
     Warns when the smallest effective sample size is below 5 % of the rows.  Host memory is O(n_draws M + M d^2).
-    Returns a ``HyperSpread``."""
+    Returns a ``HyperSpread``.
+
+    ``exact=True``: the same draws from the same seed, but log r_si = mean_s(x_i) - mean_0(x_i) with the model
+    REFACTORISED at theta + dtheta_s -- one ``gpr.predict_thetas`` call (``gpry_predict_thetas``) with theta itself as its
+    first row, so that a draw that does not move theta has log r = 0 exactly; theta is ``laplace.theta``.  The fitted model
+    is not touched.  Everything downstream of log r is the code of the first-order mode, and the summaries stay UNWEIGHTED
+    over the draws, so that the two modes remain comparable: ``theta_logw`` says how far the Laplace Gaussian is from the
+    marginal likelihood at each draw and is not applied.  The first-order call is still made (it decides which rows the
+    gates reject, and ``first_order_miss`` compares the two).  A draw whose matrix is not positive definite is dropped
+    from every summary and flagged in ``failed``; a ValueError is raised when all fail.  See ``HyperSpread`` for the
+    fields this mode adds."""
     X = np.atleast_2d(np.asarray(X, dtype=float))
     y = np.asarray(y, dtype=float)
     n, d = X.shape
@@ -172,6 +196,35 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
     alive = np.isfinite(res["y"])                       # rows the gates reject take no part
     if not alive.any():
         raise ValueError("every row of the sample is rejected by the classifier or the trust region")
+    device_ms = res["device_ms"]
+    more = dict(exact=False, lml=None, lml0=None, failed=None, sigma_theta_draws=None, first_order_miss=None, theta_logw=None,
+                theta_ess=None)
+    ok = None                                           # exact mode: the draws that take part
+    if exact:
+        th0 = np.asarray(lap.theta, dtype=float)
+        pt = gpr._predict_thetas_full(Xk, np.vstack([th0[None, :], th0[None, :] + dtheta]))
+        if pt["info"][0] != 0:
+            raise ValueError("hyper_spread: the matrix at theta itself is not positive definite")
+        failed = np.asarray(pt["info"][1:]) != 0
+        if failed.all():
+            raise ValueError(f"hyper_spread: the matrix is not positive definite at any of the {n_draws} draws of theta")
+        ok = ~failed
+        mean_s = pt["mean"][1:][ok]
+        linear = logr[ok]
+        logr = mean_s - pt["mean"][0][None, :]
+        lml0, lml = float(pt["lml"][0]), np.asarray(pt["lml"][1:], dtype=float)
+        quad = 0.5 * np.einsum("sf,fg,sg->s", dtheta[:, free], np.linalg.inv(cov), dtheta[:, free]) / scale ** 2
+        bounds = np.asarray(lap.bounds, dtype=float)
+        th_s = th0[None, :] + dtheta
+        inside = np.all((th_s[:, free] >= bounds[free, 0]) & (th_s[:, free] <= bounds[free, 1]), axis=1)
+        with np.errstate(invalid="ignore"):
+            theta_logw = np.where(inside & ok, lml - lml0 + quad, -np.inf)
+        tw = np.exp(theta_logw - theta_logw.max()) if np.isfinite(theta_logw.max()) else np.zeros(n_draws)
+        more = dict(exact=True, lml=lml, lml0=lml0, failed=failed, sigma_theta_draws=mean_s.std(axis=0),
+                    first_order_miss=float(np.max(np.abs(logr[:, alive] - linear[:, alive]))), theta_logw=theta_logw,
+                    theta_ess=float(tw.sum() ** 2 / np.sum(tw * tw)) if tw.any() else 0.0)
+        device_ms = device_ms + pt["device_ms"]
+        del pt, mean_s, linear
     max_abs_logr = float(np.max(np.abs(logr[:, alive])))
     logr[:, ~alive] = -np.inf
     top = logr.max(axis=1)
@@ -181,8 +234,8 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
     ws = e / tot[:, None]
     ess = 1.0 / np.sum(ws * ws, axis=1)
     means = ws.dot(Xk)
-    covs = np.empty((n_draws, d, d))
-    for s in range(n_draws):                            # weighted Grams, one draw at a time: O(M d) beside ws
+    covs = np.empty((len(logr), d, d))
+    for s in range(len(logr)):                          # weighted Grams, one draw at a time: O(M d) beside ws
         cen = Xk - means[s]
         covs[s] = (cen * ws[s][:, None]).T.dot(cen)
     mean0 = wk.dot(Xk)
@@ -192,10 +245,17 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
     with np.errstate(divide="ignore", invalid="ignore"):
         mean_shift_sigma = means.std(axis=0) / np.sqrt(var0)
         cov_ratio_std = (np.einsum("saa->sa", covs) / var0).std(axis=0)
+    logZ_std, ess_min = float(dlogZ.std()), float(ess.min())
+    if ok is not None and not ok.all():                 # the per-draw arrays keep their length: NaN where the draw failed
+        def spread(a):
+            full = np.full((n_draws,) + a.shape[1:], np.nan)
+            full[ok] = a
+            return full
+        dlogZ, means, covs, ess = spread(dlogZ), spread(means), spread(covs), spread(ess)
     out = HyperSpread(dtheta=dtheta, dlogZ=dlogZ, means=means, covs=covs, ess=ess, mean0=mean0, cov0=cov0,
-                      logZ_std=float(dlogZ.std()), mean_shift_sigma=mean_shift_sigma, cov_ratio_std=cov_ratio_std,
-                      ess_min=float(ess.min()), sigma_theta=sigma_theta, max_abs_logr=max_abs_logr, keep=keep, n_points=m,
-                      device_ms=res["device_ms"], seed=seed, scale=scale)
+                      logZ_std=logZ_std, mean_shift_sigma=mean_shift_sigma, cov_ratio_std=cov_ratio_std,
+                      ess_min=ess_min, sigma_theta=sigma_theta, max_abs_logr=max_abs_logr, keep=keep, n_points=m,
+                      device_ms=device_ms, seed=seed, scale=scale, **more)
     if out.ess_min < 0.05 * m:
         warnings.warn(f"hyper_spread: the smallest effective sample size over the draws is {out.ess_min:.1f} of {m} "
                       "rows (< 5 %): the hyper-parameters are too uncertain for the reweighted sample to mean anything")

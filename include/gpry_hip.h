@@ -706,6 +706,38 @@ int gpry_lml_hessian(gpry_ctx* ctx, const double* theta, double* lml, double* gr
  * included. */
 int gpry_mean_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* y_out, double* G_out, double* device_ms);
 
+/* ---- The posterior mean at M points under B thetas, without touching the model the context holds (predict_thetas.hip;
+ * gpry_amd/gpr.py: predict_thetas, gpry_amd/hyper.py: hyper_spread(exact=True)).
+ * thetas: B rows of n_theta entries laid out as for gpry_lml_batch ([log C, log l_1 .. l_d], log w last with
+ * GPRY_KERNEL_WHITE; every row has its own w); the kernel family is the context's, as given to gpry_set_theta (all four
+ * ids).  X (M x d, raw coordinates where the affine map has an x-affine, as for gpry_mean_theta_grad).  B and M are
+ * unbounded: the thetas go through in chunks of scratch sets (the arena of gpry_lml_batch), the points in chunks of 65536.
+ *   mean (B x M, row-major)   mean[b M + i] = y_mean + y_std k_b(x_i)^T alpha_b, alpha_b = (C_b phi_b + diag(alpha + w_b))^-1 y_:
+ *                             the UNCLIPPED, UNGATED mean in untransformed units (what G_out of gpry_mean_theta_grad
+ *                             differentiates); a point so far away that k underflows gives exactly y_mean;
+ *   lml (B, nullable)         gpry_lml(theta_b, want_grad = 0), bit for bit;
+ *   info (B, nullable)        gpry_lml's convention: a theta whose matrix is not positive definite has info > 0, lml = -inf
+ *                             and a row of NaN in mean, on its own -- the other rows are unaffected.
+ * Up to the "lml_batch" limit one chain of launches (covariance build, factor, alpha_, log-determinant) carries all thetas
+ * of a chunk, each in a scratch set of its own, always in the latency schedule (option "lml_schedule" is not read); one
+ * kernel then evaluates every (theta, point) of the chunk, four points per workgroup.  Above the limit, with the rocSOLVER comparator, where fewer
+ * than two sets fit, with one theta and at 128 padded rows the thetas go one after another through the same chain and the
+ * same kernel in the context's own scratch.
+ * The bits of mean[b, i] and lml[b] depend on the model, theta_b and x_i alone: not on B, M, the row's or the point's
+ * position, how thetas or points are chunked or split over calls, the route, option "lml_batch_mb" or the context.  A
+ * point is evaluated with the arithmetic of gpry_predict's one-point path: mean[b, i] has the bits of gpry_predict(x_i[None])
+ * on a context factorised at theta_b with the clip off and no gates (gpry_predict's other paths have bits of their own).
+ * Refused (-1, with gpry_last_error) before anything runs: NULL thetas, X or mean; B < 1 or M < 1; no training set or no
+ * kernel id; a theta entry or a coordinate that is not finite; d > 32.  After a refusal the context answers the next call
+ * as before.
+ * State contract: that of gpry_lml_batch -- borrows the batch arena, the scratch of the objective and the samplers' staging
+ * buffer, disarms the factor cache of gpry_lml, stops the resident predict kernel first.  The prediction factor and the
+ * context's theta, a sweep, a Kriging-believer session, the gates, the buffers of gpry_loo and the scratch of
+ * gpry_mean_theta_grad are not touched.  Stage timers: "predict_thetas" (a chunk's chain), "predict_thetas_mean" (the
+ * point kernel).  device_ms (nullable): device time of the call, copies included. */
+int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* lml,
+                        int* info, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
