@@ -95,6 +95,7 @@ SIGNATURES = {
     "gpry_hessian_mean": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_mean_theta_grad": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_thetas": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_predict_thetas_var": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_cov": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_sample_joint": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_double, _vp, _vp, _vp, _vp,
                                     _P(C.c_int), _P(C.c_double), _P(C.c_double)]),
@@ -788,12 +789,14 @@ class Device:
         return out
 
     # -- the mean under a batch of thetas (gpry_amd/gpr.py: predict_thetas; gpry_amd/hyper.py: hyper_spread(exact=True)) ----
-    def predict_thetas(self, thetas, X):
+    def predict_thetas(self, thetas, X, want_var=False):
         """The unclipped, ungated posterior mean at the rows of ``X`` (M, d), raw coordinates, under every row of
         ``thetas`` (B, n_theta; the device's vector) in one call (gpry_predict_thetas): a dict with ``mean`` (B, M),
         ``lml`` (B,; the bits of ``lml(theta, False)``), ``info`` (B,) and ``device_ms``.  A theta whose matrix is not
         positive definite has ``info > 0``, ``lml = -inf`` and a row of NaN.  The model the context holds is not
-        disturbed.  Any number of thetas and points; all four kernels."""
+        disturbed.  Any number of thetas and points; all four kernels.  ``want_var=True`` (gpry_predict_thetas_var): the
+        dict has ``var`` (B, M) as well, the predictive variance ``y_std^2 (C_b + w_b - |V_b k_b(x)|^2)`` in untransformed
+        units, not clamped at 0; ``mean``, ``lml`` and ``info`` keep their bits."""
         thetas = self._theta_rows(thetas)
         X = _f64(X)
         if X.ndim != 2 or X.shape[1] != self.d:
@@ -801,8 +804,13 @@ class Device:
         B, M = thetas.shape[0], X.shape[0]
         out = dict(mean=np.empty((B, M)), lml=np.empty(B), info=np.zeros(B, dtype=np.int32))
         ms = C.c_double(0.0)
-        self._check(self._lib.gpry_predict_thetas(self._h, _ptr(thetas), B, _ptr(X), M, _ptr(out["mean"]), _ptr(out["lml"]),
-                                                  _ptr(out["info"]), C.byref(ms)), "gpry_predict_thetas")
+        if want_var:
+            out["var"] = np.empty((B, M))
+            self._check(self._lib.gpry_predict_thetas_var(self._h, _ptr(thetas), B, _ptr(X), M, _ptr(out["mean"]), _ptr(out["var"]),
+                                                          _ptr(out["lml"]), _ptr(out["info"]), C.byref(ms)), "gpry_predict_thetas_var")
+        else:
+            self._check(self._lib.gpry_predict_thetas(self._h, _ptr(thetas), B, _ptr(X), M, _ptr(out["mean"]), _ptr(out["lml"]),
+                                                      _ptr(out["info"]), C.byref(ms)), "gpry_predict_thetas")
         out["device_ms"] = ms.value
         return out
 

@@ -24,11 +24,34 @@
 // training rows broadcast from LDS and one running sum per point runs the points four to five times as fast and was
 // measured; its sums have another order than every other mean of this library, and where two weights of opposite sign
 // and size 500 meet -- duplicated training rows -- it differs from them by 3e-13 of the mean.  It was not kept.)
+//
+// gpry_predict_thetas_var: the same call with the predictive variance beside the mean,
+//   var[b, i] = y_std^2 ((C_b + w_b) - |V_b k_b(x_i)|^2),    V_b = L_b^-1,
+// not clamped at 0 (gpry_predict_cov's diagonal).  The value-only chain leaves V_b in the theta's second N x N piece
+// (solve_alpha needs it) and is finished with the third (T of the factor chain: every reader of it runs a chain of its
+// own first), so that piece takes the cross-kernel panel of pv_panel_points(Np) points and, behind it, the partial
+// sums.  Per panel of points, with the thetas of the chunk in grid.z:
+//   pt_var_panel_kernel     K*_b (Np rows x the panel's columns, padded to 64): C_b corr_r2_fast(r^2), r^2 one fma
+//                           chain over the coordinates in ascending order, the point scaled as the point kernel scales it
+//                           ((x - lo) / span / l); rows from N on and columns beyond the panel's points are exact zeros;
+//   gemm_f64_kernel         U = V_b K*_b by the project's FP64 MFMA engine (gemm_f64.hip) with KM_A_LOWER and the EPI_SUMSQ
+//                           epilogue, the product of the sweep's register-staged contraction (sweep.hip: contract_sweep), row-major tiles:
+//                           128 x 128 tiles, k ascending from 0 to the end of the row block's diagonal tile -- the tiles of V
+//                           above the diagonal are never visited -- and the column sums of squares taken in the epilogue
+//                           into one partial sum per row block and point; U never goes to HBM.  The engine takes the
+//                           theta from grid.z (gemm_fill_batch) and leaves a theta without a factor alone (info);
+//   pt_var_finish_kernel    the row blocks' partial sums added in ascending order, then y_std^2 ((C_b + w_b) - ss).
+// Each column of an MFMA tile is an accumulation chain of its own and every order above is a function of Np alone, so
+// the bits of var[b, i] depend on the model, theta_b and x_i, never on B, M, positions, the other points of the tile,
+// chunking, the route or option "lml_batch_mb"; a point whose k underflows gives y_std^2 (C_b + w_b) exactly.
 #include "ns_common.h"
 
 #define PT_R 4              // points per workgroup
 #define PT_CHUNK 65536      // points per launch
 #define PT_MAXB 96          // thetas per chain at the most (objective_batch_general's chunk)
+#define PV_BM 128           // rows of V per row block of the contraction (the engine's tile)
+#define PV_BN 64            // what a panel's columns are padded to (the panel kernel's tile; the engine guards its columns by eights)
+#define PV_LDX (GPRY_MAX_DIM + 1)
 
 template <int DP, int KID>
 __global__ __launch_bounds__(256) void predict_thetas_kernel(NsArgs a, KernParams kp, AffParams ap, const double* __restrict__ bpar,
@@ -68,6 +91,57 @@ __global__ __launch_bounds__(256) void predict_thetas_kernel(NsArgs a, KernParam
     }
 }
 
+template <int KID>
+__global__ __launch_bounds__(256) void pt_var_panel_kernel(const double* __restrict__ Xs_, int64_t N, int d, int dpad, int has_aff,
+                                                           AffParams ap, double C, const double* __restrict__ bpar, int64_t bstride,
+                                                           const double* __restrict__ X, int64_t npts, double* __restrict__ Kst_,
+                                                           int64_t ldk) {
+    __shared__ double s_p[PV_BN * PV_LDX];      // the tile's points, scaled
+    __shared__ double s_r[64 * PV_LDX];         // 64 scaled training rows
+    const int z = (int)blockIdx.z, t = threadIdx.x;
+    const double* __restrict__ Xs = bset(Xs_, z, bstride);
+    double* __restrict__ Kst = bset(Kst_, z, bstride);
+    const double* __restrict__ par = bpar ? bset(bpar, z, bstride) : nullptr;
+    if (par) C = par[0];
+    const int64_t c0 = (int64_t)blockIdx.x * PV_BN, r0 = (int64_t)blockIdx.y * 64;
+    for (int e = t; e < PV_BN * d; e += 256) {
+        const int p = e / d, k = e - p * d;
+        double v = 0.0;
+        if (c0 + p < npts) {
+            v = X[(c0 + p) * d + k];
+            if (has_aff) v = (v - ap.lo[k]) / ap.span[k];
+            v = v / (par ? par[1 + k] : ap.ls[k]);
+        }
+        s_p[p * PV_LDX + k] = v;
+        s_r[p * PV_LDX + k] = Xs[(r0 + p) * dpad + k];          // (r0 + p < Np: the grid covers the padded rows)
+    }
+    __syncthreads();
+    const int col = t & 63, rg = t >> 6;
+    for (int i = 0; i < 16; i++) {
+        const int row = rg * 16 + i;
+        double r2 = 0.0;
+        for (int k = 0; k < d; k++) {
+            const double df = s_p[col * PV_LDX + k] - s_r[row * PV_LDX + k];
+            r2 = fma(df, df, r2);
+        }
+        const double v = (r0 + row < N && c0 + col < npts) ? C * corr_r2_fast<KID>(r2) : 0.0;
+        Kst[(r0 + row) * ldk + c0 + col] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void pt_var_finish_kernel(const double* __restrict__ part_, int64_t ldk, int nrb, double prior,
+                                                            const double* __restrict__ bpar, int64_t bstride, double ys2, int64_t n,
+                                                            double* __restrict__ out, int64_t ldo) {
+    const int z = (int)blockIdx.z;
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    const double* __restrict__ part = bset(part_, z, bstride);
+    if (bpar) { const double* par = bset(bpar, z, bstride); prior = par[0] + par[GPRY_BPAR_WHITE]; }
+    double ss = 0.0;
+    for (int ti = 0; ti < nrb; ti++) ss += part[(int64_t)ti * ldk + c];
+    out[(int64_t)z * ldo + c] = ys2 * (prior - ss);
+}
+
 namespace {
 
 // the call in flight: the chain below is handed to objective_batch_general as a plain function and finds the points, the
@@ -77,9 +151,49 @@ struct PtCall {
     double* dout = nullptr;         // PT_MAXB x ldo means of the chunk in flight
     int64_t M = 0, ldo = 0;
     double* mean = nullptr;         // the caller's B x M
+    double* dvar = nullptr;         // PT_MAXB x ldo variances of the chunk in flight (NULL: the mean alone)
+    double* var = nullptr;          // the caller's B x M
     int64_t done = 0;               // thetas whose rows have been queued
 };
 thread_local PtCall* g_pt = nullptr;
+
+// points per panel: the third N x N piece of a scratch set holds the Np x pc panel and the Np / 128 x pc partial
+// sums behind it (a function of Np alone; 64 at Np = 128)
+int64_t pv_panel_points(int64_t Np) { return Np * Np / (Np + Np / PV_BM) / PV_BN * PV_BN; }
+
+// var of the ctx->bn thetas the chain has just served at points [c0, c0 + n) of the call, into c->dvar
+int pt_var_chunk(gpry_ctx* ctx, const PtCall* c, const KernParams& kp, const AffParams& ap, int64_t c0, int64_t n) {
+    StageScope s(ctx, "predict_thetas_var");
+    const int64_t Np = ctx->Np, pc = pv_panel_points(Np);
+    const int d = ctx->d, nrb = (int)(Np / PV_BM);
+    const unsigned bn = (unsigned)ctx->bn;
+    double* Kst = ctx->dW3;                 // free behind the value-only chain
+    double* part = ctx->dW3 + Np * pc;
+    const double ys2 = ctx->tf.y_std * ctx->tf.y_std;
+    for (int64_t p0 = 0; p0 < n; p0 += pc) {
+        const int64_t np = n - p0 < pc ? n - p0 : pc;
+        const unsigned nct = (unsigned)((np + PV_BN - 1) / PV_BN);
+#define PV(KID) \
+    hipLaunchKernelGGL((pt_var_panel_kernel<KID>), dim3(nct, (unsigned)(Np / 64), bn), dim3(256), 0, ctx->stream, ctx->dXs, ctx->N, d, \
+                       ctx->dpad, kp.has_aff, ap, kp.C, ctx->bpar, ctx->bstride, c->dX + (c0 + p0) * d, np, Kst, pc)
+        DISPATCH_KID(ctx->kernel_id, PV)
+#undef PV
+        {
+            StageScope sc(ctx, "predict_thetas_contract");
+            GemmArgs g = {};
+            g.A = ctx->dW2; g.lda = Np; g.B = Kst; g.ldb = pc; g.C = part; g.ldc = pc;
+            g.M = (int)Np; g.N = (int)(nct * PV_BN); g.K = (int)Np;
+            // (row-major tiles, as joint.hip's U = V K*^T: the sweep's super-tile map puts a panel of at most 64 tiles on one XCD)
+            g.kmode = KM_A_LOWER; g.tile_map = TM_ROWMAJOR;
+            g.info = ctx->dinfo;
+            GPRY_TRY(gemm_f64_launch(ctx, g, false, false, EPI_SUMSQ));
+        }
+        hipLaunchKernelGGL(pt_var_finish_kernel, dim3((unsigned)((np + 255) / 256), 1, bn), dim3(256), 0, ctx->stream, part, pc, nrb,
+                           ctx_prior_var(ctx), ctx->bpar, ctx->bstride, ys2, np, c->dvar + p0, c->ldo);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return 0;
+}
 
 // gpry_lml's value-only chain, then the means of the ctx->bn thetas it served at all points, chunk of points by chunk
 int pt_chain(gpry_ctx* ctx, int /*want_grad*/, double* dres) {
@@ -114,6 +228,11 @@ int pt_chain(gpry_ctx* ctx, int /*want_grad*/, double* dres) {
         }
         HIP_TRY(ctx, hipMemcpy2DAsync(c->mean + c->done * c->M + c0, sizeof(double) * c->M, c->dout, sizeof(double) * c->ldo,
                                       sizeof(double) * n, (size_t)ctx->bn, hipMemcpyDeviceToHost, ctx->stream));
+        if (c->dvar) {
+            GPRY_TRY(pt_var_chunk(ctx, c, kp, ap, c0, n));
+            HIP_TRY(ctx, hipMemcpy2DAsync(c->var + c->done * c->M + c0, sizeof(double) * c->M, c->dvar, sizeof(double) * c->ldo,
+                                          sizeof(double) * n, (size_t)ctx->bn, hipMemcpyDeviceToHost, ctx->stream));
+        }
     }
     c->done += ctx->bn;
     return 0;
@@ -121,11 +240,11 @@ int pt_chain(gpry_ctx* ctx, int /*want_grad*/, double* dres) {
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* lml,
-                        int* info, double* device_ms) {
-    if (!ctx) return gpry_fail(nullptr, -1, "gpry_predict_thetas: ctx is NULL");
+// both entry points: var == NULL is gpry_predict_thetas
+int pt_run(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* var, double* lml,
+           int* info, double* device_ms) {
     if (!thetas || !X || !mean) return gpry_fail(ctx, -1, "predict_thetas: thetas, X and mean must not be NULL");
     if (B < 1 || M < 1) return gpry_fail(ctx, -1, "predict_thetas: B = %lld thetas, M = %lld points", (long long)B, (long long)M);
     if (ctx->N > 0 && !ctx->have_theta) return gpry_fail(ctx, -1, "predict_thetas: no kernel id (call gpry_set_theta)");
@@ -143,12 +262,14 @@ int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const do
 
     // the points, once per call, and the means of one chunk of thetas and points: the samplers' staging buffer
     PtCall call;
-    call.M = M; call.ldo = M < PT_CHUNK ? M : PT_CHUNK; call.mean = mean;
+    call.M = M; call.ldo = M < PT_CHUNK ? M : PT_CHUNK; call.mean = mean; call.var = var;
     const int64_t xbytes = round_up((int64_t)sizeof(double) * M * d, 256);
     const int64_t maxb = B < PT_MAXB ? B : PT_MAXB;
-    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, xbytes + (int64_t)sizeof(double) * maxb * call.ldo));
+    const int64_t obytes = round_up((int64_t)sizeof(double) * maxb * call.ldo, 256);        // (used with var alone)
+    GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, var ? xbytes + 2 * obytes : xbytes + (int64_t)sizeof(double) * maxb * call.ldo));
     call.dX = reinterpret_cast<const double*>(ctx->dmc);
     call.dout = reinterpret_cast<double*>(ctx->dmc + xbytes);
+    if (var) call.dvar = reinterpret_cast<double*>(ctx->dmc + xbytes + obytes);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dmc, X, sizeof(double) * M * d, hipMemcpyHostToDevice, ctx->stream));
@@ -201,12 +322,31 @@ int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const do
     // a theta whose matrix is not positive definite: a row of NaN, on its own
     for (int64_t b = 0; b < B; b++) {
         if (vinfo[(size_t)b] != 0)
-            for (int64_t i = 0; i < M; i++) mean[b * M + i] = NAN;
+            for (int64_t i = 0; i < M; i++) {
+                mean[b * M + i] = NAN;
+                if (var) var[b * M + i] = NAN;
+            }
         if (lml) lml[b] = vlml[(size_t)b];
         if (info) info[b] = vinfo[(size_t)b];
     }
     if (device_ms) *device_ms = ms;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* lml,
+                        int* info, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_predict_thetas: ctx is NULL");
+    return pt_run(ctx, thetas, B, X, M, mean, nullptr, lml, info, device_ms);
+}
+
+int gpry_predict_thetas_var(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* var,
+                            double* lml, int* info, double* device_ms) {
+    if (!ctx) return gpry_fail(nullptr, -1, "gpry_predict_thetas_var: ctx is NULL");
+    return pt_run(ctx, thetas, B, X, M, mean, var, lml, info, device_ms);
 }
 
 }  // extern "C"

@@ -810,7 +810,7 @@ class GaussianProcessRegressor(_RM, _BE):
         M = self._grad_map(self.kernel_, G.shape[1])
         return out["y"], G if M is None else G.dot(M.T)
 
-    def predict_thetas(self, X, thetas, validate=True, full=False):
+    def predict_thetas(self, X, thetas, validate=True, full=False, return_std=False):
         """``(mean (B, M), lml (B,), info (B,))``: the posterior mean at the rows of ``X`` (M, d) under every row of
         ``thetas`` (B, ...), one refactorisation per row, in one device call (``gpry_predict_thetas``) that leaves the
         fitted model as it is: ``kernel_``, the fitted attributes and the factor are not changed.  The mean is the
@@ -821,7 +821,13 @@ class GaussianProcessRegressor(_RM, _BE):
         through a clone of the kernel, as ``log_marginal_likelihood`` maps its theta (isotropic and fixed entries, a
         ``WhiteKernel`` in either operand order); ``full=True``: the device's own vector
         ``[log C, log l_1 .. l_d (, log w)]``.  All four kernels; any number of rows and points.  ``n_eval`` grows by
-        B M, ``n_eval_loglike`` by B."""
+        B M, ``n_eval_loglike`` by B.
+
+        ``return_std=True``: ``(mean, std (B, M), lml, info)`` -- the predictive standard deviation under every row as
+        well, from the same call (``gpry_predict_thetas_var``): ``std = sqrt(max(var, 0))`` with
+        ``var = y_std^2 (C_b + w_b - |L_b^-1 k_b(x)|^2)`` in untransformed units, what ``predict(return_std=True)`` returns
+        at a model refitted to the row with the clip off (to rounding: the device's standard deviations have several
+        summation orders).  NaN in the rows with ``info > 0``.  ``mean``, ``lml`` and ``info`` keep their bits."""
         thetas = np.asarray(thetas, dtype=float)
         if thetas.ndim > 2 or thetas.size == 0:
             raise ValueError(f"predict_thetas: thetas of shape (B, n_theta) are needed, got {thetas.shape}")
@@ -835,12 +841,15 @@ class GaussianProcessRegressor(_RM, _BE):
             if thetas.shape[1] != len(kernel.theta):
                 raise ValueError(f"predict_thetas: the kernel has {len(kernel.theta)} entries of theta, the rows {thetas.shape[1]}")
             rows = np.stack([np.asarray(kernel.clone_with_theta(th).device_spec(self.d)[1], dtype=float) for th in thetas])
-        out = self._predict_thetas_full(X, rows, validate)
+        out = self._predict_thetas_full(X, rows, validate, want_var=bool(return_std))
+        if return_std:
+            with np.errstate(invalid="ignore"):
+                return out["mean"], np.sqrt(np.maximum(out["var"], 0.0)), out["lml"], out["info"]
         return out["mean"], out["lml"], out["info"]
 
-    def _predict_thetas_full(self, X, rows, validate=True):
+    def _predict_thetas_full(self, X, rows, validate=True, want_var=False):
         """The device call of ``predict_thetas`` with the rows in the device's own vector: its dict (``mean``, ``lml``,
-        ``info``, ``device_ms``)."""
+        ``info``, ``device_ms``, and with ``want_var`` the unclamped ``var``)."""
         from gpry_amd.mc import _push_model
         X = np.ascontiguousarray(self._validate_X(np.atleast_2d(X), validate), dtype=float)
         if X.ndim != 2 or X.shape[1] != self.d or len(X) == 0:
@@ -849,7 +858,7 @@ class GaussianProcessRegressor(_RM, _BE):
             raise ValueError("predict_thetas needs a model with training data")
         rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=float)
         _push_model(self, "predict_thetas")
-        out = self.device.predict_thetas(rows, X)
+        out = self.device.predict_thetas(rows, X, want_var=True) if want_var else self.device.predict_thetas(rows, X)
         self.n_eval += rows.shape[0] * len(X)
         self.n_eval_loglike += rows.shape[0]
         return out

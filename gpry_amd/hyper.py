@@ -3,7 +3,8 @@
 ``hyper_laplace(gpr)`` evaluates the log marginal likelihood, its gradient and its Hessian at theta in one device call
 (``gpry_lml_hessian``, closed form) and reads from them which entries the data pin and which are sloppy, how they are
 correlated, which are held by a bound, and the Laplace evidence of the kernel family.  A report: it warns of nothing,
-gates nothing and changes no fit.
+gates nothing and changes no fit.  ``hyper_spread`` carries the Gaussian's draws of theta to a Monte Carlo sample of the
+posterior, ``hyper_predict`` to the predictive mean and error bar at given points.
 """
 import warnings
 from collections import namedtuple
@@ -95,6 +96,49 @@ def hyper_laplace(gpr, theta=None):
                         device_s=out["device_ms"] / 1e3, wall_s=time() - t_start)
 
 
+def _theta_draws(gpr, who, n_draws, seed, laplace, scale):
+    """The draws of theta that ``hyper_spread`` and ``hyper_predict`` share: the argument checks, the Laplace report
+    (``laplace``; None: ``hyper_laplace(gpr)``) and ``dtheta`` (n_draws, p) ~ N(0, scale^2 cov) over the free entries from
+    ``np.random.default_rng(seed)`` through the Cholesky factor of cov, zero in the held entries.  Returns
+    ``(n_draws, seed, scale, lap, free, cov, dtheta)``."""
+    n_draws, scale = int(n_draws), float(scale)
+    if n_draws < 2:
+        raise ValueError(f"n_draws must be at least 2 (got {n_draws})")
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError(f"scale must be positive and finite (got {scale})")
+    if seed is None:
+        seed = int(np.random.default_rng().integers(2**63 - 1))
+    seed = int(seed)
+    lap = hyper_laplace(gpr) if laplace is None else laplace
+    if not lap.negdef or lap.cov is None:
+        raise ValueError(f"{who}: negdef is False -- minus the Hessian of the log marginal likelihood over the free "
+                         "entries is not positive definite, there is no covariance of theta to draw from")
+    free = np.asarray(lap.free, dtype=bool)
+    k = int(free.sum())
+    if k == 0:
+        raise ValueError(f"{who}: no entry of theta is free (all are fixed or held by a bound): nothing to draw")
+    cov = np.asarray(lap.cov, dtype=float)
+    dtheta = np.zeros((n_draws, len(free)))
+    dtheta[:, free] = scale * np.random.default_rng(seed).standard_normal((n_draws, k)).dot(np.linalg.cholesky(cov).T)
+    return n_draws, seed, scale, lap, free, cov, dtheta
+
+
+def _theta_weights(lap, free, cov, dtheta, scale, lml, lml0, ok):
+    """``(theta_logw, tw, theta_ess)`` of the draws: the log ratio of the marginal likelihood to the Laplace Gaussian the
+    draw came from, ``lml_s - lml0 + dtheta_s^T cov^-1 dtheta_s / (2 scale^2)`` over the free entries (-inf for a draw that
+    leaves ``lap.bounds`` or is not ``ok``), ``tw = exp(theta_logw - max)`` (zeros when no draw has a weight) and its Kish
+    effective sample size."""
+    th0 = np.asarray(lap.theta, dtype=float)
+    quad = 0.5 * np.einsum("sf,fg,sg->s", dtheta[:, free], np.linalg.inv(cov), dtheta[:, free]) / scale ** 2
+    bounds = np.asarray(lap.bounds, dtype=float)
+    th_s = th0[None, :] + dtheta
+    inside = np.all((th_s[:, free] >= bounds[free, 0]) & (th_s[:, free] <= bounds[free, 1]), axis=1)
+    with np.errstate(invalid="ignore"):
+        theta_logw = np.where(inside & ok, lml - lml0 + quad, -np.inf)
+    tw = np.exp(theta_logw - theta_logw.max()) if np.isfinite(theta_logw.max()) else np.zeros(len(dtheta))
+    return theta_logw, tw, float(tw.sum() ** 2 / np.sum(tw * tw)) if tw.any() else 0.0
+
+
 class HyperSpread:
     """What ``hyper_spread`` returns.  Per draw s (arrays of length ``n_draws``): ``dtheta`` (n_draws, p; the draw in the
     device's vector, zero in the held entries), ``dlogZ`` (the change of log Z), ``means`` (n_draws, d), ``covs``
@@ -160,22 +204,7 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
     w = np.full(n, 1.0 / max(n, 1)) if w is None else np.asarray(w, dtype=float)
     if y.shape != (n,) or w.shape != (n,):
         raise ValueError(f"expected y and w of shape ({n},), got {y.shape} and {w.shape}")
-    n_draws, scale = int(n_draws), float(scale)
-    if n_draws < 2:
-        raise ValueError(f"n_draws must be at least 2 (got {n_draws})")
-    if not (scale > 0.0 and np.isfinite(scale)):
-        raise ValueError(f"scale must be positive and finite (got {scale})")
-    if seed is None:
-        seed = int(np.random.default_rng().integers(2**63 - 1))
-    seed = int(seed)
-    lap = hyper_laplace(gpr) if laplace is None else laplace
-    if not lap.negdef or lap.cov is None:
-        raise ValueError("hyper_spread: negdef is False -- minus the Hessian of the log marginal likelihood over the free "
-                         "entries is not positive definite, there is no covariance of theta to draw from")
-    free = np.asarray(lap.free, dtype=bool)
-    k = int(free.sum())
-    if k == 0:
-        raise ValueError("hyper_spread: no entry of theta is free (all are fixed or held by a bound): nothing to draw")
+    n_draws, seed, scale, lap, free, cov, dtheta = _theta_draws(gpr, "hyper_spread", n_draws, seed, laplace, scale)
     keep = np.flatnonzero((w > 0) & np.isfinite(w) & np.isfinite(y))
     if len(keep) == 0:
         raise ValueError("the sample has no row of positive weight and finite y")
@@ -187,9 +216,6 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
     p = len(free)
     if G.shape != (m, p):
         raise ValueError(f"hyper_spread: the Laplace report has {p} entries of theta, the model {G.shape[1]}")
-    cov = np.asarray(lap.cov, dtype=float)
-    dtheta = np.zeros((n_draws, p))
-    dtheta[:, free] = scale * np.random.default_rng(seed).standard_normal((n_draws, k)).dot(np.linalg.cholesky(cov).T)
     Gf = G[:, free]
     sigma_theta = np.sqrt(np.maximum(np.einsum("if,fg,ig->i", Gf, cov, Gf), 0.0)) * scale
     logr = dtheta.dot(G.T)                              # (n_draws, m)
@@ -213,16 +239,10 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
         linear = logr[ok]
         logr = mean_s - pt["mean"][0][None, :]
         lml0, lml = float(pt["lml"][0]), np.asarray(pt["lml"][1:], dtype=float)
-        quad = 0.5 * np.einsum("sf,fg,sg->s", dtheta[:, free], np.linalg.inv(cov), dtheta[:, free]) / scale ** 2
-        bounds = np.asarray(lap.bounds, dtype=float)
-        th_s = th0[None, :] + dtheta
-        inside = np.all((th_s[:, free] >= bounds[free, 0]) & (th_s[:, free] <= bounds[free, 1]), axis=1)
-        with np.errstate(invalid="ignore"):
-            theta_logw = np.where(inside & ok, lml - lml0 + quad, -np.inf)
-        tw = np.exp(theta_logw - theta_logw.max()) if np.isfinite(theta_logw.max()) else np.zeros(n_draws)
+        theta_logw, _, theta_ess = _theta_weights(lap, free, cov, dtheta, scale, lml, lml0, ok)
         more = dict(exact=True, lml=lml, lml0=lml0, failed=failed, sigma_theta_draws=mean_s.std(axis=0),
                     first_order_miss=float(np.max(np.abs(logr[:, alive] - linear[:, alive]))), theta_logw=theta_logw,
-                    theta_ess=float(tw.sum() ** 2 / np.sum(tw * tw)) if tw.any() else 0.0)
+                    theta_ess=theta_ess)
         device_ms = device_ms + pt["device_ms"]
         del pt, mean_s, linear
     max_abs_logr = float(np.max(np.abs(logr[:, alive])))
@@ -260,3 +280,72 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
         warnings.warn(f"hyper_spread: the smallest effective sample size over the draws is {out.ess_min:.1f} of {m} "
                       "rows (< 5 %): the hyper-parameters are too uncertain for the reweighted sample to mean anything")
     return out
+
+
+class HyperPredict:
+    """What ``hyper_predict`` returns, at the M rows of X in untransformed units.  ``mean0``, ``sigma0`` (M,): mean and
+    sigma at the fitted theta (row 0 of the call: the unclipped mean and ``sqrt(max(var, 0))``).  Over the surviving draws
+    of theta: ``mean`` (the average of the draws' means), ``sigma_gp`` (the square root of the average of
+    ``max(var_s, 0)``: the GP's own error bar, averaged over theta), ``sigma_theta`` (the standard deviation of the draws'
+    means: what theta's uncertainty adds), ``sigma_total = sqrt(sigma_gp^2 + sigma_theta^2)`` (the law of total variance)
+    and ``inflation = sigma_total / sigma0`` (inf or NaN where sigma0 is 0).  Per draw s (length ``n_draws``, NaN where
+    the draw failed): ``dtheta`` (n_draws, p), ``means`` and ``vars`` (n_draws, M; the variance as the device returns it,
+    not clamped), ``lml``.  ``lml0``; ``failed`` (n_draws,) bool: the draws whose matrix was not positive definite, left
+    out of every summary; ``theta_logw`` (n_draws,) and ``theta_ess``: as in ``HyperSpread``.  ``weighted``: whether the
+    summaries use the self-normalised weights ``exp(theta_logw)``.  ``device_ms``, ``seed``, ``scale``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return (f"HyperPredict(n_points={len(self.mean0)}, n_draws={len(self.lml)}, failed={int(np.sum(self.failed))}, "
+                f"max inflation={np.nanmax(self.inflation):.3g}, theta_ess={self.theta_ess:.1f}, weighted={self.weighted})")
+
+
+def hyper_predict(gpr, X, n_draws=64, seed=None, laplace=None, scale=1.0, weighted=False):
+    """The predictive at the rows of ``X`` (M, d) with the hyper-parameters marginalised over the Laplace Gaussian of
+    ``hyper_laplace``: by the law of total variance the error bar at x is
+    ``E_theta[sigma^2(x | theta)] + Var_theta[mean(x | theta)]``.  The draws are ``hyper_spread``'s -- the same Gaussian
+    (``laplace``: a ``HyperLaplace``; None: ``hyper_laplace(gpr)``), the same seed convention, entries that are not free
+    held -- with the fitted theta (``laplace.theta``) in front as row 0 of ONE ``gpr.predict_thetas`` call
+    (``gpry_predict_thetas_var``: one refactorisation per draw, mean and variance of every draw at every point).  The
+    fitted model is not touched.  Returns a ``HyperPredict``.
+
+    The summaries are UNWEIGHTED over the draws by default, comparable with ``hyper_spread``; ``weighted=True`` applies
+    the self-normalised importance weights ``exp(theta_logw)`` (the marginal likelihood over the Laplace Gaussian, zero
+    for a draw outside the kernel's bounds), computed as in ``hyper_spread(exact=True)``.  A report: it changes no
+    default anywhere.  Raises a ValueError when there is no covariance to draw from, when the matrix at theta itself or
+    at every draw is not positive definite, or when ``weighted`` leaves no draw with a weight."""
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    n_draws, seed, scale, lap, free, cov, dtheta = _theta_draws(gpr, "hyper_predict", n_draws, seed, laplace, scale)
+    th0 = np.asarray(lap.theta, dtype=float)
+    pt = gpr._predict_thetas_full(X, np.vstack([th0[None, :], th0[None, :] + dtheta]), want_var=True)
+    if pt["info"][0] != 0:
+        raise ValueError("hyper_predict: the matrix at theta itself is not positive definite")
+    failed = np.asarray(pt["info"][1:]) != 0
+    if failed.all():
+        raise ValueError(f"hyper_predict: the matrix is not positive definite at any of the {n_draws} draws of theta")
+    ok = ~failed
+    means, vars_ = np.array(pt["mean"][1:], dtype=float), np.array(pt["var"][1:], dtype=float)
+    means[failed], vars_[failed] = np.nan, np.nan
+    lml0, lml = float(pt["lml"][0]), np.asarray(pt["lml"][1:], dtype=float)
+    theta_logw, tw, theta_ess = _theta_weights(lap, free, cov, dtheta, scale, lml, lml0, ok)
+    if weighted:
+        if not tw.any():
+            raise ValueError("hyper_predict: weighted=True and no draw of theta has a weight (all failed or left the bounds)")
+        wts = tw[ok] / tw[ok].sum()
+    else:
+        wts = np.full(int(ok.sum()), 1.0 / int(ok.sum()))
+    m_ok, v_ok = means[ok], np.maximum(vars_[ok], 0.0)
+    mean = wts.dot(m_ok)
+    sigma_gp = np.sqrt(wts.dot(v_ok))
+    sigma_theta = np.sqrt(wts.dot((m_ok - mean[None, :]) ** 2))
+    sigma_total = np.sqrt(sigma_gp ** 2 + sigma_theta ** 2)
+    mean0 = np.array(pt["mean"][0], dtype=float)
+    sigma0 = np.sqrt(np.maximum(pt["var"][0], 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inflation = sigma_total / sigma0
+    return HyperPredict(mean0=mean0, sigma0=sigma0, mean=mean, sigma_gp=sigma_gp, sigma_theta=sigma_theta,
+                        sigma_total=sigma_total, inflation=inflation, dtheta=dtheta, means=means, vars=vars_, lml=lml, lml0=lml0,
+                        failed=failed, theta_logw=theta_logw, theta_ess=theta_ess,
+                        weighted=bool(weighted), device_ms=pt["device_ms"], seed=seed, scale=scale)

@@ -738,6 +738,30 @@ int gpry_mean_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* y
 int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* lml,
                         int* info, double* device_ms);
 
+/* ---- ... and the predictive variance beside it: what the error bar at x is made of once theta is marginalised
+ * (predict_thetas.hip; gpry_amd/gpr.py: predict_thetas(return_std=True), gpry_amd/hyper.py: hyper_predict).
+ * gpry_predict_thetas with one more output; with var NULL it IS gpry_predict_thetas.
+ *   var (B x M, row-major, nullable)   var[b M + i] = y_std^2 (C_b + w_b - |V_b k_b(x_i)|^2), V_b = L_b^-1, w_b = 0 without a
+ *                             white term: the prior variance of a new point at theta_b minus what the data explain, in
+ *                             untransformed units.  NOT clamped at 0 -- rounding near a training point may leave a tiny
+ *                             negative number (the convention of gpry_predict_cov's diagonal).  A theta with info > 0 has a
+ *                             row of NaN, on its own; a point so far away that k underflows gives exactly y_std^2 (C_b + w_b).
+ * mean, lml and info come from the kernels of gpry_predict_thetas and have its bits.  Per panel of points (as many as
+ * fit, with their partial sums, into the third N x N piece of a theta's scratch set: about Np of them) three launches
+ * carry all thetas of the chunk: the cross-kernel panel K*_b, the lower-triangular product V_b K*_b by the FP64 MFMA
+ * engine of gemm_f64.hip with the column sums of squares taken in its epilogue (the product is never stored), and the
+ * finish.  The route that takes the thetas one after another makes the same launches for one theta.
+ * The bits of var[b, i] depend on the model, theta_b and x_i alone: not on B, M, the row's or the point's position, the
+ * other points, how thetas or points are chunked or split over calls, the route, option "lml_batch_mb" or the context.
+ * They are not the bits of any of gpry_predict's standard deviations (which differ among themselves).
+ * Entry checks, refusals and the state contract are those of gpry_predict_thetas; the only scratch beyond its own is that
+ * third piece of the scratch sets it borrows anyway, and as much again of the samplers' staging buffer.  Stage timers:
+ * those of gpry_predict_thetas, "predict_thetas_var" (the three kernels, per chunk of points) and, inside it,
+ * "predict_thetas_contract" (the matrix-pipe product alone, per panel; what tools/time_predict_thetas_var.py takes the
+ * contraction's rate from). */
+int gpry_predict_thetas_var(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* var,
+                            double* lml, int* info, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
