@@ -103,6 +103,7 @@ SIGNATURES = {
     "gpry_svm_fit": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int64, _vp,
                                _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int64), _P(C.c_int), _P(C.c_double)]),
     "gpry_leave_out": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_predict_without": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -895,12 +896,10 @@ class Device:
         return dict(alpha=alpha, rho=rho.value, objective=obj.value, violation=viol.value, n_iter=int(nit.value),
                     status=int(status.value), device_ms=ms.value)
 
-    def leave_out(self, groups):
-        """Joint predictive of every group of training targets from the points outside it (gpry_leave_out).  ``groups``: a
-        sequence of index sequences (1 to 64 distinct indices each; groups may overlap).  A dict with ``mean`` and ``cov``
-        (lists, one (n_g,) and one (n_g, n_g) array per group, in the order of the group's indices, units of y), ``chi2``,
-        ``logpdf`` and ``info`` (one per group; info != 0: the group's block of K^-1 was not positive definite and its
-        outputs are NaN), ``dof`` and ``device_ms``."""
+    @staticmethod
+    def _group_arrays(groups):
+        """A list of index sequences as gpry_leave_out and gpry_predict_without take it: ``(ngroups, sizes, offsets, idx,
+        ok)``; ``ok`` False: the library will refuse the list (none, an empty group or one above 64 indices)."""
         groups = [np.ascontiguousarray(g, dtype=np.int64).reshape(-1) for g in groups]
         ng = len(groups)
         sizes = np.array([len(g) for g in groups], dtype=np.int64)
@@ -908,6 +907,38 @@ class Device:
         np.cumsum(sizes, out=offsets[1:])
         idx = np.concatenate(groups) if ng else np.zeros(0, dtype=np.int64)
         ok = ng >= 1 and sizes.min() >= 1 and sizes.max() <= 64     # (the library refuses; no arrays for a refused request)
+        return ng, sizes, offsets, idx, bool(ok)
+
+    def predict_without(self, groups, X, want=("dmean", "dvar")):
+        """What the model would predict at the rows of ``X`` (M, d; raw coordinates) without each group of training points
+        (gpry_predict_without), as a change against the model it holds: a dict with ``dmean`` and ``dvar`` (ngroups, M;
+        the change of the unclipped, ungated mean and of the latent variance, units of y and y^2, ``dvar >= 0``; None
+        where ``want`` leaves one out), ``info`` (ngroups,; non-zero: the group's block of K^-1 is not positive definite
+        and its rows are NaN) and ``device_ms``.  ``groups`` as for ``leave_out``.  Same theta, y map and noise: nothing is
+        refactorised, and the model is not disturbed."""
+        ng, sizes, offsets, idx, ok = self._group_arrays(groups)
+        X = _f64(X)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError(f"expected points of shape (npts, {self.d}), got {X.shape}")
+        if not any(k in want for k in ("dmean", "dvar")):
+            raise ValueError("predict_without: want must name dmean or dvar")
+        M = X.shape[0]
+        shape = (ng, M) if ok and M >= 1 else (0, M)
+        out = {k: (np.empty(shape) if k in want else None) for k in ("dmean", "dvar")}
+        out["info"] = np.zeros(ng, dtype=np.int32)
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_predict_without(self._h, _ptr(idx), _ptr(offsets), ng, _ptr(X), M, _ptr(out["dmean"]),
+                                                   _ptr(out["dvar"]), _ptr(out["info"]), C.byref(ms)), "gpry_predict_without")
+        out["device_ms"] = ms.value
+        return out
+
+    def leave_out(self, groups):
+        """Joint predictive of every group of training targets from the points outside it (gpry_leave_out).  ``groups``: a
+        sequence of index sequences (1 to 64 distinct indices each; groups may overlap).  A dict with ``mean`` and ``cov``
+        (lists, one (n_g,) and one (n_g, n_g) array per group, in the order of the group's indices, units of y), ``chi2``,
+        ``logpdf`` and ``info`` (one per group; info != 0: the group's block of K^-1 was not positive definite and its
+        outputs are NaN), ``dof`` and ``device_ms``."""
+        ng, sizes, offsets, idx, ok = self._group_arrays(groups)
         mean, cov = np.empty(len(idx) if ok else 0), np.empty(int(np.sum(sizes ** 2)) if ok else 0)
         chi2, logpdf, info = np.empty(ng), np.empty(ng), np.zeros(ng, dtype=np.int32)
         ms = C.c_double(0.0)

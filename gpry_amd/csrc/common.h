@@ -265,6 +265,8 @@ struct gpry_ctx {
     int64_t hess_cap = 0;
     double* dtg = nullptr;             // gpry_mean_theta_grad: the right-hand sides U, T = V U and W = K^-1 U of one call (doubles)
     int64_t tg_cap = 0;
+    uint8_t* dpw = nullptr;            // gpry_predict_without: the stacked group rows VG, P, S, the panel, s, slices, outputs (bytes; predict_without.hip)
+    int64_t pw_cap = 0, pw_np = 0;     // ... and the padded model size it was last used with
     uint8_t* dsvm = nullptr;           // gpry_svm_fit: coordinate-major training set, alpha, gradient, labels, status block (bytes)
     int64_t svm_cap = 0;
     void* hsvm = nullptr; int64_t hsvm_cap = 0;    // gpry_svm_fit: pinned image of its upload (bytes)
@@ -518,6 +520,9 @@ bool panel_timed_out(int marker);                       // fourth status word: a
 int panel_timeout_error(gpry_ctx* ctx, int marker);
 // loo.hip: gpry_loo's pass over an inverse factor V (partial sums per 64 x 64 tile; ceil(N / 64) x Np doubles each)
 int loo_pass_launch(gpry_ctx* ctx, const double* V, double* qpart, double* wpart);
+// predict_thetas.hip: gpry_predict_thetas_var's cross-kernel panel (pt_var_panel_kernel) for the model the context holds, at
+// its own theta: Kst[k * ldk + c], k < Np, c < cols (a multiple of 64 that covers npts); zeros from row N and column npts on
+int pv_panel_launch(gpry_ctx* ctx, const double* dX, int64_t npts, int64_t cols, double* Kst, int64_t ldk);
 // api.hip: the B thetas of a call in ONE chain of launches (arena of scratch sets, chunking, parameter and result staging) --
 // the chain itself is the caller's: gpry_lml_batch's (lml_chain) or gpry_loo_objective_batch's (loo_fit.hip).  A chain is the
 // code of a single evaluation that honours gpry_ctx::bn / bstride / bpar and writes theta tb's results to row tb of `dres`.

@@ -168,6 +168,12 @@ int ensure_capacity(gpry_ctx* ctx, int64_t N, int d) {
         (void)hipFree(ctx->dhess);
         ctx->dhess = nullptr; ctx->hess_cap = 0;
     }
+    // the scratch of gpry_predict_without grows linearly with Np: given back below half the size it was last used with
+    if (ctx->dpw && 2 * Np < ctx->pw_np) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(ctx->dpw);
+        ctx->dpw = nullptr; ctx->pw_cap = 0; ctx->pw_np = 0;
+    }
     ctx->N = N; ctx->Np = Np; ctx->d = d; ctx->dpad = dpad;
     return 0;
 }
@@ -254,7 +260,7 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
                     ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc, ctx->dknn,
-                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm, ctx->dhess, ctx->dtg};
+                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm, ctx->dhess, ctx->dtg, ctx->dpw};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hloo) (void)hipHostFree(ctx->hloo);

@@ -20,30 +20,19 @@
 // workgroup per group adds the chunks ascending, puts the identity on the padding's diagonal, factors B in LDS (the
 // 16 x 16 pieces of chol16.h, one wave), inverts the factor column by column into the unused upper triangle, and forms
 // delta = B^-1 alpha_G, B^-1 = W^T W, chi^2 and log det.  A group is one fixed chain of operations on its own columns:
-// the same bits whatever other groups share the call and wherever it stands in the list.
+// the same bits whatever other groups share the call and wherever it stands in the list.  gpry_predict_without
+// (predict_without.hip) runs the same two kernels through lgo.h and takes W and z = W alpha_G from the finish.
 //
 // Both read V, alpha_, y_ and the noise vector and write to a buffer of their own (ctx->dloo): the state of predict, of
 // the sweep, of a Kriging-believer session and of the samplers is not touched.
 #include "ns_common.h"
 #include "chol16.h"
+#include "lgo.h"
 #include <algorithm>
 #include <vector>
 
 #define LOO_T 64            // tile of the pass over V
 #define LOO_LD 65           // row stride (doubles) of its LDS image: column reads and row reads both conflict free
-#define LGO_MAX 64          // largest group
-#define LGO_KC 256          // training rows per workgroup of the Gram
-#define LGO_KS 32           // ... and per LDS step
-#define LGO_LD 66           // row stride of the LDS images of the group kernels (chol_panel.hip's)
-#define LGO_MAX_GROUPS (1 << 20)
-#define LGO_BATCH_DOUBLES (int64_t(1) << 25)     // partial Grams of one batch of groups (256 MB)
-
-struct LgoGroup {
-    int64_t idx_off;        // first entry in the sorted index list (and in the per-index outputs)
-    int64_t part_off;       // first double of the group's partial Grams: (nch - c0) slices of np x np
-    int64_t cov_off;        // first double of its n x n covariance block
-    int n, np, c0, pad;     // size, padded size, first chunk that holds a non-zero row
-};
 
 // grid: the lower-triangle tiles (ti, tj), tj <= ti, of the leading nt x nt tiles; 256 threads.  grid.z: the thetas of a
 // batched objective (gpry_ctx::bn) -- V and the partial sums of theta blockIdx.z lie bstride doubles further on; y is shared
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(256) void lgo_finish_kernel(const double* __restric
                                                          const double* __restrict__ y, int nch, double y_mean, double y_std,
                                                          double* __restrict__ omean, double* __restrict__ ocov,
                                                          double* __restrict__ ochi2, double* __restrict__ ologpdf,
-                                                         int* __restrict__ oinfo) {
+                                                         int* __restrict__ oinfo, double* __restrict__ oW, double* __restrict__ oz) {
     __shared__ double sB[LGO_MAX * LGO_LD];
     __shared__ double sa[LGO_MAX], sz[LGO_MAX], sdl[LGO_MAX], srd[LGO_MAX], swd[LGO_MAX];
     __shared__ int sbad;
@@ -217,8 +206,12 @@ __global__ __launch_bounds__(256) void lgo_finish_kernel(const double* __restric
     __syncthreads();
     const int bad = sbad;
     if (bad) {                             // not positive definite: this group alone reports it
-        for (int e = t; e < n * n; e += 256) ocov[G.cov_off + e] = NAN;
-        if (t < n) omean[G.idx_off + t] = NAN;
+        for (int e = t; ocov && e < n * n; e += 256) ocov[G.cov_off + e] = NAN;
+        if (omean && t < n) omean[G.idx_off + t] = NAN;
+        if (oW) {
+            for (int e = t; e < LGO_MAX * LGO_MAX; e += 256) oW[(int64_t)blockIdx.x * LGO_MAX * LGO_MAX + e] = 0.0;
+            if (t < LGO_MAX) oz[(int64_t)blockIdx.x * LGO_MAX + t] = 0.0;
+        }
         if (t == 0) { ochi2[blockIdx.x] = NAN; ologpdf[blockIdx.x] = NAN; oinfo[blockIdx.x] = bad; }
         return;
     }
@@ -244,7 +237,19 @@ __global__ __launch_bounds__(256) void lgo_finish_kernel(const double* __restric
         sdl[t] = s;
     }
     __syncthreads();
-    if (t < n) omean[G.idx_off + t] = ns_rn((y[idx[G.idx_off + t]] - sdl[t]) * y_std) + y_mean;
+    if (omean && t < n) omean[G.idx_off + t] = ns_rn((y[idx[G.idx_off + t]] - sdl[t]) * y_std) + y_mean;
+    // gpry_predict_without (predict_without.hip): W dense, row k = [W_k0 .. W_kk, 0 ...], and z = W alpha_G, zeros in the padding
+    if (oW) {
+        double* Wg = oW + (int64_t)blockIdx.x * LGO_MAX * LGO_MAX;
+        const int a = t & 63;
+        for (int k = t >> 6; k < LGO_MAX; k += 4) {
+            double w = 0.0;
+            if (k < n && a < k) w = sB[a * LGO_LD + k];
+            if (k < n && a == k) w = swd[k];
+            Wg[k * LGO_MAX + a] = w;
+        }
+        if (t < LGO_MAX) oz[(int64_t)blockIdx.x * LGO_MAX + t] = t < n ? sz[t] : 0.0;
+    }
     if (t == 0) {
         double chi = 0.0, ld = 0.0;
         for (int i = 0; i < n; i++) { chi = fma(sa[i], sdl[i], chi); ld += log(sB[i * LGO_LD + i]); }
@@ -253,7 +258,7 @@ __global__ __launch_bounds__(256) void lgo_finish_kernel(const double* __restric
         oinfo[blockIdx.x] = 0;
     }
     const double ys2 = y_std * y_std;
-    for (int e = t; e < n * n; e += 256) { // (B^-1)_ab = sum over k >= max(a, b) of W_ka W_kb: the same chain for (a, b) and (b, a)
+    for (int e = t; ocov && e < n * n; e += 256) { // (B^-1)_ab = sum over k >= max(a, b) of W_ka W_kb: the same chain for (a, b) and (b, a)
         const int a = e / n, b = e - a * n, hi = a > b ? a : b, lo = a > b ? b : a;
         double s = (hi == lo ? swd[hi] : sB[lo * LGO_LD + hi]) * swd[hi];
         for (int k = hi + 1; k < n; k++) s = fma(sB[a * LGO_LD + k], sB[b * LGO_LD + k], s);
@@ -270,6 +275,57 @@ int loo_require(gpry_ctx* ctx, const char* who) {
 }
 
 }  // namespace
+
+// the checks of a list of groups and the groups in ascending index order, for gpry_leave_out and gpry_predict_without
+// (predict_without.hip); perm: place in the caller's group of the sorted group's entries; *ncov: the sum of n^2
+int lgo_parse_groups(gpry_ctx* ctx, const char* who, const int64_t* idx, const int64_t* offsets, int64_t ngroups,
+                     std::vector<LgoGroup>* groups_, std::vector<int>* sidx_, std::vector<int>* perm_, int64_t* ncov) {
+    if (!idx || !offsets) return gpry_fail(ctx, -1, "%s: idx or offsets is NULL", who);
+    if (ngroups < 1 || ngroups > LGO_MAX_GROUPS)
+        return gpry_fail(ctx, -1, "%s: ngroups = %lld, need 1 <= ngroups <= %d", who, (long long)ngroups, LGO_MAX_GROUPS);
+    const int64_t N = ctx->N;
+    std::vector<LgoGroup>& groups = *groups_;
+    std::vector<int>&sidx = *sidx_, &perm = *perm_;
+    groups.assign((size_t)ngroups, LgoGroup());
+    sidx.clear(); perm.clear();
+    if (offsets[0] != 0) return gpry_fail(ctx, -1, "%s: offsets[0] = %lld, need 0", who, (long long)offsets[0]);
+    std::vector<std::pair<int64_t, int>> srt;
+    int64_t cov_off = 0;
+    for (int64_t g = 0; g < ngroups; g++) {
+        const int64_t n = offsets[g + 1] - offsets[g];
+        if (n < 1) return gpry_fail(ctx, -1, "%s: group %lld is empty", who, (long long)g);
+        if (n > LGO_MAX) return gpry_fail(ctx, -1, "%s: group %lld has %lld points, at most %d", who, (long long)g, (long long)n, LGO_MAX);
+        srt.clear();
+        for (int64_t a = 0; a < n; a++) {
+            const int64_t i = idx[offsets[g] + a];
+            if (i < 0 || i >= N)
+                return gpry_fail(ctx, -1, "%s: index %lld of group %lld is outside [0, %lld)", who, (long long)i, (long long)g, (long long)N);
+            srt.push_back({i, (int)a});
+        }
+        std::sort(srt.begin(), srt.end());
+        for (int64_t a = 1; a < n; a++)
+            if (srt[(size_t)a].first == srt[(size_t)a - 1].first)
+                return gpry_fail(ctx, -1, "%s: group %lld holds index %lld more than once", who, (long long)g, (long long)srt[(size_t)a].first);
+        LgoGroup& G = groups[(size_t)g];
+        G.idx_off = (int64_t)sidx.size(); G.cov_off = cov_off; G.part_off = 0;
+        G.n = (int)n; G.np = (int)round_up(n, 16); G.c0 = (int)(srt[0].first / LGO_KC); G.pad = 0;
+        cov_off += n * n;
+        for (int64_t a = 0; a < n; a++) { sidx.push_back((int)srt[(size_t)a].first); perm.push_back(srt[(size_t)a].second); }
+    }
+    *ncov = cov_off;
+    return 0;
+}
+
+// the Gram and the finish of `ng` groups whose partial Grams fit `dpart` (LgoGroup::part_off), on the context's factor.  oW, oz
+// (nullable, gpry_predict_without): W = L_B^-1, 64 x 64 dense per group, and z = W alpha_G, 64 per group; omean, ocov nullable
+void lgo_launch(gpry_ctx* ctx, const int* didx, const LgoGroup* dgroups, int64_t ng, double* dpart, double* omean, double* ocov,
+                double* ochi2, double* ologpdf, int* oinfo, double* oW, double* oz) {
+    const int nch = (int)((ctx->N + LGO_KC - 1) / LGO_KC);
+    hipLaunchKernelGGL(lgo_gram_kernel, dim3((unsigned)ng, (unsigned)nch), dim3(256), 0, ctx->stream, ctx->dV, ctx->Np, ctx->N, didx,
+                       dgroups, dpart);
+    hipLaunchKernelGGL(lgo_finish_kernel, dim3((unsigned)ng), dim3(256), 0, ctx->stream, dpart, dgroups, didx, ctx->dalpha_, ctx->dy,
+                       nch, ctx->tf.y_mean, ctx->tf.y_std, omean, ocov, ochi2, ologpdf, oinfo, oW, oz);
+}
 
 // the pass of gpry_loo over another inverse factor (loo_fit.hip: the V of an objective evaluation): the same launch, so
 // the partial sums -- and q_i once they are added ascending -- are the bits gpry_loo forms for the same model
@@ -326,38 +382,12 @@ int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, in
     if (!ctx) return gpry_fail(nullptr, -1, "gpry_leave_out: ctx is NULL");
     GPRY_TRY(serve_stop(ctx));
     GPRY_TRY(loo_require(ctx, "gpry_leave_out"));
-    if (!idx || !offsets) return gpry_fail(ctx, -1, "gpry_leave_out: idx or offsets is NULL");
-    if (ngroups < 1 || ngroups > LGO_MAX_GROUPS)
-        return gpry_fail(ctx, -1, "gpry_leave_out: ngroups = %lld, need 1 <= ngroups <= %d", (long long)ngroups, LGO_MAX_GROUPS);
-    const int64_t N = ctx->N, Np = ctx->Np;
+    const int64_t N = ctx->N;
     const int nch = (int)((N + LGO_KC - 1) / LGO_KC);
-    // the groups in ascending index order; perm: place in the caller's group of the sorted group's entries
-    if (offsets[0] != 0) return gpry_fail(ctx, -1, "gpry_leave_out: offsets[0] = %lld, need 0", (long long)offsets[0]);
-    std::vector<LgoGroup> groups((size_t)ngroups);
+    std::vector<LgoGroup> groups;
     std::vector<int> sidx, perm;
-    std::vector<std::pair<int64_t, int>> srt;
     int64_t cov_off = 0;
-    for (int64_t g = 0; g < ngroups; g++) {
-        const int64_t n = offsets[g + 1] - offsets[g];
-        if (n < 1) return gpry_fail(ctx, -1, "gpry_leave_out: group %lld is empty", (long long)g);
-        if (n > LGO_MAX) return gpry_fail(ctx, -1, "gpry_leave_out: group %lld has %lld points, at most %d", (long long)g, (long long)n, LGO_MAX);
-        srt.clear();
-        for (int64_t a = 0; a < n; a++) {
-            const int64_t i = idx[offsets[g] + a];
-            if (i < 0 || i >= N)
-                return gpry_fail(ctx, -1, "gpry_leave_out: index %lld of group %lld is outside [0, %lld)", (long long)i, (long long)g, (long long)N);
-            srt.push_back({i, (int)a});
-        }
-        std::sort(srt.begin(), srt.end());
-        for (int64_t a = 1; a < n; a++)
-            if (srt[(size_t)a].first == srt[(size_t)a - 1].first)
-                return gpry_fail(ctx, -1, "gpry_leave_out: group %lld holds index %lld more than once", (long long)g, (long long)srt[(size_t)a].first);
-        LgoGroup& G = groups[(size_t)g];
-        G.idx_off = (int64_t)sidx.size(); G.cov_off = cov_off; G.part_off = 0;
-        G.n = (int)n; G.np = (int)round_up(n, 16); G.c0 = (int)(srt[0].first / LGO_KC); G.pad = 0;
-        cov_off += n * n;
-        for (int64_t a = 0; a < n; a++) { sidx.push_back((int)srt[(size_t)a].first); perm.push_back(srt[(size_t)a].second); }
-    }
+    GPRY_TRY(lgo_parse_groups(ctx, "gpry_leave_out", idx, offsets, ngroups, &groups, &sidx, &perm, &cov_off));
     const int64_t ncov = cov_off, nidx = (int64_t)sidx.size();
     // batches of groups whose partial Grams fit LGO_BATCH_DOUBLES (a group's bits do not depend on its batch)
     int64_t part_max = 0;
@@ -396,10 +426,7 @@ int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, in
         HIP_TRY(ctx, hipMemcpyAsync(didx, sidx.data(), sz[1], hipMemcpyHostToDevice, st));
         for (size_t bi = 0; bi + 1 < batch_first.size(); bi++) {
             const int64_t g0 = batch_first[bi], ng = batch_first[bi + 1] - g0;
-            hipLaunchKernelGGL(lgo_gram_kernel, dim3((unsigned)ng, (unsigned)nch), dim3(256), 0, st, ctx->dV, Np, N, didx,
-                               dgroups + g0, dpart);
-            hipLaunchKernelGGL(lgo_finish_kernel, dim3((unsigned)ng), dim3(256), 0, st, dpart, dgroups + g0, didx, ctx->dalpha_,
-                               ctx->dy, nch, ctx->tf.y_mean, ctx->tf.y_std, dmean, dcov, dchi + g0, dlp + g0, dinfo + g0);
+            lgo_launch(ctx, didx, dgroups + g0, ng, dpart, dmean, dcov, dchi + g0, dlp + g0, dinfo + g0, nullptr, nullptr);
         }
         HIP_TRY(ctx, hipGetLastError());
         if (mean) HIP_TRY(ctx, hipMemcpyAsync(hmean.data(), dmean, sz[2], hipMemcpyDeviceToHost, st));

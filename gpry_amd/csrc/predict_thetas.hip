@@ -129,6 +129,18 @@ __global__ __launch_bounds__(256) void pt_var_panel_kernel(const double* __restr
     }
 }
 
+int pv_panel_launch(gpry_ctx* ctx, const double* dX, int64_t npts, int64_t cols, double* Kst, int64_t ldk) {
+    const KernParams kp = make_kp(ctx);
+    const AffParams ap = make_ap(ctx, kp.has_aff);
+#define PV(KID) \
+    hipLaunchKernelGGL((pt_var_panel_kernel<KID>), dim3((unsigned)(cols / PV_BN), (unsigned)(ctx->Np / 64), 1), dim3(256), 0, ctx->stream, \
+                       ctx->dXs, ctx->N, ctx->d, ctx->dpad, kp.has_aff, ap, kp.C, (const double*)nullptr, (int64_t)0, dX, npts, Kst, ldk)
+    DISPATCH_KID(ctx->kernel_id, PV)
+#undef PV
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void pt_var_finish_kernel(const double* __restrict__ part_, int64_t ldk, int nrb, double prior,
                                                             const double* __restrict__ bpar, int64_t bstride, double ys2, int64_t n,
                                                             double* __restrict__ out, int64_t ldo) {

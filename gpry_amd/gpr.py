@@ -1526,15 +1526,44 @@ class GaussianProcessRegressor(_RM, _BE):
         of y_G under that predictive), ``info`` (non-zero: the group's block of K^-1 was not positive definite, its
         outputs are NaN), ``groups`` (the index arrays) and ``device_ms``.  Unclipped and ungated."""
         self._cv_ready("leave_out")
+        groups = self._cv_groups(groups)
+        res = self.device.leave_out(groups)
+        res["groups"] = groups
+        return res
+
+    def _cv_groups(self, groups, each=False):
+        """``groups`` of ``leave_out`` / ``predict_without`` as a list of index arrays: index sequences, ``"last"`` or,
+        where ``each`` allows it, ``"each"`` (every training point alone)."""
         if isinstance(groups, str):
+            if groups == "each" and each:
+                return [np.array([i], dtype=np.int64) for i in range(len(self.y_train))]
             if groups != "last":
-                raise ValueError(f"groups: index sequences or 'last' (got {groups!r})")
+                raise ValueError(f"groups: index sequences{', ' + repr('each') if each else ''} or 'last' (got {groups!r})")
             k = int(getattr(self, "n_last_appended_finite", 0))
             if k < 1:
                 raise ValueError("groups='last': the last append_to_data added no finite point")
             groups = [np.arange(len(self.y_train) - k, len(self.y_train))]
-        groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
-        res = self.device.leave_out(groups)
+        return [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+
+    def predict_without(self, X, groups, validate=True):
+        """What the surrogate would predict at the rows of ``X`` had a group of training points never been bought, as a
+        change against today's prediction, on the device (``gpry_predict_without``) from the factor it holds and without
+        a refactorisation.  ``groups``: as ``leave_out`` takes them -- a sequence of index sequences into ``X_train`` /
+        ``y_train`` (1 to 64 distinct indices each; groups may overlap), or ``"last"``, the finite points of the last
+        ``append_to_data`` -- or ``"each"``: every training point alone (a jackknife).  A dict: ``dmean`` and ``dvar``
+        (ngroups, M): mean and variance without the group minus those with it, in untransformed units (``dvar >= 0``: a
+        point never lowers the variance elsewhere by leaving); ``info`` (non-zero: the group's block of K^-1 was not
+        positive definite, its rows are NaN), ``groups`` (the index arrays) and ``device_ms``.
+        The counterfactual is at today's theta, pre-processors and noise: nothing is refitted, neither the
+        hyper-parameters nor ``Normalize_y``.  The changes are those of the unclipped mean and of the latent variance, as
+        ``loo`` reports them: ``clip_factor``, the classifier and the trust region play no part."""
+        self._cv_ready("predict_without")
+        X = self._validate_X(np.atleast_2d(X), validate)
+        if X.shape[1] != self.d:
+            raise ValueError(f"predict_without: rows of dimension {self.d} are needed, got shape {X.shape}")
+        groups = self._cv_groups(groups, each=True)
+        res = self.device.predict_without(groups, X)
+        self.n_eval += len(groups) * X.shape[0]
         res["groups"] = groups
         return res
 

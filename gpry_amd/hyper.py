@@ -173,6 +173,29 @@ class HyperSpread:
                 f"ess_min={self.ess_min:.1f}, max_abs_logr={self.max_abs_logr:.3g})")
 
 
+def reweight(wk, Xk, logr):
+    """The sample ``Xk`` (m, d) with normalised weights ``wk`` reweighted by each row of ``logr`` (S, m; -inf: the row
+    takes no part): ``(dlogZ, ws, ess, means, covs, mean0, cov0)`` -- log sum_i w_i r_si, the normalised weights w_i r_si,
+    their Kish effective sample size, mean and covariance under them, and the sample's own mean and covariance.  What
+    ``hyper_spread`` and ``mc.batch_influence`` make their reports of."""
+    d = Xk.shape[1]
+    top = logr.max(axis=1)
+    e = wk[None, :] * np.exp(logr - top[:, None])
+    tot = e.sum(axis=1)
+    dlogZ = top + np.log(tot)
+    ws = e / tot[:, None]
+    ess = 1.0 / np.sum(ws * ws, axis=1)
+    means = ws.dot(Xk)
+    covs = np.empty((len(logr), d, d))
+    for s in range(len(logr)):                          # weighted Grams, one draw at a time: O(M d) beside ws
+        cen = Xk - means[s]
+        covs[s] = (cen * ws[s][:, None]).T.dot(cen)
+    mean0 = wk.dot(Xk)
+    cen0 = Xk - mean0
+    cov0 = (cen0 * wk[:, None]).T.dot(cen0)
+    return dlogZ, ws, ess, means, covs, mean0, cov0
+
+
 def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=1.0, exact=False):
     """How far the posterior moves because theta is only known as well as the data pin it: the Monte Carlo sample
     ``(X, y, w)`` that ``mc_sample_from_gp`` returned, reweighted to first order under ``n_draws`` draws
@@ -247,20 +270,7 @@ def hyper_spread(gpr, X, y, w=None, n_draws=256, seed=None, laplace=None, scale=
         del pt, mean_s, linear
     max_abs_logr = float(np.max(np.abs(logr[:, alive])))
     logr[:, ~alive] = -np.inf
-    top = logr.max(axis=1)
-    e = wk[None, :] * np.exp(logr - top[:, None])
-    tot = e.sum(axis=1)
-    dlogZ = top + np.log(tot)
-    ws = e / tot[:, None]
-    ess = 1.0 / np.sum(ws * ws, axis=1)
-    means = ws.dot(Xk)
-    covs = np.empty((len(logr), d, d))
-    for s in range(len(logr)):                          # weighted Grams, one draw at a time: O(M d) beside ws
-        cen = Xk - means[s]
-        covs[s] = (cen * ws[s][:, None]).T.dot(cen)
-    mean0 = wk.dot(Xk)
-    cen0 = Xk - mean0
-    cov0 = (cen0 * wk[:, None]).T.dot(cen0)
+    dlogZ, ws, ess, means, covs, mean0, cov0 = reweight(wk, Xk, logr)
     var0 = np.diag(cov0)
     with np.errstate(divide="ignore", invalid="ignore"):
         mean_shift_sigma = means.std(axis=0) / np.sqrt(var0)

@@ -17,6 +17,7 @@ from gpry_amd.maximize import (hessian_gp, laplace_covmat, laplace_gp, maximize_
                                profile_gp)  # (beside mc_sample_from_gp: the best fit, its curvature and profiles)
 from gpry_amd.hyper import HyperLaplace, hyper_laplace  # noqa: F401  (... and the curvature of the marginal likelihood in theta)
 from gpry_amd.hyper import HyperSpread, hyper_spread  # noqa: F401  (... and what it does to the posterior: to first order, or with exact=True refactorised per draw)
+from gpry_amd.hyper import reweight as _reweight
 from gpry_amd.hyper import HyperPredict, hyper_predict  # noqa: F401  (... and to the error bar at a point: mean and sigma with theta marginalised)
 from gpry_amd.tools import generic_params_names, get_Xnumber
 
@@ -351,6 +352,83 @@ def validate_gp(gpr, groups=None):
         out["groups"] = dict(chi2=g["chi2"], dof=g["dof"], logpdf=g["logpdf"], info=g["info"], indices=g["groups"])
         out["device_ms"] += g["device_ms"]
     return GPValidation(**out)
+
+
+class BatchInfluence:
+    """What ``batch_influence`` returns.  Per group g (arrays of length ``len(groups)``), "before" being the surrogate
+    without the group's training points and "now" the one the regressor holds: ``dlogZ`` (log Z_before - log Z_now),
+    ``kl`` (the Kullback-Leibler divergence from the posterior now to the posterior before, >= 0), ``ess`` (Kish, of the
+    sample reweighted to "before"), ``means`` (ngroups, d) and ``covs`` (ngroups, d, d) of the reweighted sample,
+    ``mean_shift_sigma`` (ngroups, d; |mean_before - mean_now| in units of today's posterior sigma), ``cov_ratio``
+    (ngroups, d; variance before over variance now), ``max_abs_logr``, ``var_gain`` (the latent variance the group
+    removed, averaged over the posterior now) and ``info`` (non-zero: the group's block of K^-1 is not positive definite,
+    its entries are NaN).  ``mean0`` / ``cov0``: today's moments.  ``groups`` (the index arrays), ``keep`` (the sample rows
+    that took part), ``n_points``, ``device_ms`` and, with ``groups="each"``, ``order``: the training indices by
+    descending ``kl``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return (f"BatchInfluence(n_points={self.n_points}, n_groups={len(self.dlogZ)}, "
+                f"kl_max={float(np.nanmax(self.kl)):.3g}, ess_min={float(np.nanmin(self.ess)):.1f})")
+
+
+def batch_influence(gpr, X, y, w=None, groups="last"):
+    """What a group of training points bought: the Monte Carlo sample ``(X, y, w)`` of today's surrogate (as
+    ``mc_sample_from_gp`` returns it) reweighted under the surrogate WITHOUT the group, from the factor on the device
+    (``gpr.predict_without``): no second sample, no Gaussian approximation, no refit and no likelihood call.  With
+    log r_i = mean_without(x_i) - mean(x_i), per group: dlogZ = log sum_i w_i r_i, kl = -sum_i w_i log r_i + dlogZ (the
+    quantity the ``GaussianKL`` convergence criterion of the reference estimates from two Gaussian fits), and the moments and
+    Kish effective sample size of the weights w_i r_i.  ``groups``: as for ``gpr.predict_without``; ``"last"`` asks what
+    the last ``append_to_data`` changed, ``"each"`` is the jackknife over the training points (case-deletion influence
+    of every likelihood evaluation, ``order`` sorting them).  The rows that take part are those of positive finite
+    weight and finite y.  The counterfactual is at today's hyper-parameters and pre-processors, unclipped and ungated.
+    Warns when a group's effective sample size is below 5 % of the rows.  A report: it changes nothing.  Returns a
+    ``BatchInfluence``."""
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    y = np.asarray(y, dtype=float)
+    n, d = X.shape
+    w = np.full(n, 1.0 / max(n, 1)) if w is None else np.asarray(w, dtype=float)
+    if y.shape != (n,) or w.shape != (n,):
+        raise ValueError(f"expected y and w of shape ({n},), got {y.shape} and {w.shape}")
+    keep = np.flatnonzero((w > 0) & np.isfinite(w) & np.isfinite(y))
+    if len(keep) == 0:
+        raise ValueError("the sample has no row of positive weight and finite y")
+    wk = w[keep] / w[keep].sum()
+    Xk = np.ascontiguousarray(X[keep])
+    m = len(keep)
+    each = isinstance(groups, str) and groups == "each"
+    res = gpr.predict_without(Xk, groups)
+    info = np.asarray(res["info"])
+    ok = info == 0
+    ng = len(info)
+    logr = np.asarray(res["dmean"], dtype=float)[ok]
+    dlogZ, ws, ess, means, covs, mean0, cov0 = _reweight(wk, Xk, logr)
+    kl = dlogZ - logr.dot(wk)
+    var0 = np.diag(cov0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean_shift_sigma = np.abs(means - mean0[None, :]) / np.sqrt(var0)
+        cov_ratio = np.einsum("saa->sa", covs) / var0
+    max_abs_logr = np.max(np.abs(logr), axis=1) if len(logr) else np.zeros(0)
+    var_gain = np.asarray(res["dvar"], dtype=float)[ok].dot(wk)
+
+    def spread(a):                                      # the per-group arrays keep their length: NaN where info != 0
+        full = np.full((ng,) + a.shape[1:], np.nan)
+        full[ok] = a
+        return full
+    out = dict(dlogZ=spread(dlogZ), kl=spread(kl), ess=spread(ess), means=spread(means), covs=spread(covs),
+               mean_shift_sigma=spread(mean_shift_sigma), cov_ratio=spread(cov_ratio), max_abs_logr=spread(max_abs_logr),
+               var_gain=spread(var_gain), mean0=mean0, cov0=cov0, info=info, groups=res["groups"], keep=keep, n_points=m,
+               device_ms=res["device_ms"])
+    if each:
+        out["order"] = np.argsort(-np.where(np.isnan(out["kl"]), -np.inf, out["kl"]), kind="stable")
+    out = BatchInfluence(**out)
+    if len(ess) and ess.min() < 0.05 * m:
+        warnings.warn(f"batch_influence: the smallest effective sample size over the groups is {ess.min():.1f} of {m} "
+                      "rows (< 5 %): the surrogate without that group is too far from today's for the reweighted sample to "
+                      "mean anything")
+    return out
 
 
 def mc_sample_from_gp_ns(gpr, bounds=None, params=None, sampler=None, sampler_options=None, output=None, run=True,

@@ -762,6 +762,33 @@ int gpry_predict_thetas(gpry_ctx* ctx, const double* thetas, int64_t B, const do
 int gpry_predict_thetas_var(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int64_t M, double* mean, double* var,
                             double* lml, int* info, double* device_ms);
 
+/* ---- Predictions without a group of training points (predict_without.hip; gpry_amd/gpr.py: predict_without; the report in
+ * gpry_amd/mc.py: batch_influence).  What the surrogate would predict at the M rows of X (raw coordinates where the affine
+ * map has an x-affine, as for gpry_mean_theta_grad) had group g = idx[offsets[g] .. offsets[g + 1]) never been bought:
+ * gpry_leave_out's groups (1 to 64 distinct indices in [0, N), groups may overlap, sorted on the host), at the current theta,
+ * y map, noise vector and white term -- nothing is refitted.  With B = (K^-1)_GG = L_B L_B^T, W = L_B^-1 (the arithmetic,
+ * and the bits, of gpry_leave_out), t = W alpha_G, S = W (V_G^T V) and s = S k*(x):
+ *   dmean[g, i] = mean_-G(x_i) - mean(x_i) = -y_std s.t        of the UNCLIPPED, UNGATED mean, units of y;
+ *   dvar[g, i]  = var_-G(x_i) - var(x_i)   = +y_std^2 |s|^2    of the latent variance, units of y^2: a sum of squares, >= 0
+ *                 (the prior variance C + w cancels: nothing is clamped);
+ *   info[g]     gpry_leave_out's: non-zero where B is not positive definite; that group's rows are NaN, the others unaffected.
+ * dmean, dvar: ngroups x M row-major, either may be NULL; info and device_ms nullable.  All four kernels, GPRY_KERNEL_WHITE,
+ * factors grown by gpry_append_rows, models below 128 rows.  No factorisation: per group one n x N x N / 2 product on the FP64
+ * matrix pipe, per point and group n N multiply-adds beside the kernel row (the stacked rows of up to 64 groups against a
+ * panel of 2048 points, on the matrix pipe).  M is unbounded (panels of 2048 points, uploads of 32768).
+ * dmean[g, i] and dvar[g, i] depend bit for bit on the model, the group as a set and the point alone: not on M, the point's
+ * position, how points or groups are split over calls, panels or batches, the other groups, the group's place in the list or
+ * the context.  A point whose k* underflows gives exactly 0 and 0.
+ * Refuses (-1, gpry_last_error) before anything is launched: NULL idx / offsets / X; both outputs NULL; ngroups < 1; M < 1; no
+ * valid factor; d > 32; a coordinate that is not finite; gpry_leave_out's group refusals (empty, above 64, out of range, an
+ * index twice).  Stops the resident predict kernel first.  Reads V, alpha_ and the scaled training rows; writes a scratch of
+ * its own (sized as predict_without.hip states, released with the context, and by gpry_set_train below half the model size it
+ * served) and the staging buffer: gpry_predict's state, a sweep, a Kriging-believer session, the samplers, gpry_loo's buffers
+ * and gpry_lml's factor cache are untouched.  Stage timers "without_setup", "without_points" and, inside the latter,
+ * "without_panel" and "without_contract". */
+int gpry_predict_without(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, int64_t ngroups, const double* X, int64_t M,
+                         double* dmean, double* dvar, int* info, double* device_ms);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
