@@ -104,6 +104,8 @@ SIGNATURES = {
                                _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int64), _P(C.c_int), _P(C.c_double)]),
     "gpry_leave_out": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _P(C.c_double)]),
     "gpry_predict_without": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _P(C.c_double)]),
+    "gpry_var_theta_grad": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _P(C.c_double)]),
+    "gpry_var_theta_grad_panel": (C.c_int64, [_vp]),
     "gpry_predict_grad": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     "gpry_predict_grad_batch": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp]),
     "gpry_predict_point": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -786,6 +788,29 @@ class Device:
         ms = C.c_double(0.0)
         self._check(self._lib.gpry_mean_theta_grad(self._h, _ptr(X), n, _ptr(out["y"]), _ptr(out["G"]), C.byref(ms)),
                     "gpry_mean_theta_grad")
+        out["device_ms"] = ms.value
+        return out
+
+    # -- the derivative of the variance in theta (gpry_amd/gpr.py: var_theta_grad; gpry_amd/hyper.py: hyper_acq_spread) ----
+    def var_theta_grad_panel(self):
+        """Points per panel of ``var_theta_grad`` for the model the context holds (gpry_var_theta_grad_panel: a function
+        of its padded size alone)."""
+        return int(self._lib.gpry_var_theta_grad_panel(self._h))
+
+    def var_theta_grad(self, X, want_var=True):
+        """The latent predictive variance and its derivative in theta = [log C, log l_1 .. log l_d (, log w)] at the rows
+        of ``X`` (npts, d), raw coordinates (gpry_var_theta_grad): a dict with ``var`` (npts,; y_std^2 (C + w - |V k|^2), not
+        clamped, clipped or gated; None with ``want_var=False``), ``G`` (npts, p; units of y^2 per unit of log theta) and
+        ``device_ms``.  Any number of points (panels of ``self.var_theta_grad_panel()``); all four kernels; models of at most
+        4096 padded rows."""
+        X = _f64(X)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError(f"expected points of shape (npts, {self.d}), got {X.shape}")
+        n = X.shape[0]
+        out = dict(var=np.empty(n) if want_var else None, G=np.empty((n, self.n_theta)))
+        ms = C.c_double(0.0)
+        self._check(self._lib.gpry_var_theta_grad(self._h, _ptr(X), n, _ptr(out["var"]), _ptr(out["G"]), C.byref(ms)),
+                    "gpry_var_theta_grad")
         out["device_ms"] = ms.value
         return out
 

@@ -267,6 +267,8 @@ struct gpry_ctx {
     int64_t tg_cap = 0;
     uint8_t* dpw = nullptr;            // gpry_predict_without: the stacked group rows VG, P, S, the panel, s, slices, outputs (bytes; predict_without.hip)
     int64_t pw_cap = 0, pw_np = 0;     // ... and the padded model size it was last used with
+    double* dvtg = nullptr;            // gpry_var_theta_grad: the d matrices dK / dlog l_a, the panel, T, Q and the d products of a panel (doubles; var_theta_grad.hip)
+    int64_t vtg_cap = 0;
     uint8_t* dsvm = nullptr;           // gpry_svm_fit: coordinate-major training set, alpha, gradient, labels, status block (bytes)
     int64_t svm_cap = 0;
     void* hsvm = nullptr; int64_t hsvm_cap = 0;    // gpry_svm_fit: pinned image of its upload (bytes)
@@ -523,6 +525,9 @@ int loo_pass_launch(gpry_ctx* ctx, const double* V, double* qpart, double* wpart
 // predict_thetas.hip: gpry_predict_thetas_var's cross-kernel panel (pt_var_panel_kernel) for the model the context holds, at
 // its own theta: Kst[k * ldk + c], k < Np, c < cols (a multiple of 64 that covers npts); zeros from row N and column npts on
 int pv_panel_launch(gpry_ctx* ctx, const double* dX, int64_t npts, int64_t cols, double* Kst, int64_t ldk);
+// lml_hessian.hip: the d matrices dK / dlog l_k among the training rows (full zero-padded squares, Km + k Np^2) from the scaled
+// rows the context holds, at its own theta: stage (b) of gpry_lml_hessian without its Hessian sums
+int lml_hess_km_launch(gpry_ctx* ctx, double* Km);
 // api.hip: the B thetas of a call in ONE chain of launches (arena of scratch sets, chunking, parameter and result staging) --
 // the chain itself is the caller's: gpry_lml_batch's (lml_chain) or gpry_loo_objective_batch's (loo_fit.hip).  A chain is the
 // code of a single evaluation that honours gpry_ctx::bn / bstride / bpar and writes theta tb's results to row tb of `dres`.

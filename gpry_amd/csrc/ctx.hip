@@ -174,6 +174,12 @@ int ensure_capacity(gpry_ctx* ctx, int64_t N, int d) {
         (void)hipFree(ctx->dpw);
         ctx->dpw = nullptr; ctx->pw_cap = 0; ctx->pw_np = 0;
     }
+    // the scratch of gpry_var_theta_grad, d Np^2 doubles and the panels behind them, by the rule of gpry_lml_hessian's
+    if (ctx->dvtg && 2 * (2 + (int64_t)d) * Np * Np < ctx->vtg_cap) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(ctx->dvtg);
+        ctx->dvtg = nullptr; ctx->vtg_cap = 0;
+    }
     ctx->N = N; ctx->Np = Np; ctx->d = d; ctx->dpad = dpad;
     return 0;
 }
@@ -260,7 +266,7 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
                     ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc, ctx->dknn,
-                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm, ctx->dhess, ctx->dtg, ctx->dpw};
+                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm, ctx->dhess, ctx->dtg, ctx->dpw, ctx->dvtg};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hloo) (void)hipHostFree(ctx->hloo);

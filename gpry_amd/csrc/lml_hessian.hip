@@ -124,7 +124,9 @@ __global__ __launch_bounds__(256) void lml_hess_mirror_kernel(const double* __re
 // (lane group g: pair (16 g + e, 16 w + cc)), lane (g, r) supplies coordinate r (and 16 + r) of its group's pair, the weight
 // comes from the lane that owns the pair.  The four waves are combined as (w0 + w1) + (w2 + w3).
 // gpart[tile][block][256]: block 0 = low-low, and for d > 16 block 1 = high-low, block 2 = high-high; 16 x 16 row-major.
-template <int NBK, int KID>
+// KM_ONLY (gpry_var_theta_grad's setup, lml_hess_km_launch below): the first phase's matrices K_k alone -- Kf, alpha, gpart
+// and mvpart are not touched.
+template <int NBK, int KID, bool KM_ONLY = false>
 __global__ __launch_bounds__(256) void lml_hess_pairs_kernel(const double* __restrict__ Xs, const double* __restrict__ Kf, int64_t Np,
                                                              const double* __restrict__ alpha, double* __restrict__ Km,
                                                              double* __restrict__ gpart, double* __restrict__ mvpart, KernParams kp,
@@ -145,8 +147,10 @@ __global__ __launch_bounds__(256) void lml_hess_pairs_kernel(const double* __res
         }
         Xi[k * LH_XLD + row] = vi; Xj[k * LH_XLD + row] = vj;
     }
-    if (t < 64) ai[t] = alpha[bi * 64 + t];
-    else if (t < 128) aj[t - 64] = alpha[bj * 64 + t - 64];
+    if (!KM_ONLY) {
+        if (t < 64) ai[t] = alpha[bi * 64 + t];
+        else if (t < 128) aj[t - 64] = alpha[bj * 64 + t - 64];
+    }
     __syncthreads();
     const int col = 16 * w + r;
     const int64_t gcol = (int64_t)bj * 64 + col, grow0 = (int64_t)bi * 64 + 16 * g;
@@ -163,9 +167,10 @@ __global__ __launch_bounds__(256) void lml_hess_pairs_kernel(const double* __res
         double kv, h, gg;
         corr_h_g<KID>(ch[e], &kv, &h, &gg);
         const bool in = grow0 + e < kp.N && gcol < kp.N;
+        ch[e] = in ? kp.C * h : 0.0;
+        if (KM_ONLY) continue;
         const double kf = Kf[(grow0 + e) * Np + gcol];
         const double W = ai[16 * g + e] * aj[col] - kf;
-        ch[e] = in ? kp.C * h : 0.0;
         wg[e] = in ? W * (kp.C * gg) : 0.0;
     }
     const int64_t sq = Np * Np;
@@ -177,12 +182,14 @@ __global__ __launch_bounds__(256) void lml_hess_pairs_kernel(const double* __res
             const double df = Xi[k * LH_XLD + 16 * g + e] - xj;
             const double v = ch[e] * (df * df);
             Km[(int64_t)k * sq + (grow0 + e) * Np + gcol] = v;
-            mv = fma(v, ai[16 * g + e], mv);
+            if (!KM_ONLY) mv = fma(v, ai[16 * g + e], mv);
         }
+        if (KM_ONLY) continue;
         mv += __shfl_xor(mv, 16);
         mv += __shfl_xor(mv, 32);
         if (g == 0) mvpart[((int64_t)bi * kp.d + k) * Np + gcol] = mv;
     }
+    if (KM_ONLY) return;
     // the weighted Gram on the matrix pipe (operand and accumulator layout: chol16.h)
     v4d acc[NB2];
 #pragma unroll
@@ -393,6 +400,23 @@ __global__ __launch_bounds__(256) void lml_hess_finish_kernel(const double* __re
         host_res[LH_HOFF + i * p + j] = h;
         host_res[LH_HOFF + j * p + i] = h;
     }
+}
+
+// Km[k] = dK / dlog l_k among the training rows, k < d: d full zero-padded squares of Np x Np doubles, from the scaled rows the
+// context holds (the caller has called ensure_pred_xs) at the context's own theta -- the matrices of stage (b), by its kernel
+int lml_hess_km_launch(gpry_ctx* ctx, double* Km) {
+    const KernParams kp = make_kp(ctx);
+    const int nb = (int)(ctx->Np / LH_T);
+    const unsigned grid = (unsigned)(nb * nb);
+#define LHK2(NBK, KID) hipLaunchKernelGGL((lml_hess_pairs_kernel<NBK, KID, true>), dim3(grid), dim3(256), 0, ctx->stream, ctx->dXs, \
+                                          (const double*)nullptr, ctx->Np, (const double*)nullptr, Km, (double*)nullptr,       \
+                                          (double*)nullptr, kp, nb)
+#define LHK4(KID) { if (ctx->d <= 16) LHK2(1, KID); else LHK2(2, KID); }
+    DISPATCH_KID(ctx->kernel_id, LHK4)
+#undef LHK4
+#undef LHK2
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
 }
 
 namespace {

@@ -810,6 +810,35 @@ class GaussianProcessRegressor(_RM, _BE):
         M = self._grad_map(self.kernel_, G.shape[1])
         return out["y"], G if M is None else G.dot(M.T)
 
+    def _var_theta_grad_full(self, X, validate=True):
+        """The device call of ``var_theta_grad`` in the device's own vector: its dict (``var``, ``G``, ``device_ms``)."""
+        from gpry_amd.mc import _push_model
+        X = np.ascontiguousarray(self._validate_X(np.atleast_2d(X), validate), dtype=float)
+        if X.ndim != 2 or X.shape[1] != self.d or len(X) == 0:
+            raise ValueError(f"var_theta_grad: rows of dimension {self.d} are needed, got shape {X.shape}")
+        if self.X_train_ is None:
+            raise ValueError("var_theta_grad needs a model with training data")
+        _push_model(self, "var_theta_grad")
+        out = self.device.var_theta_grad(X)
+        self.n_eval += len(X)
+        return out
+
+    def var_theta_grad(self, X, validate=True, full=False):
+        """``(var, G)``: the latent predictive variance at the rows of ``X`` (npts, d) and its derivative in the
+        hyper-parameters at the fitted theta, on the device (``gpry_var_theta_grad``, closed form, no refactorisation), in
+        units of y^2 per unit of log theta: the twin of ``mean_theta_grad``.  var (npts,) is y_std^2 (C + w - |V k|^2), the
+        variance of ``predict_thetas(return_std=True)`` before its clamp -- not clamped at 0, not clipped, not gated.
+        ``full=False``: one column per entry of ``kernel_.theta`` (``mean_theta_grad``'s mapping: an isotropic length
+        scale sums its tied columns, fixed entries drop out, a ``WhiteKernel`` in either operand order); ``full=True``:
+        the device's own vector ``[log C, log l_1 .. l_d (, log w)]``.  All four kernels; any number of points; models of
+        more than 4096 padded rows are refused by the device.  ``n_eval`` grows by npts."""
+        out = self._var_theta_grad_full(X, validate)
+        G = out["G"]
+        if full:
+            return out["var"], G
+        M = self._grad_map(self.kernel_, G.shape[1])
+        return out["var"], G if M is None else G.dot(M.T)
+
     def predict_thetas(self, X, thetas, validate=True, full=False, return_std=False):
         """``(mean (B, M), lml (B,), info (B,))``: the posterior mean at the rows of ``X`` (M, d) under every row of
         ``thetas`` (B, ...), one refactorisation per row, in one device call (``gpry_predict_thetas``) that leaves the

@@ -4,7 +4,8 @@
 (``gpry_lml_hessian``, closed form) and reads from them which entries the data pin and which are sloppy, how they are
 correlated, which are held by a bound, and the Laplace evidence of the kernel family.  A report: it warns of nothing,
 gates nothing and changes no fit.  ``hyper_spread`` carries the Gaussian's draws of theta to a Monte Carlo sample of the
-posterior, ``hyper_predict`` to the predictive mean and error bar at given points.
+posterior, ``hyper_predict`` to the predictive mean and error bar at given points, ``hyper_acq_spread`` -- to first order --
+to sigma and the LogExp acquisition at given points and to their ranking.
 """
 import warnings
 from collections import namedtuple
@@ -359,3 +360,133 @@ def hyper_predict(gpr, X, n_draws=64, seed=None, laplace=None, scale=1.0, weight
                         sigma_total=sigma_total, inflation=inflation, dtheta=dtheta, means=means, vars=vars_, lml=lml, lml0=lml0,
                         failed=failed, theta_logw=theta_logw, theta_ess=theta_ess,
                         weighted=bool(weighted), device_ms=pt["device_ms"], seed=seed, scale=scale)
+
+
+class HyperAcqSpread:
+    """What ``hyper_acq_spread`` returns, at the n rows of X in untransformed units, theta in the device's own vector
+    (p entries).  ``mean`` (``predict`` of the row: clip and gates included, -inf for a gated row), ``var`` (the latent
+    variance, not clamped) and ``sigma = sqrt(max(var, 0))``; ``G_mean``, ``G_var`` (n, p): their derivatives in theta.
+    ``sigma_mean_theta`` = sqrt(g_m^T S g_m) with S = scale^2 cov over the free entries (``hyper_spread``'s
+    ``sigma_theta``), ``sigma_rel_theta`` = sqrt(g_v^T S g_v) / (2 var): the relative standard deviation of sigma itself
+    (NaN where var <= 0).  ``acq`` (n,): LogExp's value 2 zeta (mean - y_max) + log(var - sigma_n^2) / 2, -inf for a dead row
+    (var <= sigma_n^2 or a mean that is not finite); ``acq_grad`` (n, p) = 2 zeta G_mean + G_var / (2 (var - sigma_n^2)), NaN
+    for a dead row; ``acq_sigma_theta`` (n,) = sqrt(g_a^T S g_a), NaN for a dead row.  ``order`` (n,): the rows by
+    descending ``acq`` (dead rows last, ties in input order).  ``flip`` (n, n; None above 256 rows):
+    Phi(-|a_i - a_j| / s_ij) with s_ij^2 = (g_i - g_j)^T S (g_i - g_j), the first-order probability that rows i and j swap rank
+    under a draw of theta; 1/2 on the diagonal, 0 where s_ij = 0 and the values differ, NaN where either row is dead.
+    ``top_flip`` (n,): the same against the top row ``order[0]`` -- 0 for that row itself, NaN for dead rows.  ``zeta``,
+    ``sigma_n``, ``baseline`` (``gpr.y_max``), ``free``, ``scale``, ``device_ms`` (the two device calls)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        live = np.isfinite(self.acq)
+        top = np.nanmax(self.top_flip) if live.any() else np.nan
+        return (f"HyperAcqSpread(n_points={len(self.acq)}, live={int(live.sum())}, zeta={self.zeta:.3g}, "
+                f"max top_flip={top:.3g})")
+
+
+FLIP_MAX_ROWS = 256         # the (n, n) table of pairwise swap probabilities is given up to this many rows
+
+
+def _phi_neg(z):
+    """Phi(-z), the standard normal's lower tail, elementwise (NaN stays NaN)."""
+    from math import erfc
+    return 0.5 * np.vectorize(erfc, otypes=[float])(np.asarray(z, dtype=float) / np.sqrt(2.0))
+
+
+def _swap_probability(a_i, a_j, s):
+    """Phi(-|a_i - a_j| / s) with the limits at s = 0: 1/2 where the values are equal too, 0 where they differ."""
+    gap = np.abs(a_i - a_j)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.where(s > 0.0, gap / s, np.where(gap > 0.0, np.inf, 0.0))
+    return _phi_neg(np.where(np.isnan(gap) | np.isnan(s), np.nan, z))
+
+
+def acq_spread_fields(mean, var, G_mean, G_var, cov_free, free, zeta, sigma_n, baseline, scale=1.0):
+    """The fields of ``HyperAcqSpread`` that are arithmetic on the two device results: a dict.  ``cov_free`` (k, k): the
+    covariance of theta over the ``free`` entries (p,) bool.  Kept apart from the device calls so that it can be checked
+    on the host alone."""
+    mean, var = np.asarray(mean, dtype=float), np.asarray(var, dtype=float)
+    G_mean, G_var = np.asarray(G_mean, dtype=float), np.asarray(G_var, dtype=float)
+    free = np.asarray(free, dtype=bool)
+    S = float(scale) ** 2 * np.asarray(cov_free, dtype=float)
+    n = len(mean)
+
+    def spread(G):
+        Gf = G[:, free]
+        return np.sqrt(np.maximum(np.einsum("if,fg,ig->i", Gf, S, Gf), 0.0))
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sigma = np.sqrt(np.maximum(var, 0.0))
+        sigma_rel_theta = np.where(var > 0.0, spread(G_var) / (2.0 * var), np.nan)
+        excess = var - sigma_n ** 2
+        live = (excess > 0.0) & np.isfinite(mean)
+        acq = np.where(live, 2.0 * zeta * (mean - baseline) + 0.5 * np.log(np.where(live, excess, 1.0)), -np.inf)
+        acq_grad = np.full(G_var.shape, np.nan)
+        acq_grad[live] = 2.0 * zeta * G_mean[live] + G_var[live] / (2.0 * excess[live])[:, None]
+    acq_sigma_theta = np.full(n, np.nan)
+    acq_sigma_theta[live] = spread(acq_grad[live])
+    order = np.argsort(-acq, kind="stable")
+    a_nan = np.where(live, acq, np.nan)
+    Af = acq_grad[:, free]
+
+    def pair_sd(Di):                                    # sqrt(D S D^T) row by row
+        return np.sqrt(np.maximum(np.einsum("...f,fg,...g->...", Di, S, Di), 0.0))
+
+    flip = None
+    if n <= FLIP_MAX_ROWS:
+        flip = _swap_probability(a_nan[:, None], a_nan[None, :], pair_sd(Af[:, None, :] - Af[None, :, :]))
+    top_flip = np.full(n, np.nan)
+    if live.any():
+        top = int(order[0])
+        top_flip = _swap_probability(a_nan, a_nan[top], pair_sd(Af - Af[top][None, :]))
+        top_flip[top] = 0.0
+    return dict(sigma=sigma, sigma_mean_theta=spread(G_mean), sigma_rel_theta=sigma_rel_theta, acq=acq, acq_grad=acq_grad,
+                acq_sigma_theta=acq_sigma_theta, order=order, flip=flip, top_flip=top_flip)
+
+
+def hyper_acq_spread(gpr, X, acq=None, laplace=None, scale=1.0):
+    """Would another plausible theta have ranked these proposals differently?  At the rows of ``X`` (n, d) -- a NORA
+    shortlist, the last proposals -- the spread of sigma and of the LogExp acquisition
+    2 zeta (mean - y_max) + log(sigma^2 - sigma_n^2) / 2 under the Laplace Gaussian of ``hyper_laplace`` (``laplace``: a
+    ``HyperLaplace``; None: ``hyper_laplace(gpr)``; ``scale`` multiplies its standard deviations), and the probability
+    that two rows swap rank.  Two device calls, ``gpr.mean_theta_grad(full=True)`` and ``gpr.var_theta_grad(full=True)``
+    (closed forms, no refactorisation; models of more than 4096 padded rows are refused by the latter).  zeta and sigma_n
+    come from ``acq``, a ``gpry_amd.acquisition_functions.LogExp`` (None: ``LogExp(dimension=d)``), sigma_n resolved as
+    ``LogExp`` resolves it for the value (its own, else the mean of ``gpr.noise_level``); the baseline is ``gpr.y_max``.
+    A row whose variance does not exceed sigma_n^2 or whose mean is not finite (a gated row) is dead, as for the
+    acquisition itself: ``acq`` -inf, its derivative NaN.
+
+    FIRST ORDER ONLY: every figure is the linearisation of mean and variance in theta at the fitted theta, carried through
+    a Gaussian -- good while ``acq_sigma_theta`` is well below 1 and theta's Gaussian is narrow.  The exact route is
+    ``gpr.predict_thetas(X, thetas, return_std=True)`` over draws of theta (``hyper_predict``'s call), one
+    refactorisation per draw.  A report: it warns of nothing, gates nothing and changes no default.
+
+    Raises the ValueErrors of ``hyper_spread`` when ``laplace.negdef`` is false (there is no covariance) or no entry of
+    theta is free.  Returns a ``HyperAcqSpread``."""
+    from gpry_amd.acquisition_functions import LogExp
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    scale = float(scale)
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError(f"scale must be positive and finite (got {scale})")
+    lap = hyper_laplace(gpr) if laplace is None else laplace
+    if not lap.negdef or lap.cov is None:
+        raise ValueError("hyper_acq_spread: negdef is False -- minus the Hessian of the log marginal likelihood over the free "
+                         "entries is not positive definite, there is no covariance of theta to draw from")
+    free = np.asarray(lap.free, dtype=bool)
+    if int(free.sum()) == 0:
+        raise ValueError("hyper_acq_spread: no entry of theta is free (all are fixed or held by a bound): nothing to draw")
+    acq = LogExp(dimension=X.shape[1]) if acq is None else acq
+    zeta, sigma_n = float(acq.zeta), float(acq._noise(gpr)[0])
+    rm = gpr._mean_theta_grad_full(X)
+    rv = gpr._var_theta_grad_full(X)
+    G_mean, G_var = np.asarray(rm["G"], dtype=float), np.asarray(rv["G"], dtype=float)
+    if G_var.shape != (len(X), len(free)):
+        raise ValueError(f"hyper_acq_spread: the Laplace report has {len(free)} entries of theta, the model {G_var.shape[1]}")
+    mean, var = np.asarray(rm["y"], dtype=float), np.asarray(rv["var"], dtype=float)
+    baseline = float(gpr.y_max)
+    fields = acq_spread_fields(mean, var, G_mean, G_var, lap.cov, free, zeta, sigma_n, baseline, scale)
+    return HyperAcqSpread(mean=mean, var=var, G_mean=G_mean, G_var=G_var, zeta=zeta, sigma_n=sigma_n, baseline=baseline,
+                          free=free, scale=scale, device_ms=rm["device_ms"] + rv["device_ms"], **fields)

@@ -18,6 +18,7 @@ from gpry_amd.maximize import (hessian_gp, laplace_covmat, laplace_gp, maximize_
 from gpry_amd.hyper import HyperLaplace, hyper_laplace  # noqa: F401  (... and the curvature of the marginal likelihood in theta)
 from gpry_amd.hyper import HyperSpread, hyper_spread  # noqa: F401  (... and what it does to the posterior: to first order, or with exact=True refactorised per draw)
 from gpry_amd.hyper import reweight as _reweight
+from gpry_amd.hyper import HyperAcqSpread, hyper_acq_spread  # noqa: F401  (... and to sigma and the LogExp acquisition at given points: would another plausible theta rank them differently)
 from gpry_amd.hyper import HyperPredict, hyper_predict  # noqa: F401  (... and to the error bar at a point: mean and sigma with theta marginalised)
 from gpry_amd.tools import generic_params_names, get_Xnumber
 

@@ -789,6 +789,46 @@ int gpry_predict_thetas_var(gpry_ctx* ctx, const double* thetas, int64_t B, cons
 int gpry_predict_without(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, int64_t ngroups, const double* X, int64_t M,
                          double* dmean, double* dvar, int* info, double* device_ms);
 
+/* ---- The derivative of the latent predictive variance in theta at a batch of points (var_theta_grad.hip; gpry_amd/gpr.py:
+ * var_theta_grad, gpry_amd/hyper.py: hyper_acq_spread).  theta, K, h, diff and dk_ia = d k_i / d log l_a = C h(r_i) diff_ia^2 as
+ * for gpry_mean_theta_grad, at the theta of the factor the context holds; dK_a = dK / dlog l_a is the same expression between
+ * training rows (zero diagonal).  With k = k*(x), t = V k, q = K^-1 k = V^T t and var(x) = y_std^2 (C + w - |t|^2):
+ *   G_0(x) = y_std^2 ((C - |t|^2) - sum_i (alpha_i + w) q_i^2)        log C
+ *   G_a(x) = y_std^2 (-2 sum_i q_i dk_ia + q^T dK_a q)                log l_a
+ *   G_w(x) = y_std^2 w (1 + |q|^2)                                    log w
+ * The log C entry uses q^T (C phi) q = q^T k - q^T diag(alpha + w) q and is formed as written, never as C - 2 k^T q + q^T (C phi) q,
+ * which cancels to nothing next to a training point.  No factorisation: once per call the d matrices dK_a among the training
+ * rows (the pairs kernel of gpry_lml_hessian), then per panel of gpry_var_theta_grad_panel(ctx) points the cross-kernel panel of
+ * gpry_predict_thetas_var, T = V K* and Q = V^T T over the triangular k-ranges of the FP64 MFMA engine of gemm_f64.hip, the d
+ * products dK_a Q in one batched launch of the same engine and one FP64 vector kernel that forms the sums above per point:
+ * (2 + 2 d) N^2 flop per point on the matrix pipe.
+ * X (npts x d, raw coordinates where the affine map has an x-affine, as for gpry_mean_theta_grad); npts is unbounded (panels
+ * inside chunks of 65536 points).  Outputs:
+ *   var_out (npts, nullable)      y_std^2 (C + w - |V k|^2), the latent variance of gpry_predict_thetas_var: not clamped at 0,
+ *                                 not clipped, not gated;
+ *   G_out (npts x p, row-major)   d var / d theta in units of y^2 per unit of log theta; finite everywhere.  A point so far away
+ *                                 that k underflows gives exactly [y_std^2 C, 0 .., y_std^2 w].
+ * Every sum has a fixed order: the bits of var and G depend on the model and the point alone, not on npts, the point's
+ * position, the other points of its panel, how a batch is split over calls, or the context.  They are not the bits of any
+ * other call's variance.
+ * Refused (-1, with gpry_last_error) before anything runs: a NULL X or G_out; npts < 1; no valid factor; d > 32; a model above
+ * 4096 padded rows (d squares of scratch, gpry_lml_hessian's limit); a coordinate that is not finite.  After a refusal the
+ * context answers the next call as before.
+ * State contract: works on a factor grown by gpry_append_rows; stops the resident predict kernel first; reads V, the scaled
+ * training rows, the noise vector and the affine map only; writes a scratch of its own (d Np^2 doubles for the dK_a and
+ * (3 + d) Np pc and the row slices' sums for a panel of pc <= gpry_var_theta_grad_panel(ctx) points, released with the context, and by gpry_set_train when
+ * the model falls below half the footprint it was sized for) and the samplers' staging buffer.  The state of gpry_predict, a
+ * sweep, a Kriging-believer session, the gates, the scratch of gpry_lml_hessian, gpry_mean_theta_grad, gpry_loo and
+ * gpry_predict_without and the factor cache of gpry_lml are not touched.  Stage timers: "var_theta_grad_setup" (the dK_a),
+ * "var_theta_grad" (a panel) and, inside it, "var_theta_grad_panel", "var_theta_grad_solve" (T and Q),
+ * "var_theta_grad_products" (the batched launch) and "var_theta_grad_finish".  device_ms (nullable): device time of the
+ * call, copies included. */
+#define GPRY_VAR_THETA_GRAD_PANEL 1024      /* the narrowest panel */
+int gpry_var_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* var_out, double* G_out, double* device_ms);
+/* points per panel of gpry_var_theta_grad for the model the context holds, a function of its padded size alone: 4096 up to
+ * 1024 padded rows, 2048 up to 2048, GPRY_VAR_THETA_GRAD_PANEL above (and for a NULL context) */
+int64_t gpry_var_theta_grad_panel(gpry_ctx* ctx);
+
 /* ---- f3: x-gradients for one point (gpry/gpr.py:1236-1266) ------------------------- */
 /* x: d doubles, raw/transformed as in gpry_predict.  With G[j][k] = d k(x, X_j) / d x_k in the
  * kernel's coordinates (kernel_.gradient_x: gpry/kernels.py:257-278 RBF, :326-432 Matern,
