@@ -252,25 +252,14 @@ struct gpry_ctx {
     int64_t gidx_cap = 0;
     uint8_t* dmc = nullptr;            // gpry_mcmc_chains: start states, proposal factor and outputs (bytes)
     int64_t mc_cap = 0;
-    uint8_t* dknn = nullptr;           // gpry_ns_knn: transposed unit-cube points and the neighbour table (bytes)
-    int64_t knn_cap = 0;
-    uint8_t* dph = nullptr;            // gpry_ns_generation_phantoms: the chains' recorded states and their y (bytes)
-    int64_t ph_cap = 0;
-    uint8_t* djoint = nullptr;         // gpry_predict_cov / gpry_sample_joint: panel, U, the two m-padded squares, draws (bytes)
-    int64_t joint_cap = 0;
-    uint8_t* dloo = nullptr;           // gpry_loo / gpry_leave_out: partial sums of the pass over V, partial Grams, outputs (bytes)
-    int64_t loo_cap = 0;
+    // The call scratch (CallScratch below): the private device buffer of whichever entry point is running -- gpry_ns_knn,
+    // gpry_ns_generation_phantoms, gpry_predict_cov / gpry_sample_joint, gpry_loo / gpry_leave_out, gpry_lml_hessian,
+    // gpry_mean_theta_grad, gpry_predict_without, gpry_var_theta_grad, gpry_svm_fit.  Written and read between a call's
+    // entry and its last stream synchronisation; no call reads what another left.
+    uint8_t* dscratch = nullptr;       // bytes
+    int64_t scratch_cap = 0, scratch_np = 0;    // ... and Np of the model when it last grew (ensure_capacity gives it back by that)
+    const char* scratch_holder = nullptr;   // the entry point that holds it now (NULL: nobody)
     void* hloo = nullptr; int64_t hloo_cap = 0;    // gpry_loo: pinned landing place of its five output rows (bytes)
-    double* dhess = nullptr;           // gpry_lml_hessian: full-square K^-1, the d matrices K_i and K^-1 K_i, partial sums (doubles)
-    int64_t hess_cap = 0;
-    double* dtg = nullptr;             // gpry_mean_theta_grad: the right-hand sides U, T = V U and W = K^-1 U of one call (doubles)
-    int64_t tg_cap = 0;
-    uint8_t* dpw = nullptr;            // gpry_predict_without: the stacked group rows VG, P, S, the panel, s, slices, outputs (bytes; predict_without.hip)
-    int64_t pw_cap = 0, pw_np = 0;     // ... and the padded model size it was last used with
-    double* dvtg = nullptr;            // gpry_var_theta_grad: the d matrices dK / dlog l_a, the panel, T, Q and the d products of a panel (doubles; var_theta_grad.hip)
-    int64_t vtg_cap = 0;
-    uint8_t* dsvm = nullptr;           // gpry_svm_fit: coordinate-major training set, alpha, gradient, labels, status block (bytes)
-    int64_t svm_cap = 0;
     void* hsvm = nullptr; int64_t hsvm_cap = 0;    // gpry_svm_fit: pinned image of its upload (bytes)
     int64_t opt_svm_iters = 4096;      // gpry_svm_fit: steps of one launch of the solver (the result does not depend on it)
 
@@ -336,6 +325,40 @@ int dev_grow(gpry_ctx* ctx, T** p, int64_t* cap, int64_t need) {
     *cap = need;
     return 0;
 }
+
+// The call scratch of the context (gpry_ctx::dscratch), held by one entry point at a time.  The caller names its regions
+// with take<T>(count) -- they lie end to end on 256-byte boundaries, in the order taken -- then claim()s: an arena that
+// somebody holds is an internal error (one claimant called another), else the buffer grows as dev_grow grows (stream
+// drained, contents not kept).  at() gives a region's device pointer, NULL for a region of no elements.  The destructor
+// lets go on every return path; what the holder queued on a side stream it has joined into ctx->stream by then, so the
+// next holder's launches are ordered behind it by the stream.
+struct CallScratch {
+    template <class T> struct Reg { int i; };
+    static const int CAP = 20;
+    gpry_ctx* ctx; const char* who;
+    int64_t bytes[CAP + 1], off[CAP + 1];      // (slot CAP: where a region beyond the capacity lands; claim() then fails)
+    int n = 0; int64_t total = 0; bool held = false;
+
+    CallScratch(gpry_ctx* c, const char* w) : ctx(c), who(w) {}
+    ~CallScratch() { if (held) ctx->scratch_holder = nullptr; }
+    template <class T> Reg<T> take(int64_t count) {
+        const int i = n < CAP ? n : CAP;
+        bytes[i] = (int64_t)sizeof(T) * count; off[i] = total;
+        total += round_up(bytes[i], 256);
+        n++;
+        return {i};
+    }
+    int claim() {
+        if (n > CAP) return gpry_fail(ctx, -1, "%s: %d scratch regions, the table holds %d", who, n, CAP);
+        if (ctx->scratch_holder)
+            return gpry_fail(ctx, -1, "%s: the call scratch is held by %s (internal error)", who, ctx->scratch_holder);
+        if (total > ctx->scratch_cap) ctx->scratch_np = ctx->Np;
+        GPRY_TRY(dev_grow(ctx, &ctx->dscratch, &ctx->scratch_cap, total));
+        ctx->scratch_holder = who; held = true;
+        return 0;
+    }
+    template <class T> T* at(Reg<T> h) const { return bytes[h.i] > 0 ? (T*)(ctx->dscratch + off[h.i]) : nullptr; }
+};
 
 // the buffer of theta `tb` in a batched launch (see gpry_ctx::bn): every per-theta pointer moves by tb * bstride doubles
 // (pointer arithmetic, not integer arithmetic: the result keeps the provenance of a kernel argument, i.e. global loads

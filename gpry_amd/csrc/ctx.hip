@@ -162,23 +162,12 @@ int ensure_capacity(gpry_ctx* ctx, int64_t N, int d) {
         (void)hipFree(ctx->barena);
         ctx->barena = nullptr; ctx->barena_cap = 0;
     }
-    // the scratch of gpry_lml_hessian, (1 + 2 d) Np^2 doubles, by the same rule
-    if (ctx->dhess && 2 * (1 + 2 * (int64_t)d) * Np * Np < ctx->hess_cap) {
+    // the call scratch (CallScratch; its largest users hold multiples of Np^2 doubles), by the same rule against the model
+    // it last grew under
+    if (ctx->dscratch && 2 * Np * Np < ctx->scratch_np * ctx->scratch_np) {
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->dhess);
-        ctx->dhess = nullptr; ctx->hess_cap = 0;
-    }
-    // the scratch of gpry_predict_without grows linearly with Np: given back below half the size it was last used with
-    if (ctx->dpw && 2 * Np < ctx->pw_np) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->dpw);
-        ctx->dpw = nullptr; ctx->pw_cap = 0; ctx->pw_np = 0;
-    }
-    // the scratch of gpry_var_theta_grad, d Np^2 doubles and the panels behind them, by the rule of gpry_lml_hessian's
-    if (ctx->dvtg && 2 * (2 + (int64_t)d) * Np * Np < ctx->vtg_cap) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(ctx->dvtg);
-        ctx->dvtg = nullptr; ctx->vtg_cap = 0;
+        (void)hipFree(ctx->dscratch);
+        ctx->dscratch = nullptr; ctx->scratch_cap = 0; ctx->scratch_np = 0;
     }
     ctx->N = N; ctx->Np = Np; ctx->d = d; ctx->dpad = dpad;
     return 0;
@@ -265,8 +254,8 @@ int gpry_ctx_destroy(gpry_ctx* ctx) {
                     ctx->dcand, ctx->dsel, ctx->dU, ctx->dXkb, ctx->dkbout, ctx->pr.dXc, ctx->pr.dmask,
                     ctx->pr.dy, ctx->pr.dsig, ctx->pr.dacq, ctx->dG,
                     ctx->gate_sv, ctx->gate_coef, ctx->gate_trust, ctx->dsplit, ctx->dbord, ctx->barena, ctx->dXcs, ctx->dYcs,
-                    ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc, ctx->dknn,
-                    ctx->dph, ctx->djoint, ctx->dloo, ctx->dsvm, ctx->dhess, ctx->dtg, ctx->dpw, ctx->dvtg};
+                    ctx->dub, ctx->dXg, ctx->dgidx, ctx->snap.dV, ctx->snap.dalpha_, ctx->snap.dXs, ctx->snap.dX, ctx->dmc,
+                    ctx->dscratch};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (ctx->hpin) (void)hipHostFree(ctx->hpin);
     if (ctx->hloo) (void)hipHostFree(ctx->hloo);
@@ -458,6 +447,7 @@ int gpry_timing_get(gpry_ctx* ctx, const char* name, double* total_ms, int64_t* 
     // (not timers either: what ensure_capacity has allocated, in training rows and in padded columns)
     if (name && !strcmp(name, "capacity_rows")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->cap; return 0; }
     if (name && !strcmp(name, "capacity_cols")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->dp_cap; return 0; }
+    if (name && !strcmp(name, "scratch_bytes")) { if (total_ms) *total_ms = 0.0; if (count) *count = ctx->scratch_cap; return 0; }
     timers_collect(ctx);
     auto it = ctx->timers.find(name);
     if (it == ctx->timers.end()) { if (total_ms) *total_ms = 0.0; if (count) *count = 0; return -1; }

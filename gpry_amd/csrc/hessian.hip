@@ -168,9 +168,7 @@ int gpry_hessian_mean(gpry_ctx* ctx, const double* X, int64_t npts, double* y_ou
                                   "training rows; it has no Hessian");
     const int d = ctx->d;
     const int64_t n = npts;
-    for (int64_t e = 0; e < n * d; e++)
-        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "gpry_hessian_mean: a coordinate of point %lld is not finite",
-                                              (long long)(e / d));
+    GPRY_TRY(check_points_finite(ctx, "gpry_hessian_mean", X, n));
     // (the mean needs no box: ns_args is handed the unit one)
     double lo[GPRY_MAX_DIM], hi[GPRY_MAX_DIM];
     for (int k = 0; k < GPRY_MAX_DIM; k++) { lo[k] = 0.0; hi[k] = 1.0; }

@@ -166,6 +166,8 @@ __global__ __launch_bounds__(256) void joint_product_kernel(const double* __rest
 namespace {
 
 struct JointWork {
+    CallScratch cs;                  // held from joint_cov to the end of the entry point that owns this
+    JointWork(gpry_ctx* ctx, const char* who) : cs(ctx, who) {}
     int64_t m = 0, mp = 0;
     int ntm = 0;
     double *X = nullptr, *Xs = nullptr, *Kst = nullptr, *U = nullptr, *mpart = nullptr, *mu = nullptr, *Sig = nullptr,
@@ -185,9 +187,7 @@ int joint_check(gpry_ctx* ctx, const char* who, const double* X, int64_t m) {
     if (!X) return gpry_fail(ctx, -1, "%s: X is NULL", who);
     if (m < 1 || m > JOINT_MAX_M) return gpry_fail(ctx, -1, "%s: m = %lld, need 1 <= m <= %d", who, (long long)m, JOINT_MAX_M);
     if (ctx->d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "%s: d = %d > %d", who, ctx->d, GPRY_MAX_DIM);
-    for (int64_t e = 0; e < m * ctx->d; e++)
-        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "%s: a coordinate of point %lld is not finite", who, (long long)(e / ctx->d));
-    return 0;
+    return check_points_finite(ctx, who, X, m);
 }
 
 // everything up to Sigma and mu on the device (queued on ctx->stream; the merged mask is on the host when this returns)
@@ -197,19 +197,21 @@ int joint_cov(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* mask, in
     const int d = ctx->d, dpad = ctx->dpad, nt = (int)(Np / 128);
     const bool small_build = mp <= 512;
     w->m = m; w->mp = mp; w->ntm = small_build ? 4 * nt : nt;
-    // one buffer: points | scaled points | k* panel | U | mean partials | mu | Sigma | L_c | Y | Z | mask
-    const int64_t sz[11] = {8 * m * d, 8 * mp * dpad, 8 * Np * mp, 8 * Np * mp, 8 * (int64_t)w->ntm * mp, 8 * mp, 8 * mp * mp,
-                            S > 0 ? 8 * mp * mp : 0, 8 * S * m, want_z ? 8 * S * m : 0, mp};
-    int64_t off[12];
-    ns_layout(sz, off);
-    GPRY_TRY(dev_grow(ctx, &ctx->djoint, &ctx->joint_cap, off[11]));
-    char* b = (char*)ctx->djoint;
-    w->X = (double*)(b + off[0]); w->Xs = (double*)(b + off[1]); w->Kst = (double*)(b + off[2]); w->U = (double*)(b + off[3]);
-    w->mpart = (double*)(b + off[4]); w->mu = (double*)(b + off[5]); w->Sig = (double*)(b + off[6]); w->Lc = (double*)(b + off[7]);
-    w->Y = (double*)(b + off[8]); w->Z = want_z ? (double*)(b + off[9]) : nullptr; w->mask = (uint8_t*)(b + off[10]);
+    // The call scratch, in this order.  Nothing below claims it again (the panel builders, the GEMM engine and, in
+    // gpry_sample_joint, potrf_lower_overlap take their buffers from the caller or from dsplit), and every launch and copy
+    // of the two entry points is on ctx->stream, which they drain (ns_end) before the claim ends.
+    CallScratch& cs = w->cs;
+    const auto rX = cs.take<double>(m * d), rXs = cs.take<double>(mp * dpad), rKst = cs.take<double>(Np * mp),
+               rU = cs.take<double>(Np * mp), rmpart = cs.take<double>((int64_t)w->ntm * mp), rmu = cs.take<double>(mp),
+               rSig = cs.take<double>(mp * mp), rLc = cs.take<double>(S > 0 ? mp * mp : 0), rY = cs.take<double>(S * m),
+               rZ = cs.take<double>(want_z ? S * m : 0);
+    const auto rmask = cs.take<uint8_t>(mp);
+    GPRY_TRY(cs.claim());
+    w->X = cs.at(rX); w->Xs = cs.at(rXs); w->Kst = cs.at(rKst); w->U = cs.at(rU); w->mpart = cs.at(rmpart); w->mu = cs.at(rmu);
+    w->Sig = cs.at(rSig); w->Lc = cs.at(rLc); w->Y = cs.at(rY); w->Z = cs.at(rZ); w->mask = cs.at(rmask);
     w->hmask.assign((size_t)mp, 0);
     if (mask) memcpy(w->hmask.data(), mask, (size_t)m);
-    HIP_TRY(ctx, hipMemcpyAsync(w->X, X, sz[0], hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(w->X, X, sizeof(double) * m * d, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(w->mask, w->hmask.data(), (size_t)mp, hipMemcpyHostToDevice, st));
     if (ctx->gates_on && ctx->opt_predict_gates) {
         GPRY_TRY(launch_gates(ctx, w->X, m, w->mask));
@@ -280,7 +282,7 @@ int gpry_predict_cov(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* m
     GPRY_TRY(joint_check(ctx, "gpry_predict_cov", X, m));
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    JointWork w;
+    JointWork w(ctx, "gpry_predict_cov");
     std::vector<double> hmu;
     {
         StageScope scope(ctx, "predict_cov");
@@ -311,7 +313,7 @@ int gpry_sample_joint(gpry_ctx* ctx, const double* X, int64_t m, const uint8_t* 
     if (info) *info = 0;
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    JointWork w;
+    JointWork w(ctx, "gpry_sample_joint");
     hipStream_t st = ctx->stream;
     const double unit = exp(ctx->theta[0]) * ctx->tf.y_std * ctx->tf.y_std;       // eps is in units of C y_std^2
     double eps = jitter < 0.0 ? 1e-10 : jitter;

@@ -20,8 +20,9 @@
 //   (f) lml_hess_finish_kernel: one workgroup per entry i <= j adds the per-tile partial sums by a strided pass and a fixed
 //       LDS tree, assembles H and writes it and its mirror image into mapped host memory.
 // Tile maps and summation orders are functions of (N, d, kernel) alone.  The evaluation works in the objective's scratch
-// (dW, dW2, dW3, dvec, dpart, dsplit) and in ctx->dhess: the factor held for prediction, a Kriging-believer session, the
-// resident pool and ctx->dloo are not touched; the factor cache of gpry_lml is cleared.
+// (dW, dW2, dW3, dvec, dpart, dsplit) and in the call scratch (CallScratch, common.h), which it holds until it has waited
+// for the chain: the factor held for prediction, a Kriging-believer session and the resident pool are not touched; the
+// factor cache of gpry_lml is cleared.
 #include "kern_math.h"
 
 #define LH_T 64
@@ -30,10 +31,6 @@
 #define LH_INFO LML_RES_INFO             // host result: gpry_lml's row [logdet/2, quad, grad ...], status words from here
 #define LH_HOFF 1024                     // ... and H, p x p row-major, from here (behind the units of the single-launch objective)
 #define LH_MAX_NP 4096
-// the batch items of the product (one per length scale) close the scratch: their area in doubles
-#define LH_ITEM_DOUBLES ((int64_t)((GPRY_MAX_DIM * sizeof(GemmBatchItem) + 7) / 8))
-static_assert(LH_ITEM_DOUBLES * 8 >= GPRY_MAX_DIM * sizeof(GemmBatchItem) && sizeof(GemmBatchItem) % 8 == 0,
-              "the item area must hold one GemmBatchItem per dimension");
 
 namespace {
 
@@ -421,43 +418,43 @@ int lml_hess_km_launch(gpry_ctx* ctx, double* Km) {
 
 namespace {
 
-// sizes and offsets (doubles) of ctx->dhess -- functions of the model size alone
+// tile counts of the stages -- functions of the model size alone
 struct LmlHessPlan {
     int nb, NB2, MB, nsplit, p;
-    int64_t ntile, o_kf, o_km, o_bm, o_gp, o_mv, o_r, o_u, o_tp, o_items, need;
+    int64_t ntile;
 };
 LmlHessPlan lml_hess_plan(const gpry_ctx* ctx) {
     LmlHessPlan q;
-    const int64_t Np = ctx->Np, sq = Np * Np;
+    const int64_t Np = ctx->Np;
     const int d = ctx->d;
     q.p = ctx_ntheta(ctx);
     q.nb = (int)(Np / LH_T);
     q.ntile = (int64_t)q.nb * (q.nb + 1) / 2;
     q.NB2 = d <= 16 ? 1 : 3;            // accumulator tiles of the weighted Gram: one block of 16 coordinates, or two
     q.MB = (d + 2 + 15) / 16;           // matrix indices 0 .. d + 1
-    q.o_kf = 0; q.o_km = sq; q.o_bm = q.o_km + d * sq;
-    q.o_gp = q.o_bm + d * sq;
-    q.o_mv = q.o_gp + (int64_t)q.nb * q.nb * q.NB2 * 256;
-    q.o_r = q.o_mv + (int64_t)q.nb * d * Np;
-    q.o_u = q.o_r + (int64_t)(d + 2) * Np;
-    q.o_tp = q.o_u + (int64_t)(d + 2) * Np;
-    q.o_items = q.o_tp + q.ntile * (q.MB * 16) * (q.MB * 16);
-    q.need = q.o_items + LH_ITEM_DOUBLES;
     // split-K of the batched product: only where the d * (Np / 128)^2 tiles leave most of the GPU idle
     q.nsplit = splitk_count((int64_t)d * (Np / 128) * (Np / 128), Np);
     return q;
 }
 
-int lml_hess_chain(gpry_ctx* ctx, double* dres) {
-    const int64_t Np = ctx->Np, N = ctx->N;
+// cs: the caller's claim of the call scratch, which it holds until it has waited for the chain
+int lml_hess_chain(gpry_ctx* ctx, CallScratch& cs, double* dres) {
+    const int64_t Np = ctx->Np, N = ctx->N, sq = Np * Np;
     const int d = ctx->d;
     const LmlHessPlan pl = lml_hess_plan(ctx);
-    // the scratch of its own is sized before the first launch
-    GPRY_TRY(dev_grow(ctx, &ctx->dhess, &ctx->hess_cap, pl.need));
-    double* hb = ctx->dhess;
-    double *Kf = hb + pl.o_kf, *Km = hb + pl.o_km, *Bm = hb + pl.o_bm, *gp = hb + pl.o_gp, *mv = hb + pl.o_mv, *R = hb + pl.o_r,
-           *U = hb + pl.o_u, *tp = hb + pl.o_tp;
-    GemmBatchItem* items = reinterpret_cast<GemmBatchItem*>(hb + pl.o_items);
+    // The call scratch, claimed before the first launch: K^-1 as a full square, the d matrices K_i and K^-1 K_i, the partial
+    // sums of the stages, the batch items of the product (one per length scale).  lml_chain and the GEMM engine work in the
+    // objective's own buffers and claim nothing; what the factor chain queues on the side stream it joins into ctx->stream
+    // before it returns, and nothing of the scratch is touched there.
+    const auto rKf = cs.take<double>(sq), rKm = cs.take<double>(d * sq), rBm = cs.take<double>(d * sq),
+               rgp = cs.take<double>((int64_t)pl.nb * pl.nb * pl.NB2 * 256), rmv = cs.take<double>((int64_t)pl.nb * d * Np),
+               rR = cs.take<double>((int64_t)(d + 2) * Np), rU = cs.take<double>((int64_t)(d + 2) * Np),
+               rtp = cs.take<double>(pl.ntile * (pl.MB * 16) * (pl.MB * 16));
+    const auto ritems = cs.take<GemmBatchItem>(GPRY_MAX_DIM);
+    GPRY_TRY(cs.claim());
+    double *Kf = cs.at(rKf), *Km = cs.at(rKm), *Bm = cs.at(rBm), *gp = cs.at(rgp), *mv = cs.at(rmv), *R = cs.at(rR), *U = cs.at(rU),
+           *tp = cs.at(rtp);
+    GemmBatchItem* items = cs.at(ritems);
     hipStream_t st = ctx->stream;
     // (a) gpry_lml's chain with gradient -- the very function, hence its bits: L in dW, V in dW2, K^-1 (lower) in dW3, alpha and
     // [logdet/2, quad, grad ...] in dvec; value, gradient and status in gpry_lml's row of `dres`
@@ -556,8 +553,9 @@ int gpry_lml_hessian(gpry_ctx* ctx, const double* theta, double* lml, double* gr
         fused = r == 0;
     }
     const bool ran = rc == 0 && !(fused && finfo != 0);
+    CallScratch cs(ctx, "gpry_lml_hessian");
     if (ran) {
-        rc = lml_hess_chain(ctx, dres);
+        rc = lml_hess_chain(ctx, cs, dres);
         at.factor_chain_ran();
     }
     if (ev1 && rc == 0) (void)hipEventRecord(ev1, ctx->stream);

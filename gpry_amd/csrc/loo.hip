@@ -23,8 +23,9 @@
 // the same bits whatever other groups share the call and wherever it stands in the list.  gpry_predict_without
 // (predict_without.hip) runs the same two kernels through lgo.h and takes W and z = W alpha_G from the finish.
 //
-// Both read V, alpha_, y_ and the noise vector and write to a buffer of their own (ctx->dloo): the state of predict, of
-// the sweep, of a Kriging-believer session and of the samplers is not touched.
+// Both read V, alpha_, y_ and the noise vector and write to the call scratch alone (CallScratch, common.h), which each holds
+// for the length of the call: the state of predict, of the sweep, of a Kriging-believer session and of the samplers is not
+// touched.
 #include "ns_common.h"
 #include "chol16.h"
 #include "lgo.h"
@@ -348,17 +349,19 @@ int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* 
     const int nt = (int)((N + LOO_T - 1) / LOO_T);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    const int64_t sz[3] = {8 * (int64_t)nt * Np, 8 * (int64_t)nt * Np, 8 * 5 * N};
-    int64_t off[4];
-    ns_layout(sz, off);
-    GPRY_TRY(dev_grow(ctx, &ctx->dloo, &ctx->loo_cap, off[3]));
-    if (sz[2] > ctx->hloo_cap) {
+    // the call scratch: the two rows of partial sums of the pass over V, the five output rows.  The two kernels below are
+    // all this call launches, on ctx->stream, which ns_end drains.
+    CallScratch cs(ctx, "gpry_loo");
+    const auto rq = cs.take<double>((int64_t)nt * Np), rw = cs.take<double>((int64_t)nt * Np), rout = cs.take<double>(5 * N);
+    GPRY_TRY(cs.claim());
+    const int64_t out_bytes = 8 * 5 * N;
+    if (out_bytes > ctx->hloo_cap) {
         if (ctx->hloo) HIP_TRY(ctx, hipHostFree(ctx->hloo));
         ctx->hloo = nullptr; ctx->hloo_cap = 0;
-        HIP_TRY(ctx, hipHostMalloc(&ctx->hloo, (size_t)sz[2], hipHostMallocDefault));
-        ctx->hloo_cap = sz[2];
+        HIP_TRY(ctx, hipHostMalloc(&ctx->hloo, (size_t)out_bytes, hipHostMallocDefault));
+        ctx->hloo_cap = out_bytes;
     }
-    double *qpart = (double*)(ctx->dloo + off[0]), *wpart = (double*)(ctx->dloo + off[1]), *out = (double*)(ctx->dloo + off[2]);
+    double *qpart = cs.at(rq), *wpart = cs.at(rw), *out = cs.at(rout);
     hipStream_t st = ctx->stream;
     {
         StageScope scope(ctx, "loo");
@@ -368,7 +371,7 @@ int gpry_loo(gpry_ctx* ctx, double* mean, double* var_y, double* var_f, double* 
                            ctx->dalpha_, ctx->dnoise, ctx_white(ctx), ctx->white ? 1 : 0, ctx->tf.y_mean, ctx->tf.y_std, out);
         HIP_TRY(ctx, hipGetLastError());
         // one copy of the five rows into pinned memory of the call's own, handed out below
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hloo, out, sz[2], hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hloo, out, out_bytes, hipMemcpyDeviceToHost, st));
     }
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
     double* dst[5] = {mean, var_y, var_f, seq_mean, seq_var_y};
@@ -406,34 +409,32 @@ int gpry_leave_out(gpry_ctx* ctx, const int64_t* idx, const int64_t* offsets, in
     }
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
-    // one buffer: groups | sorted indices | mean | cov | chi2 | logpdf | info | partial Grams
-    const int64_t sz[8] = {(int64_t)sizeof(LgoGroup) * ngroups, 4 * nidx, 8 * nidx, 8 * ncov, 8 * ngroups, 8 * ngroups,
-                           4 * ngroups, 8 * part_max};
-    int64_t off[9];
-    ns_layout(sz, off);
-    GPRY_TRY(dev_grow(ctx, &ctx->dloo, &ctx->loo_cap, off[8]));
-    uint8_t* b = ctx->dloo;
-    LgoGroup* dgroups = (LgoGroup*)(b + off[0]);
-    int* didx = (int*)(b + off[1]);
-    double *dmean = (double*)(b + off[2]), *dcov = (double*)(b + off[3]), *dchi = (double*)(b + off[4]),
-           *dlp = (double*)(b + off[5]), *dpart = (double*)(b + off[7]);
-    int* dinfo = (int*)(b + off[6]);
+    // the call scratch, in this order.  lgo_launch takes every buffer from its caller, and all of the call is queued on
+    // ctx->stream, which ns_end drains.
+    CallScratch cs(ctx, "gpry_leave_out");
+    const auto rgroups = cs.take<LgoGroup>(ngroups); const auto ridx = cs.take<int>(nidx);
+    const auto rmean = cs.take<double>(nidx), rcov = cs.take<double>(ncov), rchi = cs.take<double>(ngroups), rlp = cs.take<double>(ngroups);
+    const auto rinfo = cs.take<int>(ngroups); const auto rpart = cs.take<double>(part_max);
+    GPRY_TRY(cs.claim());
+    LgoGroup* dgroups = cs.at(rgroups);
+    int *didx = cs.at(ridx), *dinfo = cs.at(rinfo);
+    double *dmean = cs.at(rmean), *dcov = cs.at(rcov), *dchi = cs.at(rchi), *dlp = cs.at(rlp), *dpart = cs.at(rpart);
     std::vector<double> hmean((size_t)nidx), hcov((size_t)ncov);
     hipStream_t st = ctx->stream;
     {
         StageScope scope(ctx, "leave_out");
-        HIP_TRY(ctx, hipMemcpyAsync(dgroups, groups.data(), sz[0], hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(didx, sidx.data(), sz[1], hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(dgroups, groups.data(), sizeof(LgoGroup) * ngroups, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(didx, sidx.data(), sizeof(int) * nidx, hipMemcpyHostToDevice, st));
         for (size_t bi = 0; bi + 1 < batch_first.size(); bi++) {
             const int64_t g0 = batch_first[bi], ng = batch_first[bi + 1] - g0;
             lgo_launch(ctx, didx, dgroups + g0, ng, dpart, dmean, dcov, dchi + g0, dlp + g0, dinfo + g0, nullptr, nullptr);
         }
         HIP_TRY(ctx, hipGetLastError());
-        if (mean) HIP_TRY(ctx, hipMemcpyAsync(hmean.data(), dmean, sz[2], hipMemcpyDeviceToHost, st));
-        if (cov) HIP_TRY(ctx, hipMemcpyAsync(hcov.data(), dcov, sz[3], hipMemcpyDeviceToHost, st));
-        if (chi2) HIP_TRY(ctx, hipMemcpyAsync(chi2, dchi, sz[4], hipMemcpyDeviceToHost, st));
-        if (logpdf) HIP_TRY(ctx, hipMemcpyAsync(logpdf, dlp, sz[5], hipMemcpyDeviceToHost, st));
-        if (info) HIP_TRY(ctx, hipMemcpyAsync(info, dinfo, sz[6], hipMemcpyDeviceToHost, st));
+        if (mean) HIP_TRY(ctx, hipMemcpyAsync(hmean.data(), dmean, sizeof(double) * nidx, hipMemcpyDeviceToHost, st));
+        if (cov) HIP_TRY(ctx, hipMemcpyAsync(hcov.data(), dcov, sizeof(double) * ncov, hipMemcpyDeviceToHost, st));
+        if (chi2) HIP_TRY(ctx, hipMemcpyAsync(chi2, dchi, sizeof(double) * ngroups, hipMemcpyDeviceToHost, st));
+        if (logpdf) HIP_TRY(ctx, hipMemcpyAsync(logpdf, dlp, sizeof(double) * ngroups, hipMemcpyDeviceToHost, st));
+        if (info) HIP_TRY(ctx, hipMemcpyAsync(info, dinfo, sizeof(int) * ngroups, hipMemcpyDeviceToHost, st));
     }
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
     // back to the caller's order inside every group

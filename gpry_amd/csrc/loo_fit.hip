@@ -26,7 +26,8 @@
 // B, its position in the batch, the chunking and its neighbours.
 //
 // The evaluation works in the objective's scratch (dW, dW2, dW3, dvec, dpart, dsplit) alone: the factor held for
-// prediction, a Kriging-believer session, the resident pool and ctx->dloo are not touched.  L and V of the scratch are
+// prediction, a Kriging-believer session and the resident pool are not touched, and the call scratch (CallScratch, common.h)
+// is not held.  L and V of the scratch are
 // overwritten (H, M), so the factor cache of gpry_lml is cleared: gpry_factorize never adopts them.
 #include "kern_math.h"
 

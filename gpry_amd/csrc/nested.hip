@@ -357,11 +357,9 @@ static int ns_generation_impl(gpry_ctx* ctx, const NsGenRequest& rq) {
     GPRY_TRY(ns_args(ctx, "nested sampler", rq.lo, rq.hi, rq.seed, &a, &kp, &ap));
     const int64_t d = ctx->d, n = rq.nsurv, k = rq.k, nc = rq.n_clusters, nw = rq.labels ? nc : 1;
     const bool lists = rq.cum_p != nullptr;
-    // phantoms: n_ph recorded states per chain, [X_ph | y_ph] in a device buffer of the context
+    // phantoms: n_ph recorded states per chain, [X_ph | y_ph] in the context's call scratch
     const int n_ph = rq.X_ph && rq.num_repeats > 0 ? (rq.num_repeats - 1) / rq.thin : 0;
     const int64_t psz[2] = {8 * k * n_ph * d, 8 * k * n_ph};
-    int64_t poff[3];
-    ns_layout(psz, poff);
     if (psz[0] + psz[1] > NS_PHANTOM_MAX_BYTES)
         return gpry_fail(ctx, -1, "%s: %d chains x %d phantoms x %d coordinates need %lld bytes, the limit is %lld", rq.who,
                          rq.k, n_ph, (int)d, (long long)(psz[0] + psz[1]), (long long)NS_PHANTOM_MAX_BYTES);
@@ -382,9 +380,13 @@ static int ns_generation_impl(gpry_ctx* ctx, const NsGenRequest& rq) {
     const auto rcnt = st.out(rq.ncalls, k);
     GPRY_TRY(st.begin());
     // ---- launch
-    if (rec) GPRY_TRY(dev_grow(ctx, &ctx->dph, &ctx->ph_cap, poff[2]));
-    double* dXp = rec ? (double*)ctx->dph : nullptr;
-    double* dyp = rec ? (double*)(ctx->dph + poff[1]) : nullptr;
+    // the call scratch: the phantoms alone, claimed only where they are recorded (a generation without them holds nothing, and
+    // both regions are empty).  Nothing else of this call claims it -- the stage lives in the pinned buffer -- and every
+    // launch and copy is on ctx->stream, which st.end() drains.
+    CallScratch cs(ctx, rq.who);
+    const auto rXp = cs.take<double>(rec ? k * n_ph * d : 0), ryp = cs.take<double>(rec ? k * n_ph : 0);
+    if (rec) GPRY_TRY(cs.claim());
+    double *dXp = cs.at(rXp), *dyp = cs.at(ryp);
     const NsGenDev g = {st.dev(rXs), st.dev(rys), st.dev(rW), st.dev(rlab), st.dev(rmem), st.dev(rmof), st.dev(rcp),
                         st.dev(rXn), st.dev(ryn), st.dev(rcnt), dXp, dyp};
     if (k > 0) ns_launch_chains(ctx, rq, a, kp, ap, g, (int)nw, n_ph);
@@ -491,12 +493,13 @@ int gpry_ns_knn(gpry_ctx* ctx, const double* lo, const double* hi, const double*
         if (!isfinite((X[e] - b.lo[c]) / (b.hi[c] - b.lo[c])))
             return gpry_fail(ctx, -1, "gpry_ns_knn: point %lld has a non-finite unit-cube coordinate %d", (long long)(e / d), c);
     }
-    const int64_t bu = round_up(sizeof(double) * n * d, 256), bx = round_up(sizeof(double) * n * d, 256),
-                  bn = round_up(sizeof(int32_t) * n * k, 256);
-    GPRY_TRY(dev_grow(ctx, &ctx->dknn, &ctx->knn_cap, bu + bx + bn));
-    double* dUT = (double*)ctx->dknn;
-    double* dX = (double*)(ctx->dknn + bu);
-    int* dnbr = (int*)(ctx->dknn + bu + bx);
+    // the call scratch: the transposed unit-cube points, the points as given, the neighbour table.  No other claimant is
+    // called from here, and everything is queued on ctx->stream, which ns_end drains.
+    CallScratch cs(ctx, "gpry_ns_knn");
+    const auto rUT = cs.take<double>(n * d), rX = cs.take<double>(n * d); const auto rnbr = cs.take<int>(n * k);
+    GPRY_TRY(cs.claim());
+    double *dUT = cs.at(rUT), *dX = cs.at(rX);
+    int* dnbr = cs.at(rnbr);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
     HIP_TRY(ctx, hipMemcpyAsync(dX, X, sizeof(double) * n * d, hipMemcpyHostToDevice, ctx->stream));

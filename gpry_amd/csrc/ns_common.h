@@ -253,6 +253,24 @@ struct NsStage {
     }
 };
 
+// ---- the checks the point-batch entry points share (hessian.hip, joint.hip, theta_grad.hip, predict_thetas.hip,
+// predict_without.hip, var_theta_grad.hip): every coordinate of the npts rows of X is finite ...
+static int check_points_finite(gpry_ctx* ctx, const char* who, const double* X, int64_t npts) {
+    const int d = ctx->d;
+    for (int64_t e = 0; e < npts * d; e++)
+        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "%s: a coordinate of point %lld is not finite", who, (long long)(e / d));
+    return 0;
+}
+// ... and the x-affine map, where the model has one, divides by a finite non-zero span
+static int check_x_affine(gpry_ctx* ctx, const char* who) {
+    if (!ctx->tf.has_x_affine) return 0;
+    for (int k = 0; k < ctx->d; k++)
+        if (!(ctx->tf.x_span[k] != 0.0) || !isfinite(ctx->tf.x_span[k]) || !isfinite(ctx->tf.x_lo[k]))
+            return gpry_fail(ctx, -1, "%s: affine map of X: span %g, offset %g in dimension %d", who, ctx->tf.x_span[k],
+                             ctx->tf.x_lo[k], k);
+    return 0;
+}
+
 // ---- the argument checks the chain entry points share (mcmc.hip, mcmc_ladders.hip, hmc.hip) --------
 // rung < 0: the one temperature of a plain chain call
 static int ns_check_temperature(gpry_ctx* ctx, const char* who, double T, int rung = -1) {

@@ -262,13 +262,8 @@ int pt_run(gpry_ctx* ctx, const double* thetas, int64_t B, const double* X, int6
     if (ctx->N > 0 && !ctx->have_theta) return gpry_fail(ctx, -1, "predict_thetas: no kernel id (call gpry_set_theta)");
     GPRY_TRY(objective_entry(ctx, "predict_thetas", thetas, B));
     const int d = ctx->d, w = ctx_ntheta(ctx);
-    for (int64_t e = 0; e < M * d; e++)
-        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "predict_thetas: a coordinate of point %lld is not finite", (long long)(e / d));
-    if (ctx->tf.has_x_affine)
-        for (int k = 0; k < d; k++)
-            if (!(ctx->tf.x_span[k] != 0.0) || !isfinite(ctx->tf.x_span[k]) || !isfinite(ctx->tf.x_lo[k]))
-                return gpry_fail(ctx, -1, "predict_thetas: affine map of X: span %g, offset %g in dimension %d", ctx->tf.x_span[k],
-                                 ctx->tf.x_lo[k], k);
+    GPRY_TRY(check_points_finite(ctx, "predict_thetas", X, M));
+    GPRY_TRY(check_x_affine(ctx, "predict_thetas"));
     std::vector<double> vlml((size_t)B, 0.0);
     std::vector<int> vinfo((size_t)B, 0);
 

@@ -25,13 +25,13 @@
 // of points or groups over calls, panels or batches, the other groups of the call or the context.  A point whose k*
 // underflows gives s = 0 exactly, and 0 and 0.
 //
-// State: reads V, alpha_, y_ and the scaled training rows; writes ctx->dpw (below) and the staging buffer ctx->dmc (the
-// points of one upload).  The scratch, in doubles, with R = min(PW_ROWS, the largest batch's rows rounded up to 128),
+// State: reads V, alpha_, y_ and the scaled training rows; writes the call scratch (CallScratch, common.h), which it holds
+// for the length of the call, and the staging buffer ctx->dmc (the points of one upload).  The scratch, in doubles, with
+// R = min(PW_ROWS, the largest batch's rows rounded up to 128),
 // pc = min(PW_PC, M rounded up to 128) and ns = pw_nsplit(Np):
 //   3 R Np  (VG, P, S)  +  Np pc  (panel)  +  R pc  (s)  +  ns R max(Np, pc)  (slices, ns > 1)  +  2 (R / 16) pc  (outputs)
 //   + the partial Grams of a batch (gpry_leave_out's, at most LGO_BATCH_DOUBLES) + 4160 per group of a batch (W, t)
-// and a few integers per group.  It is released with the context, and by gpry_set_train when the model's padded size falls
-// below half of the size it was last used with.
+// and a few integers per group.
 #include "ns_common.h"
 #include "lgo.h"
 #include <algorithm>
@@ -121,13 +121,8 @@ int gpry_predict_without(gpry_ctx* ctx, const int64_t* idx, const int64_t* offse
     if (ctx->d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "%s: d = %d > %d", who, ctx->d, GPRY_MAX_DIM);
     const int d = ctx->d;
     const int64_t N = ctx->N, Np = ctx->Np;
-    for (int64_t e = 0; e < M * d; e++)
-        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "%s: a coordinate of point %lld is not finite", who, (long long)(e / d));
-    if (ctx->tf.has_x_affine)
-        for (int k = 0; k < d; k++)
-            if (!(ctx->tf.x_span[k] != 0.0) || !isfinite(ctx->tf.x_span[k]) || !isfinite(ctx->tf.x_lo[k]))
-                return gpry_fail(ctx, -1, "%s: affine map of X: span %g, offset %g in dimension %d", who, ctx->tf.x_span[k],
-                                 ctx->tf.x_lo[k], k);
+    GPRY_TRY(check_points_finite(ctx, who, X, M));
+    GPRY_TRY(check_x_affine(ctx, who));
     std::vector<LgoGroup> groups;
     std::vector<int> sidx, perm;
     int64_t ncov = 0;
@@ -168,36 +163,37 @@ int gpry_predict_without(gpry_ctx* ctx, const int64_t* idx, const int64_t* offse
                 rbmap[(size_t)(b * (R / 16) + grow0[(size_t)g] / 16 + q)] = make_int2((int)(g - batch_first[(size_t)b]), q);
         }
 
-    const int64_t sz[18] = {(int64_t)sizeof(LgoGroup) * ngroups, 4 * nidx, 4 * ngroups, 8 * 2 * ngroups, 8 * LGO_MAX * LGO_MAX * gb_max,
-                            8 * LGO_MAX * gb_max, 4 * nbatch * R, 8 * nbatch * (R / 16), 4 * 2 * ngroups, 8 * part_max,
-                            8 * Np * R, 8 * R * Np, 8 * R * Np, 8 * Np * pcw, 8 * R * pcw,
-                            ns > 1 ? 8 * ns * R * std::max(Np, pcw) : 0, 8 * gb_max * pcw, 8 * gb_max * pcw};
-    int64_t off[19];
-    ns_layout(sz, off);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
     GPRY_TRY(ensure_pred_xs(ctx));
-    GPRY_TRY(dev_grow(ctx, &ctx->dpw, &ctx->pw_cap, off[18]));
-    ctx->pw_np = Np;
+    // The call scratch, in this order.  lgo_launch and pv_panel_launch take their buffers from here, the GEMM engine its
+    // slices (`split`), so nothing below claims it again; the points of an upload go through the staging buffer dmc, which is
+    // no part of it.  Everything is queued on ctx->stream, which ns_end drains.
+    CallScratch cs(ctx, who);
+    const auto rgroups = cs.take<LgoGroup>(ngroups); const auto ridx = cs.take<int>(nidx), rinfo = cs.take<int>(ngroups);
+    const auto rchilp = cs.take<double>(2 * ngroups), rW = cs.take<double>(LGO_MAX * LGO_MAX * gb_max), rz = cs.take<double>(LGO_MAX * gb_max);
+    const auto rrowidx = cs.take<int>(nbatch * R); const auto rrbmap = cs.take<int2>(nbatch * (R / 16));
+    const auto rgrow0gn = cs.take<int>(2 * ngroups);
+    const auto rpart = cs.take<double>(part_max), rVG = cs.take<double>(Np * R), rP = cs.take<double>(R * Np), rS = cs.take<double>(R * Np),
+               rKst = cs.take<double>(Np * pcw), rsv = cs.take<double>(R * pcw),
+               rsplit = cs.take<double>(ns > 1 ? ns * R * std::max(Np, pcw) : 0), rom = cs.take<double>(gb_max * pcw),
+               rov = cs.take<double>(gb_max * pcw);
+    GPRY_TRY(cs.claim());
     const int64_t xc = std::min<int64_t>(PW_XC, M);
     GPRY_TRY(dev_grow(ctx, &ctx->dmc, &ctx->mc_cap, (int64_t)sizeof(double) * xc * d));
-    uint8_t* b0 = ctx->dpw;
-    LgoGroup* dgroups = (LgoGroup*)(b0 + off[0]);
-    int *didx = (int*)(b0 + off[1]), *dinfo = (int*)(b0 + off[2]), *drowidx = (int*)(b0 + off[6]), *dgrow0 = (int*)(b0 + off[8]),
-        *dgn = dgrow0 + ngroups;
-    int2* drbmap = (int2*)(b0 + off[7]);
-    double *dchi = (double*)(b0 + off[3]), *dlp = dchi + ngroups, *dW = (double*)(b0 + off[4]), *dz = (double*)(b0 + off[5]),
-           *dpart = (double*)(b0 + off[9]), *VG = (double*)(b0 + off[10]), *P = (double*)(b0 + off[11]), *S = (double*)(b0 + off[12]),
-           *Kst = (double*)(b0 + off[13]), *sv = (double*)(b0 + off[14]), *split = ns > 1 ? (double*)(b0 + off[15]) : nullptr,
-           *om = (double*)(b0 + off[16]), *ov = (double*)(b0 + off[17]);
+    LgoGroup* dgroups = cs.at(rgroups);
+    int *didx = cs.at(ridx), *dinfo = cs.at(rinfo), *drowidx = cs.at(rrowidx), *dgrow0 = cs.at(rgrow0gn), *dgn = dgrow0 + ngroups;
+    int2* drbmap = cs.at(rrbmap);
+    double *dchi = cs.at(rchilp), *dlp = dchi + ngroups, *dW = cs.at(rW), *dz = cs.at(rz), *dpart = cs.at(rpart), *VG = cs.at(rVG),
+           *P = cs.at(rP), *S = cs.at(rS), *Kst = cs.at(rKst), *sv = cs.at(rsv), *split = cs.at(rsplit), *om = cs.at(rom), *ov = cs.at(rov);
     double* dX = reinterpret_cast<double*>(ctx->dmc);
     hipStream_t st = ctx->stream;
     const double y_std = ctx->tf.y_std, ys2 = y_std * y_std;
     std::vector<int> hinfo((size_t)ngroups, 0);
-    HIP_TRY(ctx, hipMemcpyAsync(dgroups, groups.data(), sz[0], hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(didx, sidx.data(), sz[1], hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(drowidx, rowidx.data(), sz[6], hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(drbmap, rbmap.data(), sz[7], hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dgroups, groups.data(), sizeof(LgoGroup) * ngroups, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(didx, sidx.data(), sizeof(int) * nidx, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(drowidx, rowidx.data(), sizeof(int) * nbatch * R, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(drbmap, rbmap.data(), sizeof(int2) * nbatch * (R / 16), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dgrow0, grow0.data(), 4 * ngroups, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dgn, gn.data(), 4 * ngroups, hipMemcpyHostToDevice, st));
     for (int64_t b = 0; b < nbatch; b++) {
@@ -249,7 +245,7 @@ int gpry_predict_without(gpry_ctx* ctx, const int64_t* idx, const int64_t* offse
             }
         }
     }
-    HIP_TRY(ctx, hipMemcpyAsync(hinfo.data(), dinfo, sz[2], hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * ngroups, hipMemcpyDeviceToHost, st));
     GPRY_TRY(ns_end(ctx, &tm, device_ms));
     // a group whose block of K^-1 is not positive definite: its rows are NaN, on their own
     for (int64_t g = 0; g < ngroups; g++) {

@@ -398,21 +398,26 @@ int gpry_svm_fit(gpry_ctx* ctx, const double* X, const uint8_t* finite, int64_t 
             lab[i] = finite[i] ? 1 : -1;
         }
     }
-    GPRY_TRY(dev_grow(ctx, &ctx->dsvm, &ctx->svm_cap, off[6]));
+    // the call scratch as one region: the device layout is the host image's, offset for offset.  No other claimant is called
+    // from here, and everything is queued on ctx->stream, which ns_end drains.
+    CallScratch cs(ctx, "gpry_svm_fit");
+    const auto rimg = cs.take<uint8_t>(off[6]);
+    GPRY_TRY(cs.claim());
+    uint8_t* dimg = cs.at(rimg);
     NsTimer tm;
     GPRY_TRY(ns_begin(ctx, &tm));
     hipStream_t st = ctx->stream;
-    const double* dXt = (const double*)(ctx->dsvm + off[0]);
-    double *da = (double*)(ctx->dsvm + off[1]), *dg = (double*)(ctx->dsvm + off[2]);
-    const signed char* dlab = (const signed char*)(ctx->dsvm + off[3]);
-    SvmStatus* dst = (SvmStatus*)(ctx->dsvm + off[4]);
-    double* dcache = (double*)(ctx->dsvm + off[5]);
+    const double* dXt = (const double*)(dimg + off[0]);
+    double *da = (double*)(dimg + off[1]), *dg = (double*)(dimg + off[2]);
+    const signed char* dlab = (const signed char*)(dimg + off[3]);
+    SvmStatus* dst = (SvmStatus*)(dimg + off[4]);
+    double* dcache = (double*)(dimg + off[5]);
     SvmStatus hs;
     memset(&hs, 0, sizeof(hs));
     int result = 1;
     {
         StageScope scope(ctx, "svm_fit");
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dsvm, host, (size_t)off[5], hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(dimg, host, (size_t)off[5], hipMemcpyHostToDevice, st));
         for (;;) {
             const long long left = (long long)max_iter - hs.n_iter;
             const long long iters = left < (long long)ctx->opt_svm_iters ? left : (long long)ctx->opt_svm_iters;

@@ -24,7 +24,8 @@
 // Setup, three launches: tg_rhs_kernel (U, one workgroup per training row), tg_vu_kernel (T = V U, one wave per row, the
 // lanes walk the row 64 columns at a time, fixed butterfly), tg_vtt_kernel (W = V^T T, one workgroup per 64 columns, the
 // waves take every fourth row, (w0 + w1) + (w2 + w3)).  Every sum has a fixed order: W's bits depend on the model alone.
-// The scratch (ctx->dtg, 2 Np TG_LD doubles): U column-major and, once T is formed, W row-major in its place; T row-major.
+// The call scratch (CallScratch, common.h; 2 Np TG_LD doubles, held for the length of the call): U column-major and, once
+// T is formed, W row-major in its place; T row-major.
 // Columns: the length scales at 0 .. 31, log C at TG_EX, log w at TG_EX + 1.  W is recomputed by every call.
 #include "ns_common.h"
 
@@ -236,9 +237,7 @@ int gpry_mean_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* y
     GPRY_TRY(require_model(ctx, true));
     if (ctx->d > GPRY_MAX_DIM) return gpry_fail(ctx, -1, "gpry_mean_theta_grad: d = %d > %d", ctx->d, GPRY_MAX_DIM);
     const int d = ctx->d, np = ctx_ntheta(ctx);
-    for (int64_t e = 0; e < npts * d; e++)
-        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "gpry_mean_theta_grad: a coordinate of point %lld is not finite",
-                                              (long long)(e / d));
+    GPRY_TRY(check_points_finite(ctx, "gpry_mean_theta_grad", X, npts));
     // (the mean needs no box: ns_args is handed the unit one)
     double lo[GPRY_MAX_DIM], hi[GPRY_MAX_DIM];
     for (int k = 0; k < GPRY_MAX_DIM; k++) { lo[k] = 0.0; hi[k] = 1.0; }
@@ -246,8 +245,12 @@ int gpry_mean_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* y
     GPRY_TRY(ns_args(ctx, "gpry_mean_theta_grad", lo, hi, 0, &a, &kp, &ap));
     const int64_t N = ctx->N, Np = ctx->Np;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    GPRY_TRY(dev_grow(ctx, &ctx->dtg, &ctx->tg_cap, 2 * Np * TG_LD));
-    double *U = ctx->dtg, *T = ctx->dtg + Np * TG_LD, *W = U;
+    // the call scratch: U (and W in its place), T.  The point batches below stage through dmc (NsStage), which is no part
+    // of it; every launch is on ctx->stream, drained by the last st.end().
+    CallScratch cs(ctx, "gpry_mean_theta_grad");
+    const auto rU = cs.take<double>(Np * TG_LD), rT = cs.take<double>(Np * TG_LD);
+    GPRY_TRY(cs.claim());
+    double *U = cs.at(rU), *T = cs.at(rT), *W = U;
     const bool wide = d > 16;
     double ms_total = 0.0;
     {

@@ -32,11 +32,10 @@
 // npts, positions, the other points of a panel, the split of a batch over panels, chunks or calls, or the context.  A
 // point whose k* underflows gives t = q = 0 exactly, and [y_std^2 C, 0 .., y_std^2 w].
 //
-// State: reads V, the scaled training rows, the noise vector and the affine map; writes ctx->dvtg (doubles: d Np^2 for the
-// dK_a, then with pc = min(vg_panel(Np), npts rounded up to 128) 3 Np pc for K*, T and Q, d Np pc for the products, (Np / 128) 35 pc
-// for the slices' sums and the batch items) and the staging buffer ctx->dmc (the points and the outputs of one chunk of
-// VG_CHUNK points).  dvtg is released with the context, and by gpry_set_train when the model falls below half of the
-// footprint it was sized for.
+// State: reads V, the scaled training rows, the noise vector and the affine map; writes the call scratch (CallScratch,
+// common.h; held for the length of the call; doubles: d Np^2 for the dK_a, then with pc = min(vg_panel(Np), npts rounded up to
+// 128) 3 Np pc for K*, T and Q, d Np pc for the products, (Np / 128) 35 pc for the slices' sums and the batch items) and the
+// staging buffer ctx->dmc (the points and the outputs of one chunk of VG_CHUNK points).
 #include "ns_common.h"
 #include <algorithm>
 
@@ -46,7 +45,6 @@
 #define VG_SLICE 128                        // training rows per workgroup of the sums: the slices are a function of Np alone
 #define VG_EX GPRY_MAX_DIM                  // slot of |t|^2 in a slice's sums; |q|^2 and sum (noise + w) q^2 behind it
 #define VG_NC (GPRY_MAX_DIM + 3)
-#define VG_ITEM_DOUBLES ((int64_t)((GPRY_MAX_DIM * sizeof(GemmBatchItem) + 7) / 8))
 static_assert(GPRY_VAR_THETA_GRAD_PANEL % 128 == 0 && VG_PC_MAX % GPRY_VAR_THETA_GRAD_PANEL == 0 && VG_CHUNK % VG_PC_MAX == 0,
               "panels are whole engine tiles inside a chunk");
 // points per panel, a function of the model size alone: Np pc = 2^22, so that T = V K* and Q = V^T T hand the engine 256 tiles
@@ -187,23 +185,24 @@ int gpry_var_theta_grad(gpry_ctx* ctx, const double* X, int64_t npts, double* va
     const int64_t N = ctx->N, Np = ctx->Np;
     if (Np > VG_MAX_NP)
         return gpry_fail(ctx, -1, "%s: %lld padded rows exceed the limit of %d", who, (long long)Np, VG_MAX_NP);
-    for (int64_t e = 0; e < npts * d; e++)
-        if (!isfinite(X[e])) return gpry_fail(ctx, -1, "%s: a coordinate of point %lld is not finite", who, (long long)(e / d));
-    if (ctx->tf.has_x_affine)
-        for (int k = 0; k < d; k++)
-            if (!(ctx->tf.x_span[k] != 0.0) || !isfinite(ctx->tf.x_span[k]) || !isfinite(ctx->tf.x_lo[k]))
-                return gpry_fail(ctx, -1, "%s: affine map of X: span %g, offset %g in dimension %d", who, ctx->tf.x_span[k],
-                                 ctx->tf.x_lo[k], k);
+    GPRY_TRY(check_points_finite(ctx, who, X, npts));
+    GPRY_TRY(check_x_affine(ctx, who));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     GPRY_TRY(ensure_pred_xs(ctx));
     const int64_t pc = vg_panel(Np), pcw = std::min<int64_t>(pc, round_up(npts, 128));
     const int64_t sq = Np * Np, pan = Np * pcw;
     const int nslice = (int)(Np / VG_SLICE);
-    const int64_t o_kst = (int64_t)d * sq, o_t = o_kst + pan, o_q = o_t + pan, o_p = o_q + pan, o_part = o_p + (int64_t)d * pan,
-                  o_items = o_part + (int64_t)nslice * VG_NC * pcw;
-    GPRY_TRY(dev_grow(ctx, &ctx->dvtg, &ctx->vtg_cap, o_items + VG_ITEM_DOUBLES));
-    double *Km = ctx->dvtg, *Kst = Km + o_kst, *Tm = Km + o_t, *Qm = Km + o_q, *Pm = Km + o_p, *part = Km + o_part;
-    GemmBatchItem* items = reinterpret_cast<GemmBatchItem*>(Km + o_items);
+    // The call scratch: the d matrices dK_a, the panel K*, T, Q, the d products of a panel, the slices' sums, the batch items
+    // of the product.  lml_hess_km_launch and pv_panel_launch take their buffers from here and claim nothing; the points and
+    // outputs of a chunk stage through dmc (NsStage), which is no part of it.  Every launch is on ctx->stream, drained by the
+    // last stg.end().
+    CallScratch cs(ctx, who);
+    const auto rKm = cs.take<double>((int64_t)d * sq), rKst = cs.take<double>(pan), rT = cs.take<double>(pan), rQ = cs.take<double>(pan),
+               rP = cs.take<double>((int64_t)d * pan), rpart = cs.take<double>((int64_t)nslice * VG_NC * pcw);
+    const auto ritems = cs.take<GemmBatchItem>(GPRY_MAX_DIM);
+    GPRY_TRY(cs.claim());
+    double *Km = cs.at(rKm), *Kst = cs.at(rKst), *Tm = cs.at(rT), *Qm = cs.at(rQ), *Pm = cs.at(rP), *part = cs.at(rpart);
+    GemmBatchItem* items = cs.at(ritems);
     const KernParams kp = make_kp(ctx);
     const AffParams ap = make_ap(ctx, kp.has_aff);
     const double ys2 = ctx->tf.y_std * ctx->tf.y_std;

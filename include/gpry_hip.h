@@ -1089,7 +1089,12 @@ int gpry_group_lml_batch(gpry_group* group, const double* thetas, int n_theta, i
  * *count = launches accumulated since gpry_timing_reset.  "lml_batch_shrinks" is a counter, not a timer: *count = the times a
  * batched objective of this context halved its chunk after an out-of-memory answer (any other failure is returned to the caller).
  * "capacity_rows" / "capacity_cols" are sizes, not timers: *count = the training rows / padded columns the context's buffers hold
- * (they grow with the largest model the context has seen and never shrink).  "batch_set_doubles" / "batch_chunk": the last
+ * (they grow with the largest model the context has seen and never shrink).  "scratch_bytes": *count = the bytes of the
+ * context's call scratch, the one device buffer that the entry points with private scratch (gpry_lml_hessian,
+ * gpry_var_theta_grad, gpry_mean_theta_grad, gpry_predict_without, gpry_predict_cov / gpry_sample_joint, gpry_loo /
+ * gpry_leave_out, gpry_svm_fit, gpry_ns_knn, gpry_ns_generation_phantoms) hold one at a time: the largest footprint any of
+ * them has needed, 0 once gpry_set_train has given it back (a model with 2 Np^2 below the square of the padded size the
+ * buffer last grew under).  "batch_set_doubles" / "batch_chunk": the last
  * batched objective of this context (gpry_lml_batch, gpry_loo_objective_batch) that ran as one chain -- *count = the doubles of
  * one theta's scratch set in its arena / the thetas one chain carried at the most (option "lml_batch_mb" holds
  * floor(mb * 2^20 / (8 * batch_set_doubles)) sets). */

@@ -25,7 +25,7 @@ N_REAL = len(cs.OPS) + len(cs.OPS) % 2          # the table against the library:
 CASES = {"a": cs.model_a(40), "b": cs.model_b(30)}
 
 
-@pytest.mark.parametrize("n", sorted({2, 4, 26, 50, N_REAL}))      # (50: the table before the later objective ops joined it)
+@pytest.mark.parametrize("n", sorted({2, 4, 26, 50, 54, N_REAL}))      # (50, 54: the table before later ops joined it)
 def test_sequences_hold_every_ordered_pair_exactly_once(n):
     seqs = list(cs.sequences(n))
     assert len(seqs) == n

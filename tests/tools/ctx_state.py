@@ -474,6 +474,35 @@ def _(dev, case):
     return dev.leave_out([r.choice(dev.N, min(s, dev.N), replace=False) for s in (1, 16, 17)])
 
 
+@op("predict_without", "predict_without")
+def _(dev, case):
+    r = case.rng("predict_without")
+    return dev.predict_without([r.choice(dev.N, min(s, dev.N), replace=False) for s in (1, 3)],
+                               case.points("predict_without", 37))
+
+
+# -- derivatives in theta, and the predictive under a batch of thetas
+@op("mean_theta_grad", "mean_theta_grad")
+def _(dev, case):
+    return dev.mean_theta_grad(case.points("mean_theta_grad", 37))
+
+
+@op("var_theta_grad", "var_theta_grad")
+def _(dev, case):
+    return dev.var_theta_grad(case.points("var_theta_grad", 37))
+
+
+def _predict_thetas(want_var):
+    def fn(dev, case):
+        thetas = np.array([case.theta_other(k) for k in (1, 2, 3)])
+        return dev.predict_thetas(thetas, case.points("predict_thetas", 37), want_var=want_var)
+    return fn
+
+
+op("predict_thetas", "predict_thetas")(_predict_thetas(False))
+op("predict_thetas_var", "predict_thetas:want_var")(_predict_thetas(True))
+
+
 @op("svm_fit", "svm_fit")
 def _(dev, case):
     X = case.rng("svm_fit").uniform(size=(65, case.d))
